@@ -1,7 +1,9 @@
 """Headline benchmark: VID key-frame detections / second, R101 Faster-RCNN + HVR (or SELSA) head,
 1000x600 frames (padded 608x1008), 300 proposals / frame, T = 15 frames / window.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3                  # the headline region alone: the contract keys
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full           # + every other measurement and check below
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed call's detections as DIR/*.npy
     python bench.py --gpus 2                      # launches the two ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
@@ -26,7 +28,11 @@ are identical to the eager ones (tests/test_graphs_gpu.py).  `--lanes 1 --no-gra
 GPU under torch.distributed.run, 127.0.0.1 rendezvous -- what tools/dist_test.sh:9-10 does for the reference) and refuses
 loudly when fewer than N devices are visible.
 
-JSON line (one line, numbers only; README.md "Reading the bench line" says what every key means).  After the contract keys:
+A plain run (no --full) sets up, warms up, times the headline region once (`--repeats`, default 1) and prints the contract keys
+(`metric`, `value`, `unit`, `n_gpus`, `steps`, `warmup`, `ms_per_step`, `higher_is_better`, `dtype`, `config`, `value_spread`,
+`per_rank`, `device`, `lib_sha16`); --full runs the headline region 5 times and everything below as well.
+
+JSON line (one line, numbers only; README.md "Reading the bench line" says what every key means).  With --full, after the contract keys:
 `within_tolerance` -- the fastest compute mode whose detections meet north_star's tolerance against the CPU oracle on the same
 frames (dtype, frames/s, its relation-core roofline, its parity); `single_lane` -- the eager one-window-in-flight figure with its
 own spread (the figure to compare builds with); `roofline` (relation core, HIP events inside the timed region); `cpu_baseline`
@@ -79,8 +85,14 @@ def parse(argv=None):
     ap.add_argument('--ladder', default='f16,f16x2,f32',
                     help='other compute modes timed after the headline (eager single lane with the relation launches tagged + the '
                          'headline\'s graph replay), each with its detections compared with the CPU oracle: the `precision_ladder` table')
-    ap.add_argument('--repeats', type=int, default=5, help='the headline region (K steps) is timed this many times: value = the median, '
-                                                           '`value_spread` lists all of them')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline: the eager single-lane and batched regions, `roofline`, the precision ladder, '
+                         'the CPU oracle leg and the tolerance claim, per-class kernel times, side loops, hipGraph side legs, the training '
+                         'step and (N > 1) the all-reduce.  Without it a run sets up, warms up, times the K steps and prints the contract keys')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the detections of the last timed call (every clip of it) to DIR/*.npy (float32)')
+    ap.add_argument('--repeats', type=int, default=None, help='the headline region (K steps) is timed this many times (default 1, with --full 5): '
+                                                              'value = the median, `value_spread` lists all of them')
     ap.add_argument('--frames', type=int, default=15)
     ap.add_argument('--proposals', type=int, default=300)
     ap.add_argument('--tol-clips', type=int, default=8, help='synthetic clips the tolerance claim (`within_tolerance`) is checked on: the benchmark\'s + this many - 1 others')
@@ -104,7 +116,10 @@ def parse(argv=None):
     ap.add_argument('--stub', action='store_true',
                     help='host-logic self-test of the launcher / barrier / max-over-ranks / JSON contract without a GPU: the window '
                          'is a fixed sleep and the process group is gloo (tests/test_bench_launcher.py); never a measurement')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def host_cores():
@@ -377,6 +392,28 @@ def stream_side_measurement(head):
     return ss
 
 
+def synth_frames(ids):
+    """[len(ids),3,608,1008] f32 on the host: synthetic.synth_frame of every id, on a few host threads (every frame has its own
+    seeded generator, so the tensor is the same as one made frame by frame)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from hvrnet_amd import synthetic as S
+    with ThreadPoolExecutor(max(1, min(8, host_cores()))) as ex:
+        return torch.cat(list(ex.map(S.synth_frame, ids)), 0)
+
+
+def dump_outputs(path, clips, head):
+    """--dump-outputs: the detections of the last timed call, one file per clip of it and branch of the head (HVR: every test
+    branch; SELSA: one), DIR/clip<w>_branch<b>.npy, float32 [n, 6] = x1, y1, x2, y2, score, class index: the per-class [k, 5]
+    arrays a caller receives, concatenated in class order."""
+    os.makedirs(path, exist_ok=True)
+    for w, r in enumerate(clips):
+        branches = r if isinstance(r[0], (list, tuple)) else [r]
+        for b, br in enumerate(branches):
+            rows = [np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 5), np.full((len(a), 1), c, dtype=np.float32)], 1)
+                    for c, a in enumerate(br)]
+            np.save(os.path.join(path, 'clip%d_branch%d.npy' % (w, b)), np.concatenate(rows, 0) if rows else np.zeros((0, 6), np.float32))
+
+
 def lib_sha16():
     from hvrnet_amd import native
     return hashlib.sha256(open(native.LIB_PATH, 'rb').read()).hexdigest()[:16]
@@ -425,7 +462,8 @@ def stub_main(args, rank, local_rank, world):
         allt = [torch.zeros(1, dtype=torch.float64) for _ in range(world)]
         dist.all_gather(allt, torch.tensor([mine], dtype=torch.float64))
         per_rank = [float(x.item()) for x in allt]
-        ar = allreduce_leg(dist, world, args.head, dev, iters=2)
+        if args.full:
+            ar = allreduce_leg(dist, world, args.head, dev, iters=2)
     if rank == 0:
         out = dict(metric='STUB (launcher self-test, not a measurement)', value=round(world * args.steps / elapsed, 3), unit='frames/s',
                    n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=round(elapsed / args.steps * 1e3, 3),
@@ -476,7 +514,7 @@ def main(argv=None):
     model = hvrnet_amd.build_model(cfg, sd, dt, dev)
     # each rank works on its own clip: different synthetic frames per rank
     frame_ids = [rank * 1000 + i for i in range(T)]
-    frames = torch.cat([S.synth_frame(i) for i in frame_ids], 0).to(dev)  # [T,3,608,1008] resident in HBM
+    frames = synth_frames(frame_ids).to(dev)  # [T,3,608,1008] resident in HBM
     metas = [S.synth_meta() for _ in range(T)]
     # W clips per call / per graph: a divisor of --steps (a step is one window); clip 0 of lane 0 is `frames`, every other clip of
     # every lane has frames of its own (lane k, clip w: ids rank * 1000 + 100 * (k * W + w) + i), so the graphs in flight read
@@ -486,7 +524,7 @@ def main(argv=None):
         W -= 1
 
     def lane_frames(k):
-        clips = [frames if (k == 0 and w == 0) else torch.cat([S.synth_frame(rank * 1000 + 100 * (k * W + w) + i) for i in range(T)], 0).to(dev)
+        clips = [frames if (k == 0 and w == 0) else synth_frames([rank * 1000 + 100 * (k * W + w) + i for i in range(T)]).to(dev)
                  for w in range(W)]
         return clips[0] if W == 1 else torch.cat(clips, 0)
     frames_w = lane_frames(0)
@@ -497,12 +535,17 @@ def main(argv=None):
 
     lanes = [torch.cuda.Stream(device=dev) for _ in range(max(1, args.inflight))] if args.inflight > 1 else [None]
     turn = [0]
+    last_call = [None]   # every clip's result of the last call a timed region read (--dump-outputs)
+
+    def read_all(pend):
+        """result() of one pending window or of the W windows of a batched call -> [every clip's result]"""
+        if isinstance(pend, list):
+            return [p_.result() for p_ in pend]
+        return [pend.result()]
 
     def read(pend):
         """result() of one pending window or of the W windows of a batched call -> the first clip's result"""
-        if isinstance(pend, list):
-            return [p_.result() for p_ in pend][0]
-        return pend.result()
+        return read_all(pend)[0]
 
     def step(prev=None, w=1):
         """Enqueues one call -- one window, or w > 1 independent clips as one batch (detectors.forward_feat_clips) -- and collects
@@ -553,7 +596,8 @@ def main(argv=None):
         pend = None
         for _ in range(steps // w):
             pend = step(pend, w)
-        res = read(pend)
+        last_call[0] = read_all(pend)
+        res = last_call[0][0]
         sync()
         el = time.perf_counter() - t0
         spans = native.profile_end() if tags else None
@@ -570,13 +614,14 @@ def main(argv=None):
             with torch.cuda.stream(st):
                 gcs.append(GraphedClip(model, lane_frames(k) if w == W else frames, metas * w, rescale=True, n_out=1, throughput=n_lanes > 1, windows=w))
         pend_l = [None] * n_lanes
+        lane_out = [None] * n_lanes
         first = [None]
 
         def collect(k):
             if pend_l[k] is not None:
-                r = read(pend_l[k])
+                lane_out[k] = read_all(pend_l[k])
                 if k == 0:
-                    first[0] = r
+                    first[0] = lane_out[k][0]
                 pend_l[k] = None
 
         def replay(i):
@@ -601,6 +646,8 @@ def main(argv=None):
             drain()
             sync()
             times.append(time.perf_counter() - t0)
+        if repeats and steps // w:
+            last_call[0] = lane_out[(steps // w - 1) % n_lanes]
         del gcs
         return times, first[0]
 
@@ -649,6 +696,67 @@ def main(argv=None):
         return out_c
 
     median = lambda xs: sorted(xs)[len(xs) // 2]   # noqa: E731
+    eager_mode = 'eager launches, %d window(s) in flight'
+    graph_mode = 'hipGraph replay (one graph per %d independent clip(s), distinct frames per lane and clip), %d windows in flight on %d HIP streams'
+
+    def headline_figures(region_times):
+        """per region the slowest rank counts; the reported region is the median one -> (seconds, every rank's own, value_spread)"""
+        per_region = [over_ranks(t_) for t_ in region_times]
+        order = sorted(range(len(per_region)), key=lambda i: per_region[i][0])
+        elapsed, per_rank = per_region[order[len(order) // 2]]
+        value_spread = dict(regions=len(per_region), frames_per_s=[round(world * args.steps / t_[0], 2) for t_ in per_region],
+                            rel_spread=round((max(t_[0] for t_ in per_region) - min(t_[0] for t_ in per_region)) / elapsed, 4))
+        return elapsed, per_rank, value_spread
+
+    def contract_keys(elapsed, n_lanes, headline_mode, res):
+        """the head of the JSON line: the contract keys and the headline's configuration"""
+        branch = res[-1] if args.head == 'hvr' else res
+        n_det = int(sum(len(r) for r in branch))
+        return dict(metric='VID frames/sec, R101 Faster-RCNN+%s, 1000x600, %d props, T=%d' % (args.head.upper(), n_prop, T),
+                    value=round(world * args.steps / elapsed, 3), unit='frames/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
+                    ms_per_step=round(elapsed / args.steps * 1e3, 3), higher_is_better=True, scaling='weak', vs_baseline=None,
+                    dtype=args.dtype, data='synthetic',
+                    config=dict(workload='configs[2]: faster_rcnn_r101_hrnmp_c5 inference, clip mode' if args.head == 'hvr'
+                                else 'configs[1]: faster_rcnn_r101_selsa_c5 inference, clip mode',
+                                frames_per_window=T, proposals_per_frame=n_prop, input='3x600x1000 padded to 608x1008',
+                                parallelism='dp%d independent clips, no collectives' % world, windows_in_flight=n_lanes * (W if headline_mode.startswith('hipGraph') else 1), clips_per_graph=W, launch=headline_mode,
+                                key_frame_detections=n_det))
+
+    def closing_keys(out, per_rank):
+        out['gpus_requested'] = args.gpus
+        out['per_rank'] = [dict(rank=i, frames_per_s=round(args.steps / t_, 3)) for i, t_ in enumerate(per_rank)]
+        out['rccl_world_size'] = dist.get_world_size() if world > 1 else 1
+        prop = torch.cuda.get_device_properties(dev)
+        out['device'] = dict(name=prop.name, cus=prop.multi_processor_count, hbm_gb=round(prop.total_memory / 2 ** 30, 1))
+        out['lib_sha16'] = lib_sha16()
+
+    if not args.full:
+        # ---- a plain run: the headline region alone -- set-up, warm-up, the K timed steps (`repeats` times, default once) and the
+        # contract keys; everything else this file measures or checks runs with --full ----
+        if args.lanes > 1 and not args.no_graphs and args.inflight == 1:
+            n_lanes = args.lanes
+            region_times, res = graph_regions(n_lanes, args.steps, args.warmup, max(1, args.repeats), W)
+            headline_mode = graph_mode % (W, n_lanes * W, n_lanes)
+        else:
+            n_lanes = max(1, args.inflight)
+            region_times = []
+            for r in range(max(1, args.repeats)):
+                el, res, _ = timed(args.steps, args.warmup if r == 0 else 1)
+                region_times.append(el)
+            headline_mode = eager_mode % n_lanes
+        elapsed, per_rank, value_spread = headline_figures(region_times)
+        if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, last_call[0], args.head)
+            out = contract_keys(elapsed, n_lanes, headline_mode, res)
+            out['value_spread'] = value_spread
+            closing_keys(out, per_rank)
+            print(json.dumps(out, separators=(',', ':')))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # ---- region (1): the eager single-lane loop, relation launches tagged; timed `repeats` times (at least 3) ----
     sl_times, rel = [], {}
     for r in range(max(1, min(args.repeats, 3))):
@@ -663,6 +771,7 @@ def main(argv=None):
                        rel_spread=round((max(sl_times) - min(sl_times)) / mine, 4))
     rel_single = rel
     res_single = res   # the eager one-window-per-call result of `frames` (what a one-clip graph has to reproduce bit for bit)
+    head_last = last_call[0]
     # ---- region (1b): the same loop with W clips per call (what a graph of the headline region holds): the relation core's grouped
     # calls tagged -- `roofline` is taken HERE when W > 1 (units_per_launch = W), the one-window region above stays as `roofline_one_window` ----
     batched_lane, batched_vs_single = None, {}
@@ -677,20 +786,18 @@ def main(argv=None):
         bm = min(b_times)
         batched_lane = dict(frames_per_s=round(args.steps / bm, 3), ms_per_step=round(bm / args.steps * 1e3, 3), steps=args.steps, clips_per_call=W)
         batched_vs_single = {args.dtype: clip_distance(args.head, res, res_single)}   # clip 0 of the W-clip call against the one-window call
-    headline_mode = 'eager launches, %d window(s) in flight' % max(1, args.inflight)
+    headline_mode = eager_mode % max(1, args.inflight)
     n_lanes = max(1, args.inflight)
     region_times = sl_times
     if args.lanes > 1 and not args.no_graphs and args.inflight == 1:
         # ---- headline region: K windows replayed from hipGraphs on `lanes` HIP streams in turn, timed `repeats` times ----
         n_lanes = args.lanes
         region_times, res = graph_regions(n_lanes, args.steps, args.warmup, max(1, args.repeats), W)
-        headline_mode = 'hipGraph replay (one graph per %d independent clip(s), distinct frames per lane and clip), %d windows in flight on %d HIP streams' % (W, n_lanes * W, n_lanes)
-    # per region the slowest rank counts; the reported region is the median one
-    per_region = [over_ranks(t_) for t_ in region_times]
-    order = sorted(range(len(per_region)), key=lambda i: per_region[i][0])
-    elapsed, per_rank = per_region[order[len(order) // 2]]
-    value_spread = dict(regions=len(per_region), frames_per_s=[round(world * args.steps / t_[0], 2) for t_ in per_region],
-                        rel_spread=round((max(t_[0] for t_ in per_region) - min(t_[0] for t_ in per_region)) / elapsed, 4))
+        headline_mode = graph_mode % (W, n_lanes * W, n_lanes)
+        head_last = last_call[0]
+    elapsed, per_rank, value_spread = headline_figures(region_times)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head_last, args.head)
 
     # ---- the precision ladder: the same window in the other compute modes (rank 0, N = 1) ----
     ladder = {}
@@ -909,20 +1016,10 @@ def main(argv=None):
         # The line is ordered for a reader of its first kilobytes: the contract keys, then the figure that carries north_star's tolerance
         # (`within_tolerance`), the steering figure (`single_lane`), `roofline`, `cpu_baseline`, the ladder; side loops last.  What each
         # key means is in README.md ("Reading the bench line"); the line itself carries numbers.
-        branch = res[-1] if args.head == 'hvr' else res
-        n_det = int(sum(len(r) for r in branch))
         peak = MFMA_PEAK_TF[args.dtype]
         roofline = roofline_of(args.dtype, rel, W)
         roofline_one = roofline_of(args.dtype, rel_single, 1) if W > 1 else None
-        out = dict(metric='VID frames/sec, R101 Faster-RCNN+%s, 1000x600, %d props, T=%d' % (args.head.upper(), n_prop, T),
-                   value=round(world * args.steps / elapsed, 3), unit='frames/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
-                   ms_per_step=round(elapsed / args.steps * 1e3, 3), higher_is_better=True, scaling='weak', vs_baseline=None,
-                   dtype=args.dtype, data='synthetic',
-                   config=dict(workload='configs[2]: faster_rcnn_r101_hrnmp_c5 inference, clip mode' if args.head == 'hvr'
-                               else 'configs[1]: faster_rcnn_r101_selsa_c5 inference, clip mode',
-                               frames_per_window=T, proposals_per_frame=n_prop, input='3x600x1000 padded to 608x1008',
-                               parallelism='dp%d independent clips, no collectives' % world, windows_in_flight=n_lanes * (W if headline_mode.startswith('hipGraph') else 1), clips_per_graph=W, launch=headline_mode,
-                               key_frame_detections=n_det))
+        out = contract_keys(elapsed, n_lanes, headline_mode, res)
         want = None
         cpu = None
         wants, wants64, noise_floor, want_props = [], [], None, []
@@ -1075,12 +1172,7 @@ def main(argv=None):
                 return c
             out['precision_ladder'] = [compact(r) for r in rows]
         out['kernel_classes'] = kc
-        out['gpus_requested'] = args.gpus
-        out['per_rank'] = [dict(rank=i, frames_per_s=round(args.steps / t_, 3)) for i, t_ in enumerate(per_rank)]
-        out['rccl_world_size'] = dist.get_world_size() if world > 1 else 1
-        prop = torch.cuda.get_device_properties(dev)
-        out['device'] = dict(name=prop.name, cus=prop.multi_processor_count, hbm_gb=round(prop.total_memory / 2 ** 30, 1))
-        out['lib_sha16'] = lib_sha16()
+        closing_keys(out, per_rank)
         if ref_loop_fps is not None:
             out['ref_loop'] = dict(frames_per_s_per_gpu=round(ref_loop_fps, 2), steps=n_loop)
             # ~650 GF (HVR) / 504 GF (SELSA) per output frame with the per-frame cache (SURVEY.md 8d "stream mode")

@@ -17,11 +17,14 @@ import os
 import sys
 import types
 
-import numpy as np
-import torch
-
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+from tests.golden import numerics  # noqa: E402
+
+numerics.pin()   # record on the CPU numeric path the tests replay on (numerics.py)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 REF = '/root/reference'
 OUT = os.path.dirname(os.path.abspath(__file__))
 
@@ -228,7 +231,7 @@ def save(name, **arrays):
 def main():
     import warnings
     warnings.filterwarnings('ignore')
-    torch.set_num_threads(8)
+    torch.set_num_threads(numerics.THREADS)
     ref = install_reference()
     from hvrnet_amd import synthetic as S
     from oracle import hvr_oracle as O
@@ -494,6 +497,46 @@ def main():
         out14[tag + '_recall_c0'] = np.asarray(res[0]['recall'])
         out14[tag + '_precision_c0'] = np.asarray(res[0]['precision'])
     save('g14_eval_map', **out14)
+
+    # ---- G16 the two shipped config files as Config.fromfile reads them, G17 nms_cpu.cpp on random boxes ----
+    save_configs('g16_configs')
+    g17 = {}
+    for seed in range(5):
+        g17['seed%d_keep' % seed] = ref.nms_cpu.nms(C.boxes(500, 4000 + seed), 0.5)
+    save('g17_nms_random', **g17)
+
+
+CONFIG_FILES = ('faster_rcnn_r101_selsa_c5.py', 'faster_rcnn_r101_hrnmp_c5.py')
+CONFIG_SECTIONS = ('model', 'train_cfg', 'test_cfg')
+
+
+def tag_tuples(v):
+    """JSON has no tuple: a tuple is stored as {"__tuple__": [...]} (tests/test_host_logic.py restores it)."""
+    if isinstance(v, dict):
+        return {k: tag_tuples(x) for k, x in v.items()}
+    if isinstance(v, tuple):
+        return {'__tuple__': [tag_tuples(x) for x in v]}
+    if isinstance(v, list):
+        return [tag_tuples(x) for x in v]
+    return v
+
+
+def save_configs(name):
+    """The settings the tests compare (model / train_cfg / test_cfg) of each shipped config file, read by Config.fromfile."""
+    import json
+    from hvrnet_amd.config import Config
+    if ONLY and not any(name.startswith(t) for t in ONLY):
+        return
+    rec = {}
+    for f in CONFIG_FILES:
+        cfg = Config.fromfile(os.path.join(REF, 'configs', f))
+        rec[f] = {s: tag_tuples(cfg[s].to_dict()) for s in CONFIG_SECTIONS}
+    path = os.path.join(OUT, name + '.json')
+    with open(path, 'w') as fh:
+        json.dump(rec, fh, indent=1, sort_keys=True)
+        fh.write('\n')
+    print('wrote %s (%.1f KB)' % (path, os.path.getsize(path) / 1024))
+
 
 if __name__ == '__main__':
     main()

@@ -18,7 +18,7 @@ def _run(args, extra_env=None):
 
 
 def test_gpus_2_launches_two_ranks_and_reports_the_slowest():
-    r = _run(['--gpus', '2', '--stub', '--steps', '10', '--warmup', '1'])
+    r = _run(['--gpus', '2', '--stub', '--steps', '10', '--warmup', '1', '--full'])   # (--full: the all-reduce leg)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout          # rank 0 prints ONE json line

@@ -3,6 +3,7 @@ BatchNorm folding, the window loop, the C-ABI export table, and the rule that th
 touches the oracle."""
 import ast
 import ctypes
+import json
 import os
 import re
 import sys
@@ -15,7 +16,27 @@ from hvrnet_amd import backbone, native, registry, synthetic, window
 from hvrnet_amd.config import Config, ConfigDict, hvr_config, selsa_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_CFG = '/root/reference/configs'
+# the shipped config files' model / train_cfg / test_cfg as Config.fromfile read them (tests/golden/make_golden.py)
+REF_CFG = os.path.join(ROOT, 'tests', 'golden', 'g16_configs.json')
+
+
+def _untag(v):
+    if isinstance(v, dict):
+        if set(v) == {'__tuple__'}:
+            return tuple(_untag(x) for x in v['__tuple__'])
+        return {k: _untag(x) for k, x in v.items()}
+    if isinstance(v, list):
+        return [_untag(x) for x in v]
+    return v
+
+
+def _ref_config(name, tmp_path):
+    """The recorded sections of the shipped config file `name`, written out as a config file and read back by Config.fromfile."""
+    with open(REF_CFG) as f:
+        rec = json.load(f)[name]
+    path = tmp_path / name
+    path.write_text(''.join('%s = %r\n' % (k, _untag(v)) for k, v in sorted(rec.items())))
+    return Config.fromfile(str(path))
 
 
 def _build(cfg):
@@ -49,10 +70,9 @@ def test_builtin_config_builds_and_state_dict_keys_are_the_checkpoint_contract(h
     assert tuple(model.state_dict()['bbox_head.selsa_1.linear_out_1.weight'].shape) == (1024, 1024, 1, 1)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason='reference tree not present')
 @pytest.mark.parametrize('name,builtin', [('faster_rcnn_r101_selsa_c5.py', selsa_config), ('faster_rcnn_r101_hrnmp_c5.py', hvr_config)])
-def test_reference_config_files_load_unchanged(name, builtin):
-    cfg = Config.fromfile(os.path.join(REF_CFG, name))
+def test_reference_config_files_load_unchanged(name, builtin, tmp_path):
+    cfg = _ref_config(name, tmp_path)
     assert cfg.test_cfg.rpn.nms_pre == 6000 and cfg.test_cfg.rcnn.nms.iou_thr == 0.3
     mine = builtin(frame_interval=10).model.to_dict()
     theirs = cfg.model.to_dict()
@@ -63,13 +83,12 @@ def test_reference_config_files_load_unchanged(name, builtin):
     assert type(model).__name__ == cfg.model.type
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason='reference tree not present')
 @pytest.mark.parametrize('name,builtin', [('faster_rcnn_r101_selsa_c5.py', 'selsa_train_config'), ('faster_rcnn_r101_hrnmp_c5.py', 'hvr_train_config')])
-def test_reference_train_cfg_builds_the_same_target_objects(name, builtin):
+def test_reference_train_cfg_builds_the_same_target_objects(name, builtin, tmp_path):
     """The shipped configs' train_cfg sections equal the built-in training configs and build assigners / samplers through
     hvrnet_amd.targets exactly as the reference's build_assigner / build_sampler would (same classes, same arguments)."""
     from hvrnet_amd import config as CFG, targets as T
-    cfg = Config.fromfile(os.path.join(REF_CFG, name))
+    cfg = _ref_config(name, tmp_path)
     mine = getattr(CFG, builtin)()
     assert cfg.train_cfg.to_dict() == mine.train_cfg.to_dict() and cfg.model.to_dict() == mine.model.to_dict()
     model = _build(Config(dict(model=cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)))

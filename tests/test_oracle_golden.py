@@ -1,6 +1,6 @@
 """Pins the CPU oracle (oracle/) to the reference: golden vectors produced by the reference's own
 modules (tests/golden/make_golden.py), the reference's doctest known-answers, the reference's
-nms_cpu.cpp compiled unmodified (oracle/_ref, when present), and hand-derived RoIAlign geometry.
+nms_cpu.cpp compiled unmodified (oracle/_ref, when present; its keep lists recorded), and hand-derived RoIAlign geometry.
 Runs on CPU (-m "not gpu")."""
 import os
 import subprocess
@@ -10,10 +10,20 @@ import pytest
 import torch
 
 from hvrnet_amd import synthetic as S
-from tests.golden import cases as C
+from tests.golden import cases as C, numerics
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, 'tests', 'golden')
+
+
+@pytest.fixture(scope='module', autouse=True)
+def recorded_thread_count():
+    """How a product or a reduction is split over threads moves its float32 sum: replay on the thread count the vectors were
+    recorded with (tests/golden/numerics.py)."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(numerics.THREADS)
+    yield
+    torch.set_num_threads(n)
 
 
 @pytest.fixture(scope='module')
@@ -75,13 +85,16 @@ def test_g3_nms_against_reference_cpu_kernel(O):
 
 
 def test_nms_against_live_reference_build(O):
+    """Random boxes against nms_cpu.cpp's keep lists as recorded (g17), and against the live build too where this checkout has one."""
     from oracle import build_ref
+    g = gold('g17_nms_random')
     ref = build_ref.load_ref()
-    if ref is None:
-        pytest.skip('oracle/_ref not built (reference tree absent)')
     for seed in range(5):
         dets = C.boxes(500, 4000 + seed)
-        assert O.nms(dets, 0.5)[1].tolist() == ref.nms(dets, 0.5).tolist()
+        keep = O.nms(dets, 0.5)[1].tolist()
+        assert keep == g['seed%d_keep' % seed].tolist(), seed
+        if ref is not None:
+            assert keep == ref.nms(dets, 0.5).tolist(), seed
 
 
 def test_roi_align_hand_derived_geometry(O):

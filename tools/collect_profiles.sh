@@ -38,12 +38,12 @@ for G in 1 4; do
 done
 # (the traffic files are keyed to this build: put them where bench.py looks before the bench lines are taken)
 r=${ROUND:-r06}; cp $out/relation_traffic.json profiles/${r}_relation_traffic.json; cp $out/relation_traffic_g4.json profiles/${r}_relation_traffic_g4.json; cp $out/relation_traffic_f16x2_g4.json profiles/${r}_relation_traffic_f16x2_g4.json
-$T python bench.py --steps 20 --warmup 3 > $out/bench.json 2> $out/bench.err
-$T python bench.py --head selsa --steps 20 --warmup 3 --no-train-step > $out/bench_selsa.json 2>/dev/null
-$T python bench.py --frames 21 --steps 10 --warmup 2 --no-train-step --no-f32-leg --no-side-loops --quick > $out/bench_T21.json 2>/dev/null   # the shipped window length (frame_interval = 10)
+$T python bench.py --full --steps 20 --warmup 3 > $out/bench.json 2> $out/bench.err
+$T python bench.py --full --head selsa --steps 20 --warmup 3 --no-train-step > $out/bench_selsa.json 2>/dev/null
+$T python bench.py --full --frames 21 --steps 10 --warmup 2 --no-train-step --no-f32-leg --no-side-loops --quick > $out/bench_T21.json 2>/dev/null   # the shipped window length (frame_interval = 10)
 # kernel stats of the bench command (the eager single-lane region is where bench.py takes the relation core's HIP events; the
 # graph legs are skipped under the profiler: a kernel-trace of two graph lanes replaying did not come back in round 3)
-rm -rf /tmp/p_ks; $T rocprofv3 --kernel-trace --stats -d /tmp/p_ks -o bench -- python bench.py --steps 8 --warmup 4 --repeats 2 --no-graphs --no-f32-leg --no-cpu-baseline --no-train-step > $out/bench_prof.json 2> $out/bench_prof.err
+rm -rf /tmp/p_ks; $T rocprofv3 --kernel-trace --stats -d /tmp/p_ks -o bench -- python bench.py --full --steps 8 --warmup 4 --repeats 2 --no-graphs --no-f32-leg --no-cpu-baseline --no-train-step > $out/bench_prof.json 2> $out/bench_prof.err
 ROCPD_SPLIT=relation_scores_bt_kernel:100 $T python tools/rocpd_stats.py $(db /tmp/p_ks) > $out/bench_kernel_stats.txt
 $T python tools/rocpd_phases.py $(db /tmp/p_ks) 4 > $out/bench_window_phases.txt 2>&1
 $T python tools/window_breakdown.py --mode bf16 --iters 3 > $out/window_breakdown_bf16.txt 2>/dev/null
@@ -53,7 +53,7 @@ fi
 
 if [[ $parts == *B* ]]; then
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf /tmp/p_$c; $T rocprofv3 --kernel-trace --pmc $c -d /tmp/p_$c -o bench -- python bench.py --steps 2 --warmup 1 --repeats 1 --no-graphs --no-side-loops --no-f32-leg --no-cpu-baseline --no-train-step > /dev/null 2>&1
+  rm -rf /tmp/p_$c; $T rocprofv3 --kernel-trace --pmc $c -d /tmp/p_$c -o bench -- python bench.py --full --steps 2 --warmup 1 --repeats 1 --no-graphs --no-side-loops --no-f32-leg --no-cpu-baseline --no-train-step > /dev/null 2>&1
   $T python tools/rocpd_pmc.py $(db /tmp/p_$c) $c > $out/pmc_$(echo $c | tr A-Z a-z).txt
 done
 # SQ / TCC passes over every kernel of the headline window (the conv classes: MFMA-busy, LDS, waits)
@@ -62,7 +62,7 @@ for set in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VA
            "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SALU SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS" \
            "TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE"; do
   i=$((i+1)); rm -rf /tmp/w_$i
-  $T rocprofv3 --kernel-trace --pmc $set -d /tmp/w_$i -o w -- python bench.py --steps 1 --warmup 1 --repeats 1 --no-cpu-baseline --no-train-step --no-side-loops --no-graphs --no-f32-leg > /dev/null 2>&1
+  $T rocprofv3 --kernel-trace --pmc $set -d /tmp/w_$i -o w -- python bench.py --full --steps 1 --warmup 1 --repeats 1 --no-cpu-baseline --no-train-step --no-side-loops --no-graphs --no-f32-leg > /dev/null 2>&1
   echo "--- pass $i: $set" >> $out/window_pmc_sq.txt
   $T python tools/pmc_dump.py $(db /tmp/w_$i) _kernel >> $out/window_pmc_sq.txt 2>&1
 done
