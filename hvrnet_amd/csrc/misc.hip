@@ -621,8 +621,19 @@ __global__ void scale_rows_kernel(const T* __restrict__ w, const float* __restri
   }
 }
 
+// A product about to be stored as T, held as an f32 value.  For half, an empty asm the compiler cannot look through: without it a
+// product stored to half is folded into one v_fma_mixlo_f16 (the EXACT product rounded once to half), one ulp off (w * s).to(half)
+// wherever the f32 product is a half-way case -- and the pack kernels' eight-wide path (packed multiplies, separate conversions) did
+// not fold, so the same weight packed to two different values depending on the path.  (bf16 / f32 have no fused form.)
+template <typename T> __device__ __forceinline__ float f32_value(float v) { return v; }
+template <> __device__ __forceinline__ float f32_value<f16_t>(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
+
 // nn.Conv2d weight [Cout][Cin][KH][KW] (f32 master) * s[Cout] -> the conv kernel's operand [Cout][KH][KW][Cin] in T:
-// the permute, the frozen BatchNorm scale and the rounding to the compute dtype in one pass
+// the permute, the frozen BatchNorm scale and the rounding to the compute dtype in one pass.  The product is rounded to f32 first,
+// then to T, as torch's (w * s).to(T) does (f32_value: see above).
 template <typename T>
 __global__ void pack_conv_weight_kernel(const float* __restrict__ w, const float* __restrict__ s, T* __restrict__ out, int Cout, int Cin,
                                         int KK) {
@@ -631,7 +642,7 @@ __global__ void pack_conv_weight_kernel(const float* __restrict__ w, const float
     const int c = (int)(idx % Cin);
     const long r = idx / Cin;
     const int t = (int)(r % KK), o = (int)(r / KK);
-    ElemTraits<T>::store(out + idx, w[((long)o * Cin + c) * KK + t] * s[o]);
+    ElemTraits<T>::store(out + idx, f32_value<T>(w[((long)o * Cin + c) * KK + t] * s[o]));
   }
 }
 
@@ -686,7 +697,7 @@ __device__ __forceinline__ void pack_one(const PackItem* __restrict__ items, int
   const int c = (int)(e % it.Cin);
   const long r = e / it.Cin;
   const int t = (int)(r % it.KK), o = (int)(r / it.KK);
-  ElemTraits<T>::store(reinterpret_cast<T*>(it.eff) + e, it.w[((long)o * it.Cin + c) * it.KK + t] * it.s[o]);
+  ElemTraits<T>::store(reinterpret_cast<T*>(it.eff) + e, f32_value<T>(it.w[((long)o * it.Cin + c) * it.KK + t] * it.s[o]));
 }
 
 template <typename T>
@@ -709,7 +720,7 @@ __global__ void pack_conv_weights_multi_kernel(const PackItem* __restrict__ item
       const float* src = it.w + ((long)o * it.Cin + c) * it.KK + t;
       float lo4[4], hi4[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { lo4[j] = src[(long)j * it.KK] * sc; hi4[j] = src[(long)(j + 4) * it.KK] * sc; }
+      for (int j = 0; j < 4; ++j) { lo4[j] = f32_value<T>(src[(long)j * it.KK] * sc); hi4[j] = f32_value<T>(src[(long)(j + 4) * it.KK] * sc); }
       T* dst = reinterpret_cast<T*>(it.eff) + e;
       store4(dst, lo4);
       store4(dst + 4, hi4);

@@ -294,7 +294,7 @@ int hvr_unpack_conv_wgrad(const float* dw, const float* scale, float* out, int C
  * columns R .. dcols - 1 of dst zero; first_tile ascending, tiles = their sum): the transposed (1x1 / linear) and the rotated (KxK, one entry per
  * filter tap) operands of the input-gradient products, from the packed weights. */
 typedef struct { const float* w; const float* scale; void* out; int64_t first; int32_t Cout, Cin, KK, pad_; } hvr_pack_item;
-typedef struct { const void* src; void* dst; int64_t lds, ldd; int32_t R, C, first_tile, tiles_c, dcols, pad_; } hvr_transpose_item;   /* dcols: columns of dst written per row (R .. dcols - 1: zeros) */
+typedef struct { const void* src; void* dst; int64_t lds, ldd; int32_t R, C, first_tile, tiles_c, dcols, pad_; } hvr_transpose_item;   /* dcols: columns of dst written per row, a multiple of 8 (R .. dcols - 1: zeros; written 8 at a time) */
 int hvr_pack_conv_weights_multi(const hvr_pack_item* items_dev, int n, int64_t total, int out_dtype, void* stream);
 /* hvr_unpack_conv_wgrad for a table of layers in one launch (the outputs of hvr_gemm_splitk_batched): entry i's f32 product dw [Cout][KK][Cin]
  * times scale -> the parameter-layout gradient out [Cout][Cin][KK], added to it when accumulate != 0; first / total as above. */

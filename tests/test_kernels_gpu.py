@@ -630,7 +630,8 @@ def test_gemm_splitk_batched_equals_the_single_products(G, M, N, K):
 def test_unpack_conv_wgrads_multi_equals_the_per_layer_unpack():
     """hvr_unpack_conv_wgrads_multi: a table of layers' f32 products x scale -> parameter-layout gradients in one launch, added or written:
     bit-identical to hvr_unpack_conv_wgrad layer by layer."""
-    for Cout, Cin, KH, KW, n in ((64, 32, 3, 3, 4), (16, 64, 1, 1, 3), (10, 6, 3, 3, 3)):   # (the last: Cin % 4 != 0 -> the element-wise path)
+    for Cout, Cin, KH, KW, n in ((64, 32, 3, 3, 4), (16, 64, 1, 1, 3), (10, 6, 3, 3, 3)):   # (all three take the vector path: 540 elements per item
+        # are a multiple of 4 and every output is its own aligned allocation; the element-wise path: test_train_kernels_gpu.py)
         _unpack_multi_case(Cout, Cin, KH, KW, n)
 
 
@@ -781,7 +782,11 @@ def test_bottleneck_tail_next_says_when_it_does_not_apply():
     h3, r3 = torch.zeros((1, 16, 16, 256), **bf), torch.zeros((1, 16, 16, 1024), **bf)
     w3, b3 = torch.zeros((1024, 256), **bf), torch.zeros(1024, device=DEV)
     wn3, bn3 = torch.zeros((256, 1024), **bf), torch.zeros(256, device=DEV)
-    
+    assert not native.bottleneck_tail_next_supported(h3, None, r3, w3, b3, 1, wn3, bn3)  # layer 3 (Cn = 256): 256 pixels, under 512 panels
+    h3, r3 = torch.zeros((4, 128, 127, 256), **bf), torch.zeros((4, 128, 127, 1024), **bf)
+    assert not native.bottleneck_tail_next_supported(h3, None, r3, w3, b3, 1, wn3, bn3)  # 65 024 pixels: 508 panels of 128
+    h3, r3 = torch.zeros((4, 128, 128, 256), **bf), torch.zeros((4, 128, 128, 1024), **bf)
+    assert native.bottleneck_tail_next_supported(h3, None, r3, w3, b3, 1, wn3, bn3)      # exactly 512 x 128 = 65 536 pixels
     h1, r1 = torch.zeros((1, 16, 16, 64), **bf), torch.zeros((1, 16, 16, 256), **bf)
     w1, b1 = torch.zeros((256, 64), **bf), torch.zeros(256, device=DEV)
     wn1, bn1 = torch.zeros((64, 256), **bf), torch.zeros(64, device=DEV)
