@@ -8,8 +8,11 @@ __version__ = '0.1.0'
 from . import registry  # noqa: F401
 from .backbone import ResLayer, ResNet, enable_training, set_compute_dtype  # noqa: F401
 from .bbox_heads import BBoxHead, HRNMPBBoxHead, SelsaBBoxHead  # noqa: F401
+from .box_ops import (bbox_flip, bbox_mapping, bbox_mapping_back, merge_aug_bboxes, merge_aug_proposals,  # noqa: F401
+                      merge_aug_scores)
 from .config import Config, hvr_config, selsa_config  # noqa: F401
 from .detectors import HNMBRCNN, SelsaRCNN  # noqa: F401
+from .pipelines import FrameIngest, FrameIngestAug  # noqa: F401
 from .registry import build_detector  # noqa: F401
 from .roi_extractor import SingleRoIExtractor  # noqa: F401
 from .rpn_head import RPNHead  # noqa: F401

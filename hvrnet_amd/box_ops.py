@@ -5,6 +5,8 @@
   bbox2roi             mmdet/core/bbox/transforms.py:149-168         (memory plumbing)
   bbox2result          mmdet/core/bbox/transforms.py:181-199         (D2H + split per class)
   multiclass_nms       mmdet/core/post_processing/bbox_nms.py:6-66   (device kernel)
+  bbox_flip / bbox_mapping / bbox_mapping_back   mmdet/core/bbox/transforms.py:114-146          (device kernels)
+  merge_aug_proposals / merge_aug_bboxes / merge_aug_scores   mmdet/core/post_processing/merge_augs.py:8-77   (device kernels)
 """
 import numpy as np
 import torch
@@ -107,3 +109,79 @@ def multiclass_nms(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1, s
     dets, labels, n = native.multiclass_nms(boxes, scores, score_thr, iou_thr, max(int(max_num), 1))
     k = int(n.item())
     return dets[:k], labels[:k]
+
+
+# ---- test-time augmentation (single frame, list inputs: the reference's signatures on the window kernels of csrc/tta.hip) ----
+def _boxes2d(bboxes):
+    if not torch.is_tensor(bboxes):
+        raise NotImplementedError('the box mappings run on device tensors (no numpy / CPU fallback)')
+    assert bboxes.shape[-1] % 4 == 0
+    return bboxes.float().reshape(-1, 4)
+
+
+def _scalar_scale(scale_factor):
+    if not isinstance(scale_factor, (int, float)):
+        raise NotImplementedError('per-axis scale_factor arrays are outside the HVR hot path')
+    return float(scale_factor)
+
+
+def bbox_mapping(bboxes, img_shape, scale_factor, flip):
+    """Original image -> testing scale (transforms.py:131-136): boxes * scale_factor, then the horizontal flip."""
+    b = _boxes2d(bboxes)
+    if b.shape[0] == 0:
+        return bboxes.float().clone()
+    rows = torch.cat([b, b.new_zeros((b.shape[0], 1))], dim=1)[None]     # [1, n, 5]: one frame's (box, score) rows
+    return native.map_aug_rois(rows, [img_shape[1]], [_scalar_scale(scale_factor)], [flip])[0, :, 1:].reshape(bboxes.shape)
+
+
+def bbox_mapping_back(bboxes, img_shape, scale_factor, flip):
+    """Testing scale -> original image (transforms.py:139-143): un-flip, then a division by scale_factor."""
+    b = _boxes2d(bboxes)
+    if b.shape[0] == 0:
+        return bboxes.float().clone()
+    out, _ = native.merge_aug_dets(b[None].contiguous(), b.new_zeros((1, b.shape[0], 1)), [img_shape[1]], [_scalar_scale(scale_factor)], [flip])
+    return out.reshape(bboxes.shape)
+
+
+def bbox_flip(bboxes, img_shape):
+    """Horizontal flip (transforms.py:114-128), shape (..., 4 k)."""
+    return bbox_mapping(bboxes, img_shape, 1.0, True)
+
+
+def merge_aug_proposals(aug_proposals, img_metas, rpn_test_cfg):
+    """merge_augs.py:8-44 for one frame: list of [n_a, 5] proposals, each in its augmentation's coordinates -> [k, 5] at
+    original scale (mapped back, NMS at nms_thr with >=, descending score, first max_num).  One host read (k)."""
+    n = [int(p.shape[0]) for p in aug_proposals]
+    mx = max(max(n), 1)
+    dev = aug_proposals[0].device
+    props = torch.zeros((len(n), 1, mx, 5), dtype=torch.float32, device=dev)
+    for a, p in enumerate(aug_proposals):
+        props[a, 0, :n[a]] = p.float()
+    counts = torch.tensor(n, dtype=torch.int32).view(-1, 1).to(dev)
+    merged, cnt = native.merge_aug_proposals(props, counts, [m['img_shape'][1] for m in img_metas],
+                                             [_scalar_scale(m['scale_factor']) for m in img_metas], [m['flip'] for m in img_metas],
+                                             rpn_test_cfg['nms_thr'], rpn_test_cfg['max_num'])
+    return merged[0, :int(cnt.item())]
+
+
+def merge_aug_bboxes(aug_bboxes, aug_scores, img_metas, rcnn_test_cfg):
+    """merge_augs.py:47-70: list of [n, 4] boxes (class-agnostic) + list of [n, ncls] scores (or None), img_metas a list of
+    one-element lists -> (mean of the boxes mapped back, mean of the scores)."""
+    boxes = torch.stack([b.float() for b in aug_bboxes], 0)
+    if boxes.shape[2] != 4:
+        raise NotImplementedError('class-specific boxes are outside the HVR hot path')
+    scores = torch.stack([s.float() for s in aug_scores], 0) if aug_scores is not None else boxes.new_zeros(boxes.shape[:2] + (1,))
+    mb, ms = native.merge_aug_dets(boxes, scores, [m[0]['img_shape'][1] for m in img_metas],
+                                   [_scalar_scale(m[0]['scale_factor']) for m in img_metas], [m[0]['flip'] for m in img_metas])
+    return mb if aug_scores is None else (mb, ms)
+
+
+def merge_aug_scores(aug_scores):
+    """merge_augs.py:73-78."""
+    if not isinstance(aug_scores[0], torch.Tensor):
+        return np.mean(aug_scores, axis=0)
+    scores = torch.stack([s.float() for s in aug_scores], 0)
+    flat = scores.reshape(scores.shape[0], -1, scores.shape[-1])
+    A = flat.shape[0]
+    _, ms = native.merge_aug_dets(flat.new_zeros((A, flat.shape[1], 4)), flat.contiguous(), [1.0] * A, [1.0] * A, [False] * A)
+    return ms.reshape(scores.shape[1:])

@@ -49,7 +49,12 @@ hipError_t run_rpn_loss(const float*, int, int, int, const long long*, const flo
 hipError_t run_ce_rows(const float*, int, int, int, const long long*, int, float*, hipStream_t);
 hipError_t run_triplet_margin(const void*, long, const void*, long, int, int, int, const long long*, const long long*, const long long*, int,
                               float, int, float*, float*, float*, float*, hipStream_t);
-hipError_t run_ingest(const uint8_t*, int, int, long, float*, int, int, int, int, const float*, const float*, int, hipStream_t);
+hipError_t run_ingest(const uint8_t*, int, int, long, float*, int, int, int, int, const float*, const float*, int, int, hipStream_t);
+size_t tta_merge_proposals_workspace_bytes(int A, int T, int mx);
+hipError_t run_tta_merge_proposals(const float*, const int*, int, int, int, const float*, const float*, const int*, float, int, float*, int*, void*,
+                                   hipStream_t);
+hipError_t run_tta_map_rois(const float*, int, int, int, const float*, const float*, const int*, float*, hipStream_t);
+hipError_t run_tta_merge_dets(const float*, const float*, int, int, int, const float*, const float*, const int*, float*, float*, hipStream_t);
 hipError_t run_mining_argreduce(const float*, int, int, long, const long long*, const long long*, long long*, hipStream_t);
 hipError_t run_relation_dscore(const void*, const void*, const void*, const void*, void*, int, long, int, long, long, float, int, hipStream_t);
 hipError_t run_im2col_stem(const float*, void*, int, int, int, int, int, int, int, hipStream_t);
@@ -1104,15 +1109,66 @@ int hvr_triplet_margin(const void* q, int64_t ldq, const void* k, int64_t ldk, i
                       "hvr_triplet_margin");
 }
 
-int hvr_ingest_frame(const uint8_t* src, int src_h, int src_w, int64_t src_pitch, float* dst, int new_h, int new_w, int pad_h, int pad_w,
-                     const float* mean3, const float* std3, int to_rgb, void* stream) {
+int hvr_ingest_frame_flip(const uint8_t* src, int src_h, int src_w, int64_t src_pitch, float* dst, int new_h, int new_w, int pad_h, int pad_w,
+                          const float* mean3, const float* std3, int to_rgb, int flip, void* stream) {
   if (!src || !dst || !mean3 || !std3) return fail(HVR_EINVAL, "null pointer");
   if (src_h <= 0 || src_w <= 0 || new_h <= 0 || new_w <= 0 || pad_h < new_h || pad_w < new_w || src_pitch < 3L * src_w)
     return fail(HVR_EINVAL, "bad ingest shape");
   for (int c = 0; c < 3; ++c)
     if (std3[c] == 0.f) return fail(HVR_EINVAL, "std must be non-zero");
-  return check_launch(run_ingest(src, src_h, src_w, src_pitch, dst, new_h, new_w, pad_h, pad_w, mean3, std3, to_rgb, (hipStream_t)stream),
-                      "hvr_ingest_frame");
+  return check_launch(run_ingest(src, src_h, src_w, src_pitch, dst, new_h, new_w, pad_h, pad_w, mean3, std3, to_rgb, flip != 0, (hipStream_t)stream),
+                      "hvr_ingest_frame_flip");
+}
+
+int hvr_ingest_frame(const uint8_t* src, int src_h, int src_w, int64_t src_pitch, float* dst, int new_h, int new_w, int pad_h, int pad_w,
+                     const float* mean3, const float* std3, int to_rgb, void* stream) {
+  return hvr_ingest_frame_flip(src, src_h, src_w, src_pitch, dst, new_h, new_w, pad_h, pad_w, mean3, std3, to_rgb, 0, stream);
+}
+
+// ---- test-time augmentation: box plumbing ----
+static int tta_check_augs(int A, const float* img_w, const float* scale_factor, const int32_t* flip) {
+  if (!img_w || !scale_factor || !flip) return fail(HVR_EINVAL, "null pointer");
+  if (A <= 0 || A > 16) return fail(HVR_EUNSUPPORTED, "1 <= augmentations <= 16, got %d", A);
+  for (int a = 0; a < A; ++a)
+    if (!(scale_factor[a] > 0.f) || !(img_w[a] > 0.f)) return fail(HVR_EINVAL, "augmentation %d: scale_factor and img_w must be positive", a);
+  return HVR_OK;
+}
+
+size_t hvr_merge_aug_proposals_workspace_bytes(int A, int T, int mx) {
+  return (A > 0 && T > 0 && mx > 0 && (long)A * mx <= 8192) ? tta_merge_proposals_workspace_bytes(A, T, mx) : 0;
+}
+
+int hvr_merge_aug_proposals(const float* proposals, const int32_t* counts, int A, int T, int mx, const float* img_w,
+                            const float* scale_factor, const int32_t* flip, float nms_thr, int max_num, float* merged,
+                            int32_t* merged_counts, void* ws, size_t ws_bytes, void* stream) {
+  if (!proposals || !counts || !merged || !merged_counts || !ws) return fail(HVR_EINVAL, "null pointer");
+  if (int rc = tta_check_augs(A, img_w, scale_factor, flip)) return rc;
+  if (T <= 0 || mx <= 0 || max_num <= 0) return fail(HVR_EINVAL, "bad merge_aug_proposals shape");
+  if ((long)A * mx > 8192) return fail(HVR_EUNSUPPORTED, "hvr_merge_aug_proposals supports A * mx <= 8192, got %ld", (long)A * mx);
+  if (max_num > 4096) return fail(HVR_EUNSUPPORTED, "hvr_merge_aug_proposals supports max_num <= 4096, got %d", max_num);
+  if (ws_bytes < hvr_merge_aug_proposals_workspace_bytes(A, T, mx)) return fail(HVR_EWORKSPACE, "merge_aug_proposals workspace too small");
+  return check_launch(run_tta_merge_proposals(proposals, counts, A, T, mx, img_w, scale_factor, flip, nms_thr, max_num, merged,
+                                              merged_counts, ws, (hipStream_t)stream),
+                      "hvr_merge_aug_proposals");
+}
+
+int hvr_map_aug_rois(const float* merged, int A, int T, int max_num, const float* img_w, const float* scale_factor, const int32_t* flip,
+                     float* rois, void* stream) {
+  if (!merged || !rois) return fail(HVR_EINVAL, "null pointer");
+  if (int rc = tta_check_augs(A, img_w, scale_factor, flip)) return rc;
+  if (T <= 0 || max_num <= 0 || (long)T * max_num > (1L << 24)) return fail(HVR_EINVAL, "bad map_aug_rois shape");
+  return check_launch(run_tta_map_rois(merged, A, T, max_num, img_w, scale_factor, flip, rois, (hipStream_t)stream), "hvr_map_aug_rois");
+}
+
+int hvr_merge_aug_dets(const float* boxes, const float* scores, int A, int R, int ncls, const float* img_w, const float* scale_factor,
+                       const int32_t* flip, float* merged_boxes, float* merged_scores, void* stream) {
+  if (R == 0) return HVR_OK;
+  if (!boxes || !scores || !merged_boxes || !merged_scores) return fail(HVR_EINVAL, "null pointer");
+  if (int rc = tta_check_augs(A, img_w, scale_factor, flip)) return rc;
+  if (R < 0 || ncls <= 0 || (long)R * (4 + ncls) > (1L << 30)) return fail(HVR_EINVAL, "bad merge_aug_dets shape");
+  return check_launch(run_tta_merge_dets(boxes, scores, A, R, ncls, img_w, scale_factor, flip, merged_boxes, merged_scores,
+                                         (hipStream_t)stream),
+                      "hvr_merge_aug_dets");
 }
 
 int hvr_ce_rows(const float* logits, int ldl, int cls_off, int ncls, const int64_t* labels, int R, float* loss, void* stream) {

@@ -36,14 +36,17 @@ __device__ __forceinline__ Tap linear_tap(int d, double scale, int n_src) {
 
 __global__ __launch_bounds__(256) void ingest_kernel(const uint8_t* __restrict__ src, int sh, int sw, long pitch, float* __restrict__ dst,
                                                      int nh, int nw, int ph, int pw, double scale_x, double scale_y, float m0, float m1,
-                                                     float m2, float s0, float s1, float s2, int to_rgb) {
+                                                     float m2, float s0, float s1, float s2, int to_rgb, int flip) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= pw || y >= ph) return;
-  const long plane = (long)ph * pw, o = (long)y * pw + x;
+  const long plane = (long)ph * pw;
   if (x >= nw || y >= nh) {   // Pad(size_divisor): zeros AFTER normalisation
+    const long o = (long)y * pw + x;
     dst[o] = 0.f; dst[plane + o] = 0.f; dst[2 * plane + o] = 0.f;
     return;
   }
+  // RandomFlip(horizontal) sits between Resize and Pad (transforms.py:190-196): the resized image is mirrored, the padding stays right / bottom
+  const long o = (long)y * pw + (flip ? nw - 1 - x : x);
   const Tap tx = linear_tap(x, scale_x, sw), ty = linear_tap(y, scale_y, sh);
   const uint8_t* r0 = src + (long)ty.i0 * pitch;
   const uint8_t* r1 = src + (long)ty.i1 * pitch;
@@ -59,11 +62,11 @@ __global__ __launch_bounds__(256) void ingest_kernel(const uint8_t* __restrict__
 }
 
 hipError_t run_ingest(const uint8_t* src, int sh, int sw, long pitch, float* dst, int nh, int nw, int ph, int pw, const float* mean3,
-                      const float* std3, int to_rgb, hipStream_t s) {
+                      const float* std3, int to_rgb, int flip, hipStream_t s) {
   // cv::resize: inv_scale = dsize / ssize (double), scale = 1 / inv_scale
   const double scale_x = 1.0 / ((double)nw / (double)sw), scale_y = 1.0 / ((double)nh / (double)sh);
   hipLaunchKernelGGL(ingest_kernel, dim3((pw + 63) / 64, (ph + 3) / 4), dim3(256), 0, s, src, sh, sw, pitch, dst, nh, nw, ph, pw, scale_x,
-                     scale_y, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], to_rgb);
+                     scale_y, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], to_rgb, flip);
   return hipGetLastError();
 }
 

@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import registry
+from . import native
 from .box_ops import bbox2result, bbox2roi
 from .registry import DETECTORS
 
@@ -63,8 +64,8 @@ class BaseDetector(nn.Module):
                 return [self.extract_feat(im_) for im_ in img]
             return self.extract_feat(img)
         if forward_feat:
-            if isinstance(img_meta[0], list) and len(img_meta[0]) != 0:
-                raise NotImplementedError('multi-scale test-time augmentation (forward_feat_aug) is outside the hot path')
+            if isinstance(img_meta[0], list) and len(img_meta[0]) != 0:      # base.py:125-126: nested metas = MultiScaleFlipAug
+                return self.forward_feat_aug(img_meta=img_meta, **kwargs)
             return self.forward_feat(img_meta=img_meta, **kwargs)
         if return_loss:
             return self.forward_train(img, img_meta, **kwargs)
@@ -391,6 +392,182 @@ class _WindowDetector(TwoStageDetector):
 
     def simple_test_bboxes(self, x, img_meta, proposals, rcnn_test_cfg, rescale=False):
         raise NotImplementedError
+
+    # ---- multi-scale / flip test-time augmentation (hnmb_rcnn.py:104-180, 640-698) ------------------------------------
+    # x[t][a] = C4 map of frame t under augmentation a, img_meta[t][a] its meta (the MultiScaleFlipAug order: scale outer, flip
+    # inner).  Per augmentation the window runs as forward_feat does; between the stages the boxes of all augmentations meet in
+    # the original image: merge_aug_proposals for all T frames (one launch), bbox_mapping into every augmentation (one launch),
+    # merge_aug_bboxes per read-out branch (one launch each), then the usual multiclass NMS.  Like forward_feat the path is
+    # speculative: the merged counts stay on the device and a frame that merged to fewer than max_num proposals sends the window
+    # through the exact, ragged re-run when the result is read.
+    @staticmethod
+    def _aug_params(img_metas, key):
+        """(img_w, scale_factor, flip) host lists over the augmentations, from the key frame's metas (hnmb_rcnn.py:645-651)."""
+        for metas in img_metas:
+            if not isinstance(metas[key]['scale_factor'], (int, float)):
+                raise NotImplementedError('per-axis scale_factor arrays are outside the HVR hot path')
+            if any(bool(m['flip']) != bool(metas[key]['flip']) for m in metas):
+                raise NotImplementedError('the frames of one augmentation share its flip flag')
+        return ([m[key]['img_shape'][1] for m in img_metas], [float(m[key]['scale_factor']) for m in img_metas],
+                [bool(m[key]['flip']) for m in img_metas])
+
+    def _aug_split(self, x, img_meta):
+        """x[t][a], img_meta[t][a] -> (feats: A logical [T,1024,h,w] C4 maps, img_metas: A lists of T metas), hnmb_rcnn.py:110-116."""
+        assert x is not None and img_meta is not None and len(x) == len(img_meta) and len(x[0]) == len(img_meta[0])
+        A = len(img_meta[0])
+        return [self._cat_frames([x_[a] for x_ in x]) for a in range(A)], [[m[a] for m in img_meta] for a in range(A)]
+
+    @staticmethod
+    def _aug_groups(feats, img_metas):
+        """Augmentations that can share a launch (same map shape and img_shape -- the flip pair of one scale), in first-seen order."""
+        groups = {}
+        for a, (f, metas) in enumerate(zip(feats, img_metas)):
+            groups.setdefault((tuple(f.shape[1:]), f.dtype, tuple(metas[0]['img_shape'][:2])), []).append(a)
+        return list(groups.values())
+
+    def _aug_group_maps(self, feats, groups):
+        """One [len(g) * T, 1024, h, w] map per group (a single augmentation's map is used as it is)."""
+        return [feats[g[0]] if len(g) == 1 else self._cat_frames([feats[a] for a in g]) for g in groups]
+
+    def aug_shared_feats(self, feats, img_metas, group_maps=None):
+        """res5 per augmentation -> list of A [c5]; the augmentations of one group go through it as one batch."""
+        if not self.feat_from_shared_head:
+            return [[f] for f in feats]
+        groups = self._aug_groups(feats, img_metas)
+        maps = group_maps if group_maps is not None else self._aug_group_maps(feats, groups)
+        out = [None] * len(feats)
+        for g, m in zip(groups, maps):
+            c5 = self.shared_head(m)
+            T = c5.shape[0] // len(g)
+            for i, a in enumerate(g):
+                out[a] = [c5[i * T:(i + 1) * T]]
+        return out
+
+    def aug_test_rpn(self, feats, img_metas, group_maps=None):
+        """RPN proposals of every augmentation, each in its own coordinates -> (proposals [A,T,mx,5], counts [A,T] int32) on the
+        device; the augmentations of one group run the RPN head and hvr_rpn_proposals as one batch of len(g) * T frames."""
+        groups = self._aug_groups(feats, img_metas)
+        maps = group_maps if group_maps is not None else self._aug_group_maps(feats, groups)
+        A, T = len(feats), len(img_metas[0])
+        props, counts = [None] * A, [None] * A
+        for g, m in zip(groups, maps):
+            rpn_outs = self.rpn_head([m])
+            p, c = self.rpn_head.get_bboxes_batched(rpn_outs[0], rpn_outs[1], [mt for a in g for mt in img_metas[a]], self.test_cfg.rpn)
+            for i, a in enumerate(g):
+                props[a], counts[a] = p[i * T:(i + 1) * T], c[i * T:(i + 1) * T]
+        return torch.stack(props, 0), torch.stack(counts, 0)
+
+    def aug_test_rpn_merged(self, feats, img_metas, group_maps=None):
+        """simple_test_rpn per augmentation + merge_aug_proposals per frame (hnmb_rcnn.py:126-146) with no host read:
+        -> (merged [T,max_num,5] in original-image coordinates, rows behind a frame's count zeroed; counts [T] int32), device."""
+        props, counts = self.aug_test_rpn(feats, img_metas, group_maps)
+        # merge_aug_proposals takes every frame's own meta (merge_augs.py:26-35); one video: the key frame's stand for all
+        img_w, scale, flip = self._aug_params(img_metas, self.key_dim)
+        return native.merge_aug_proposals(props, counts, img_w, scale, flip, self.test_cfg.rpn.nms_thr, self.test_cfg.rpn.max_num)
+
+    def aug_test_bboxes(self, feats, img_metas, proposal_list, rcnn_test_cfg, defer=False):
+        """hnmb_rcnn.py:640-698.  feats: per augmentation [c5 map of its T frames]; proposal_list: the merged proposals in
+        original-image coordinates -- a [T,n,5] tensor (every frame has n rows: the speculative form) or a list of T [n_t,5]
+        tensors.  Per augmentation: bbox_mapping with the key frame's img_shape / scale_factor, RoIAlign, the relation head and
+        the decode in the augmentation's coordinates (rescale=False, no NMS); per read-out branch merge_aug_bboxes and one
+        multiclass NMS.  -> (det_bboxes per branch, det_labels per branch); defer=True -> [(dets [max,5], labels [max], n [1])]
+        per branch, device tensors.  rcnn_test_cfg without `nms`: (merged boxes per branch, merged scores per branch)."""
+        key, A = self.key_dim, len(feats)
+        img_w, scale, flip = self._aug_params(img_metas, key)
+        if torch.is_tensor(proposal_list):
+            padded, n_t = proposal_list, None
+        else:
+            n_t = [int(p_.shape[0]) for p_ in proposal_list]
+            padded = proposal_list[0].new_zeros((len(n_t), max(max(n_t), 1), 5))
+            for t, p_ in enumerate(proposal_list):
+                padded[t, :n_t[t], :p_.shape[1]] = p_[:, :5]
+        T, n = int(padded.shape[0]), int(padded.shape[1])
+        rois_all = native.map_aug_rois(padded.float(), img_w, scale, flip)                 # [A, T * n, 5]
+        if n_t is None or all(c == n for c in n_t):
+            start, length, pick = key * n, n, None
+        else:
+            start, length = int(sum(n_t[:key])), n_t[key]
+            pick = torch.cat([torch.arange(t * n, t * n + c) for t, c in enumerate(n_t)]).to(padded.device)
+        cur_range = dict(start=start, length=length)
+        hvr = type(self).__name__ == 'HNMBRCNN'
+        aug_bboxes, aug_scores = [], []
+        for a in range(A):
+            rois = rois_all[a] if pick is None else rois_all[a].index_select(0, pick)
+            roi_feats = self.get_roi_feat(feats[a], rois)
+            key_rois = rois[start:start + length].clone()
+            key_rois[:, 0] = 0
+            meta = img_metas[a][0]      # simple_test_bboxes reads img_meta[0] (hnmb_rcnn.py:603-604)
+            if hvr:
+                cls_score, bbox_pred = self.bbox_head.forward_test(roi_feats, [cur_range], key_dim=key, all_res=False)
+                bboxes, scores = self.bbox_head.get_det_bboxes(key_rois, cls_score, bbox_pred, meta['img_shape'], meta['scale_factor'],
+                                                               rescale=False, cfg=None)
+            else:
+                cls_score, bbox_pred = self.bbox_head(roi_feats, cur_range, key_dim=key, all_res=False)[:2]
+                bboxes, scores = self.bbox_head.get_det_bboxes(key_rois, cls_score, bbox_pred, meta['img_shape'], meta['scale_factor'],
+                                                               rescale=False, cfg=None)
+                bboxes, scores = [bboxes], [scores]
+            aug_bboxes.append(bboxes)
+            aug_scores.append(scores)
+        outs = []
+        for i in range(len(aug_scores[0])):
+            mb, ms = native.merge_aug_dets(torch.stack([b[i] for b in aug_bboxes], 0), torch.stack([s_[i] for s_ in aug_scores], 0),
+                                           img_w, scale, flip)
+            if rcnn_test_cfg is not None and hasattr(rcnn_test_cfg, 'nms'):
+                if rcnn_test_cfg.nms.get('type', 'nms') != 'nms':
+                    raise NotImplementedError('only greedy nms is on the HVR hot path')
+                outs.append(self.bbox_head._nms(mb, ms, rcnn_test_cfg, defer))
+            else:
+                outs.append((mb, ms))
+        if defer and rcnn_test_cfg is not None and hasattr(rcnn_test_cfg, 'nms'):
+            return [o[0] for o in outs]
+        return [o[0] for o in outs], [o[1] for o in outs]
+
+    def forward_feat_aug(self, x=None, img_meta=None, proposals=None, rescale=False, defer=False, speculate=True):
+        """One window under A augmentations (hnmb_rcnn.py:104-180) -> the result format of forward_feat; detections always come
+        out at original scale and, as in the reference, rescale=False multiplies their boxes by img_metas[0][0]['scale_factor'].
+        `proposals` is accepted and ignored as in the reference.  defer=True -> PendingWindow.  HNMBRCNN returns its two
+        branches; SelsaRCNN (which lacks the method in the reference) the one-branch form."""
+        feats, img_metas = self._aug_split(x, img_meta)
+        groups = self._aug_groups(feats, img_metas)
+        maps = self._aug_group_maps(feats, groups)
+        dev = feats[0].device
+        if self.rpn_side_stream and feats[0].is_cuda:    # the RPN branch and the merge underneath res5, as in _c5_and_rois
+            main, side = torch.cuda.current_stream(dev), self._side_stream(dev)
+            ready = torch.cuda.Event()
+            ready.record(main)
+            with torch.cuda.stream(side):
+                side.wait_event(ready)
+                merged, counts = self.aug_test_rpn_merged(feats, img_metas, maps)
+                done = torch.cuda.Event()
+                done.record(side)
+            c5 = self.aug_shared_feats(feats, img_metas, maps)
+            main.wait_event(done)
+            merged.record_stream(main)
+            counts.record_stream(main)
+            for m in maps:
+                m.record_stream(side)
+        else:
+            merged, counts = self.aug_test_rpn_merged(feats, img_metas, maps)
+            c5 = self.aug_shared_feats(feats, img_metas, maps)
+        mx = int(merged.shape[1])
+        single = type(self).__name__ == 'SelsaRCNN'
+        factor = None if rescale else float(img_metas[0][0]['scale_factor'])
+        if speculate:
+            branches = self.aug_test_bboxes(c5, img_metas, merged, self.test_cfg.rcnn, defer=True)
+            if factor is not None:
+                branches = [(torch.cat([d[:, :4] * factor, d[:, 4:]], dim=1), l, n) for d, l, n in branches]
+            pending = PendingWindow(branches, counts, mx, self.bbox_head.num_classes,
+                                    lambda: self.forward_feat_aug(x, img_meta, proposals, rescale, speculate=False), single=single)
+            return pending if defer else pending.result()
+        counts_h = counts.tolist()                       # exact path: a mid-window host read of T integers
+        proposal_list = [merged[t, :c] for t, c in enumerate(counts_h)]
+        det_bboxes, det_labels = self.aug_test_bboxes(c5, img_metas, proposal_list, self.test_cfg.rcnn)
+        results = []
+        for d, l in zip(det_bboxes, det_labels):
+            if factor is not None:
+                d = torch.cat([d[:, :4] * factor, d[:, 4:]], dim=1)
+            results.append(bbox2result(d, l, self.bbox_head.num_classes))
+        return results[0] if single else results
 
     def simple_test(self, img, img_meta, proposals=None, rescale=False):
         """Clip-mode test as the reference's simple_test INTENDS it (hnmb_rcnn.py:615-638, selsa_rcnn.py:319-338): img

@@ -140,6 +140,11 @@ SYMBOLS = {
     'hvr_ce_rows': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'hvr_triplet_margin': (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     'hvr_ingest_frame': (_i, [_vp, _i, _i, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    'hvr_ingest_frame_flip': (_i, [_vp, _i, _i, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
+    'hvr_merge_aug_proposals_workspace_bytes': (_sz, [_i, _i, _i]),
+    'hvr_merge_aug_proposals': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _sz, _vp]),
+    'hvr_map_aug_rois': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'hvr_merge_aug_dets': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'hvr_mining_argreduce': (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp]),
     'hvr_roi_align_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp]),
     'hvr_roi_align_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
@@ -1022,16 +1027,79 @@ def triplet_margin(q, k, anchor_idx, pos_idx, neg_idx, margin, need_grad=True):
     return out2, dq, dk
 
 
-def ingest_frame(frame, new_hw, pad_hw, mean, std, to_rgb=False):
-    """frame uint8 [H, W, 3] (cuda, rows contiguous) -> f32 [1, 3, pad_h, pad_w]: resize + normalise + pad in one kernel."""
+def ingest_frame(frame, new_hw, pad_hw, mean, std, to_rgb=False, flip=None):
+    """frame uint8 [H, W, 3] (cuda, rows contiguous) -> f32 [1, 3, pad_h, pad_w]: resize + normalise + pad in one kernel.
+    flip: None -> hvr_ingest_frame; True / False -> hvr_ingest_frame_flip (the resized image mirrored before the padding)."""
     _need_cuda(frame)
     assert frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3 and frame.stride(2) == 1 and frame.stride(1) == 3
     out = torch.empty((1, 3, int(pad_hw[0]), int(pad_hw[1])), dtype=torch.float32, device=frame.device)
     m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+    if flip is not None:
+        _check(lib().hvr_ingest_frame_flip(_ptr(frame), frame.shape[0], frame.shape[1], frame.stride(0), _ptr(out), int(new_hw[0]), int(new_hw[1]),
+                                           int(pad_hw[0]), int(pad_hw[1]), ctypes.cast(m3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p),
+                                           int(bool(to_rgb)), int(bool(flip)), _stream()), 'hvr_ingest_frame_flip')
+        return out
     _check(lib().hvr_ingest_frame(_ptr(frame), frame.shape[0], frame.shape[1], frame.stride(0), _ptr(out), int(new_hw[0]), int(new_hw[1]),
                                   int(pad_hw[0]), int(pad_hw[1]), ctypes.cast(m3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p),
                                   int(bool(to_rgb)), _stream()), 'hvr_ingest_frame')
     return out
+
+
+def _aug_arrays(img_w, scale_factor, flip):
+    """host arrays (img_w, scale_factor, flip) of the A augmentations for the hvr_*_aug_* calls"""
+    A = len(img_w)
+    assert A == len(scale_factor) == len(flip) and A > 0
+    w = (ctypes.c_float * A)(*[float(v) for v in img_w])
+    s = (ctypes.c_float * A)(*[float(v) for v in scale_factor])
+    f = (ctypes.c_int32 * A)(*[int(bool(v)) for v in flip])
+    return A, w, s, f, (ctypes.cast(w, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), ctypes.cast(f, ctypes.c_void_p))
+
+
+def merge_aug_proposals(proposals, counts, img_w, scale_factor, flip, nms_thr, max_num):
+    """proposals [A,T,mx,5] f32, counts [A,T] int32 (device) + the augmentations' (img_w, scale_factor, flip) host lists ->
+    (merged [T,max_num,5] in original-image coordinates, rows behind the count zeroed; merged_counts [T] int32), device tensors."""
+    _need_cuda(proposals, counts)
+    assert proposals.dtype == torch.float32 and counts.dtype == torch.int32 and proposals.dim() == 4 and proposals.shape[3] == 5
+    A, T, mx = (int(v) for v in proposals.shape[:3])
+    A_, w, s, f, ptrs = _aug_arrays(img_w, scale_factor, flip)
+    assert A_ == A and tuple(counts.shape) == (A, T)
+    if A * mx > 8192:
+        raise HvrError('hvr_merge_aug_proposals supports A * mx <= 8192, got %d x %d' % (A, mx))
+    proposals, counts = proposals.contiguous(), counts.contiguous()
+    merged = torch.empty((T, int(max_num), 5), dtype=torch.float32, device=proposals.device)
+    mcounts = torch.empty(T, dtype=torch.int32, device=proposals.device)
+    ws = _workspace(lib().hvr_merge_aug_proposals_workspace_bytes(A, T, mx), proposals.device, 'tta_merge')
+    with _span('merge_aug_proposals', float(proposals.numel() * 4)):
+        _check(lib().hvr_merge_aug_proposals(_ptr(proposals), _ptr(counts), A, T, mx, ptrs[0], ptrs[1], ptrs[2], float(nms_thr), int(max_num),
+                                             _ptr(merged), _ptr(mcounts), _ptr(ws), ws.numel(), _stream()), 'hvr_merge_aug_proposals')
+    return merged, mcounts
+
+
+def map_aug_rois(merged, img_w, scale_factor, flip):
+    """merged [T,max_num,5] (original-image coordinates) -> rois [A, T * max_num, 5] = (frame index, box in augmentation a's coordinates)."""
+    _need_cuda(merged)
+    assert merged.dtype == torch.float32 and merged.dim() == 3 and merged.shape[2] == 5
+    T, mx = int(merged.shape[0]), int(merged.shape[1])
+    A, w, s, f, ptrs = _aug_arrays(img_w, scale_factor, flip)
+    rois = torch.empty((A, T * mx, 5), dtype=torch.float32, device=merged.device)
+    with _span('map_aug_rois', float(rois.numel() * 4)):
+        _check(lib().hvr_map_aug_rois(_ptr(merged.contiguous()), A, T, mx, ptrs[0], ptrs[1], ptrs[2], _ptr(rois), _stream()), 'hvr_map_aug_rois')
+    return rois
+
+
+def merge_aug_dets(boxes, scores, img_w, scale_factor, flip):
+    """boxes [A,R,4] (each augmentation's own coordinates), scores [A,R,ncls] f32 -> (merged boxes [R,4] at original scale, merged scores [R,ncls])."""
+    _need_cuda(boxes, scores)
+    assert boxes.dtype == torch.float32 and scores.dtype == torch.float32 and boxes.dim() == 3 and boxes.shape[2] == 4 and scores.dim() == 3
+    A, R, ncls = (int(v) for v in scores.shape)
+    A_, w, s, f, ptrs = _aug_arrays(img_w, scale_factor, flip)
+    assert A_ == A and tuple(boxes.shape) == (A, R, 4)
+    out_b = torch.empty((R, 4), dtype=torch.float32, device=boxes.device)
+    out_s = torch.empty((R, ncls), dtype=torch.float32, device=boxes.device)
+    with _span('merge_aug_dets', float(boxes.numel() * 4 + scores.numel() * 4)):
+        _check(lib().hvr_merge_aug_dets(_ptr(boxes.contiguous()), _ptr(scores.contiguous()), A, R, ncls, ptrs[0], ptrs[1], ptrs[2], _ptr(out_b),
+                                        _ptr(out_s), _stream()), 'hvr_merge_aug_dets')
+    return out_b, out_s
 
 
 def mining_argreduce(aff, labels, all_labels):

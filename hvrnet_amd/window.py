@@ -27,7 +27,9 @@ class VideoWindowRunner(object):
     cache_frames=False: the reference's loop as it stands -- every emitted window recomputes res5 / RPN / RoIAlign /
     fc_new_1 for all T frames (hnmb_rcnn.py:195-222).  cache_frames=True: those per-frame results are computed once when
     the frame arrives (`model.frame_tensors`) and a window runs only the relation stages and the read-out on the
-    T cached entries (`model.forward_feat_frames`); same detections, about a third of the work per output frame."""
+    T cached entries (`model.forward_feat_frames`); same detections, about a third of the work per output frame.
+    Test-time augmentation (cache_frames=False only): `img` a list of A tensors and `img_meta` a list of A metas per frame
+    (`pipelines.FrameIngestAug`); the nested metas send every emitted window through `model.forward_feat_aug`."""
 
     def __init__(self, model, window, rescale=True, cache_frames=False):
         assert window % 2 == 1, 'window = 2 * frame_interval + 1'
@@ -60,7 +62,13 @@ class VideoWindowRunner(object):
     def step(self, img, img_meta, flag, frame_offset, seg_len=None):
         """One loader iteration; returns the list of (frame_offset, result) emitted by it."""
         out = []
-        feat = self.model(img=img, img_meta=[img_meta], backbone_feat=True)[0]
+        if isinstance(img, (list, tuple)):   # MultiScaleFlipAug form: img = A tensors, img_meta = A metas -> the deque holds A C4 maps per frame
+            if self.cache_frames:
+                raise NotImplementedError('the per-frame cache does not cover test-time augmentation (cache_frames=False does)')
+            feat = [f[0] for f in self.model(img=list(img), img_meta=list(img_meta), backbone_feat=True)]
+            img_meta = list(img_meta)
+        else:
+            feat = self.model(img=img, img_meta=[img_meta], backbone_feat=True)[0]
         self._entry = self.model.frame_tensors(feat, img_meta) if self.cache_frames else None
         if flag == FIRST:
             self._reset()

@@ -463,6 +463,40 @@ int hvr_det_loss_sampled(const float* logits, int ldl, int cls_off, int reg_off,
  * (mmdet/datasets/pipelines/transforms.py:111-124,260-269,308-313) in one kernel instead of three CPU passes per frame. */
 int hvr_ingest_frame(const uint8_t* src, int src_h, int src_w, int64_t src_pitch, float* dst, int new_h, int new_w, int pad_h, int pad_w,
                      const float* mean3, const float* std3, int to_rgb, void* stream);
+/* The same with RandomFlip(horizontal) in its place between Resize and Pad (transforms.py:190-196, the flip=True half of a
+ * MultiScaleFlipAug test pipeline, mmdet/datasets/pipelines/test_aug.py): flip != 0 mirrors the resized new_h x new_w image, the
+ * zero padding stays on the right and at the bottom.  flip == 0 is hvr_ingest_frame bit for bit. */
+int hvr_ingest_frame_flip(const uint8_t* src, int src_h, int src_w, int64_t src_pitch, float* dst, int new_h, int new_w, int pad_h, int pad_w,
+                          const float* mean3, const float* std3, int to_rgb, int flip, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Test-time augmentation (multi-scale / flip): the box plumbing between the per-augmentation stages of
+ * HNMBRCNN.forward_feat_aug / aug_test_bboxes (mmdet/models/detectors/hnmb_rcnn.py:104-180, 640-698) for all T frames of a
+ * window, with no host read.  An augmentation a is (img_w[a], scale_factor[a], flip[a]): HOST arrays of A entries, 1 <= A <= 16.
+ * Un-flip / flip: x1' = img_w - x2 - 1, x2' = img_w - x1 - 1; back = (un-flip, then a true division by scale_factor), forward =
+ * (times scale_factor, then flip) -- bbox_mapping_back / bbox_mapping of mmdet/core/bbox/transforms.py:114-146.
+ *   hvr_merge_aug_proposals: merge_aug_proposals (mmdet/core/post_processing/merge_augs.py:8-44) per frame, one launch for the
+ *                       window: proposals [A][T][mx][5] f32 of which rows < counts[a][t] ([A][T] int32, device) are valid ->
+ *                       mapped back, concatenated in augmentation order, greedy NMS at IoU >= nms_thr (nms_cpu semantics),
+ *                       survivors by descending score (ties: lower concatenated index), the first max_num of them:
+ *                       merged [T][max_num][5] in original-image coordinates, rows behind merged_counts[t] ([T] int32, device)
+ *                       zeroed.  A * mx <= 8192, max_num <= 4096.  One workgroup per frame.
+ *   hvr_map_aug_rois:   bbox_mapping + bbox2roi (transforms.py:131-136,149-168 as hnmb_rcnn.py:645-651 uses them: ONE img_w /
+ *                       scale_factor / flip per augmentation, the key frame's, for all frames): merged [T][max_num][5] ->
+ *                       rois [A][T * max_num][5] = (frame index, box in augmentation a's coordinates).
+ *   hvr_merge_aug_dets: merge_aug_bboxes (merge_augs.py:47-70): boxes [A][R][4] (each in its augmentation's coordinates, i.e.
+ *                       hvr_det_decode with scale_factor = 0) and scores [A][R][ncls] -> merged_boxes [R][4] = mean over a of the
+ *                       boxes mapped back, merged_scores [R][ncls] = mean over a (sums in augmentation order, one division by A).
+ *                       Feeds hvr_multiclass_nms (R <= 512 there).
+ * ---------------------------------------------------------------------------------- */
+size_t hvr_merge_aug_proposals_workspace_bytes(int A, int T, int mx);
+int hvr_merge_aug_proposals(const float* proposals, const int32_t* counts, int A, int T, int mx, const float* img_w,
+                            const float* scale_factor, const int32_t* flip, float nms_thr, int max_num, float* merged,
+                            int32_t* merged_counts, void* ws, size_t ws_bytes, void* stream);
+int hvr_map_aug_rois(const float* merged, int A, int T, int max_num, const float* img_w, const float* scale_factor, const int32_t* flip,
+                     float* rois, void* stream);
+int hvr_merge_aug_dets(const float* boxes, const float* scores, int A, int R, int ncls, const float* img_w, const float* scale_factor,
+                       const int32_t* flip, float* merged_boxes, float* merged_scores, void* stream);
 
 #ifdef __cplusplus
 }
