@@ -621,6 +621,21 @@ static int relation_apply_pass(const void* P, const void* Vt, float* mstat, floa
   return check_launch(run_tile_op(p, EPI_APPLY, s), "relation: apply");
 }
 
+// relation_normalize_kernel / relation_normalize_split_kernel keep one factor per 128-key block of a row in a fixed LDS table
+// (misc.hip, `g[128]`): the sweeps take at most kNormalizeMaxBlocks blocks = 16 384 keys.  Checked before anything is launched.
+constexpr int kNormalizeMaxBlocks = 128;
+static int normalize_blocks_ok(int Mk, const char* what) {
+  if (rel_ldp(Mk) / 128 > kNormalizeMaxBlocks)
+    return fail(HVR_EUNSUPPORTED, "%s: Mk=%d exceeds the %d keys (%d blocks of 128) the normalising sweep supports", what, Mk,
+                kNormalizeMaxBlocks * 128, kNormalizeMaxBlocks);
+  return HVR_OK;
+}
+// whether relation_split_tail normalises P~ in a sweep of its own (HVR_SPLIT_NORMALIZE = 0 / 1 forces the folded / the swept form)
+static bool split_normalizes(int Mq) {
+  static const int split_normalize = std::getenv("HVR_SPLIT_NORMALIZE") ? std::atoi(std::getenv("HVR_SPLIT_NORMALIZE")) : -1;
+  return split_normalize == 1 || (split_normalize < 0 && Mq >= 1024);
+}
+
 // What follows the scores pass of ONE split-half problem: V^T (V == nullptr: the scores launch wrote it), then either one normalising sweep over P~ + a plain product, or the apply
 // pass with the block weights g = 2^(m_t - m*) / L folded in per 128-key block (EPI_APPLY: a block is four split K-steps of three
 // MFMAs, its un-scaled partial joins the running total by one FMA per accumulator register).  Shared by hvr_relation_fwd and the
@@ -645,8 +660,7 @@ static int relation_split_tail(void* P, void* Vt, float* mstat, float* lstat, co
   // 0.29 ms) -- the fold needs the double-buffered apply shapes (the pipelined loop is written for two K-steps per block), and one
   // normalising sweep over P~ (22 us at 7.5 TB/s out of the Infinity Cache) + the pipelined plain product is cheaper than they are.
   // HVR_SPLIT_NORMALIZE = 0 / 1 forces the folded / the swept form.
-  static const int split_normalize = std::getenv("HVR_SPLIT_NORMALIZE") ? std::atoi(std::getenv("HVR_SPLIT_NORMALIZE")) : -1;
-  if (split_normalize == 1 || (split_normalize < 0 && Mq >= 1024)) {
+  if (split_normalizes(Mq)) {
     rc = check_launch(run_relation_normalize(P, mstat, lstat, Mq, nt, ldp, HVR_F16S, 1.f, s), "relation: normalise (split half)");
     if (rc) return rc;
     return check_launch(run_tile_op(p, EPI_LINEAR, s), "relation: apply (split half, plain product)");
@@ -688,6 +702,7 @@ int hvr_relation_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
     // split half: the scores pass (block-local maxima, P~ stored x 2^12 in the split format) -- on the 352 x 256 persistent tiles of
     // relation_bt.hip for window-sized problems, else on the tile engine -- then relation_split_tail
     if (ldv % 64 || !aligned128(V) || ldo % 32 || !aligned128(O) || D % 64) return fail(HVR_EINVAL, "split-half relation: D, ldv multiples of 64, ldo of 32, 128-byte aligned V / O");
+    if (split_normalizes(Mq) && (rc = normalize_blocks_ok(Mk, "split-half relation"))) return rc;
     const bool bt = staging && scores_bt_supported(Mq, Mk, D, ldq, ldk, ldv, ldp, Q, K, V, P, Vt, 1, true);
     if (bt) {   // (V^T is written by the same launch)
       ScoresBTParams b;
@@ -790,6 +805,10 @@ int hvr_relation_fwd_grouped(const void* Q, int64_t ldq, int64_t gsq, const void
   const bool strides_ok = split ? (gsq % 32 == 0 && gsk % 32 == 0 && gsv % 32 == 0 && gso % 32 == 0)
                                 : (two_byte && gsq % 8 == 0 && gsk % 8 == 0 && gsv % 8 == 0 && gso % 8 == 0);
   if (split && (ldv % 64 || !aligned128(V) || ldo % 32 || !aligned128(O) || D % 64)) return fail(HVR_EINVAL, "split-half relation: D, ldv multiples of 64, ldo of 32, 128-byte aligned V / O");
+  if (split && split_normalizes(Mq)) {
+    const int rc = normalize_blocks_ok(Mk, "split-half relation");
+    if (rc) return rc;
+  }
   // (exact: "bit for bit hvr_relation_fwd's" only holds when the single call takes the SAME scores kernel -- a per-group tile count
   // the one-group rule sends to the tile engine, e.g. Mq = Mk = 5 400: 352 tiles, runs as per-group single calls)
   // ---- few query rows (the key stage, hrnmp_bbox_head.py:269-278,888-891: 300 x 4 500 per clip), two-byte operands: ONE launch per pass
@@ -916,6 +935,7 @@ int hvr_relation_probs(const void* Q, int64_t ldq, const void* K, int64_t ldk, v
   if (Mq <= 0 || Mk <= 0) return fail(HVR_EINVAL, "empty relation Mq=%d Mk=%d", Mq, Mk);
   if (!(scale > 0.f)) return fail(HVR_EINVAL, "relation scale must be positive, got %g", (double)scale);
   if (ldp != rel_ldp(Mk)) return fail(HVR_EINVAL, "P rows must be %ld elements (keys padded to 128), got %ld", rel_ldp(Mk), (long)ldp);
+  if (int rc = normalize_blocks_ok(Mk, "relation probs")) return rc;
   if (ws_bytes < hvr_relation_probs_workspace_bytes(Mq, Mk)) return fail(HVR_EWORKSPACE, "relation probs workspace too small");
   const int nt = (int)(ldp / 128);
   float* mstat = (float*)ws;

@@ -282,6 +282,8 @@ __global__ __launch_bounds__(1024) void rpn_loss_kernel(const float* __restrict_
     const int r = m / A, a = m - r * A;
     const float* row = o + (long)r * ldo;
     float* drow = d_o + (long)r * ldo;
+    if (a == 0)   // columns 5A .. ldo belong to no anchor: their gradient is zero (d_o arrives uninitialised)
+      for (int c = 5 * A; c < ldo; ++c) drow[c] = 0.f;
     const float x = row[a], z = (float)labels[m], w = label_w[m];
     // F.binary_cross_entropy_with_logits: max(x,0) - x z + log(1 + exp(-|x|))
     const float ex = expf(-fabsf(x));

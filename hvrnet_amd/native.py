@@ -746,13 +746,18 @@ def relation_ldp(Mk):
     return (Mk + 127) // 128 * 128
 
 
-def relation_probs(q, k, scale, staging=None):
-    """softmax(scale * q @ k^T, dim=1) as a [Mq, ldp] matrix of q's dtype (padding columns zero)."""
+def relation_probs(q, k, scale, staging=None, out=None):
+    """softmax(scale * q @ k^T, dim=1) as a [Mq, ldp] matrix of q's dtype (padding columns zero); `out`: a contiguous [Mq, ldp]
+    tensor to write into (every element is overwritten)."""
     _need_cuda(q, k)
     Mq, D = q.shape
     Mk = k.shape[0]
     ldp = relation_ldp(Mk)
-    P = torch.empty((Mq, ldp), dtype=q.dtype, device=q.device)
+    if out is None:
+        P = torch.empty((Mq, ldp), dtype=q.dtype, device=q.device)
+    else:
+        assert out.shape == (Mq, ldp) and out.dtype == q.dtype and out.device == q.device and out.is_contiguous()
+        P = out
     ws = _workspace(lib().hvr_relation_probs_workspace_bytes(Mq, Mk), q.device, 'relation_probs')
     _check(lib().hvr_relation_probs(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(P), ldp, Mq, Mk, D, float(scale), _dt(q),
                                     STAGING if staging is None else staging, _ptr(ws), ws.numel(), _stream()), 'hvr_relation_probs')
@@ -916,16 +921,25 @@ def unpack_conv_wgrad(dw, scale, shape, accumulate_into=None):
     return out
 
 
+def _loss_operands(labels, label_weights, bbox_targets, bbox_weights, n):
+    """The per-row (per-anchor) operands of the loss kernels as contiguous int64 / f32 tensors of the right length.  The results are
+    NAMED by the caller until after the launch: a converted copy passed as `_ptr(t.float())` dies with the expression, and the
+    caching allocator hands its block to the next temporary before the kernel has read it."""
+    assert labels.numel() == label_weights.numel() == n, 'labels / label_weights: one value per anchor (rows * A) or row'
+    assert bbox_targets.numel() == bbox_weights.numel() == 4 * n, 'bbox_targets / bbox_weights: four values per anchor or row'
+    return labels.contiguous(), label_weights.float().contiguous(), bbox_targets.float().contiguous(), bbox_weights.float().contiguous()
+
+
 def det_loss(logits, cls_off, reg_off, ncls, labels, label_weights, bbox_targets, bbox_weights, beta=1.0, w_cls=1.0, w_bbox=1.0):
     """BBoxHead.loss on a fused [R, ld] f32 logit matrix -> (out3 = [loss_cls, loss_bbox, acc] f32, dlogits [R, ld] f32)."""
     _need_cuda(logits, labels, label_weights, bbox_targets, bbox_weights)
     assert logits.dtype == torch.float32 and logits.is_contiguous() and labels.dtype == torch.long
+    labels, lw, bt, bw = _loss_operands(labels, label_weights, bbox_targets, bbox_weights, logits.shape[0])
     out3 = torch.empty(3, dtype=torch.float32, device=logits.device)
     dlogits = torch.empty_like(logits)
-    _check(lib().hvr_det_loss(_ptr(logits), logits.shape[1], cls_off, reg_off, ncls, _ptr(labels.contiguous()),
-                              _ptr(label_weights.float().contiguous()), _ptr(bbox_targets.float().contiguous()),
-                              _ptr(bbox_weights.float().contiguous()), logits.shape[0], float(beta), float(w_cls), float(w_bbox),
-                              _ptr(out3), _ptr(dlogits), _stream()), 'hvr_det_loss')
+    _check(lib().hvr_det_loss(_ptr(logits), logits.shape[1], cls_off, reg_off, ncls, _ptr(labels), _ptr(lw), _ptr(bt), _ptr(bw),
+                              logits.shape[0], float(beta), float(w_cls), float(w_bbox), _ptr(out3), _ptr(dlogits), _stream()),
+           'hvr_det_loss')
     return out3, dlogits
 
 
@@ -991,12 +1005,13 @@ def rpn_loss(o, A, labels, label_weights, bbox_targets, bbox_weights, counts, be
     _need_cuda(o, labels, label_weights, bbox_targets, bbox_weights, counts)
     assert o.dtype == torch.float32 and o.dim() == 2 and o.is_contiguous() and labels.dtype == torch.long
     rows = o.shape[0]
-    assert labels.numel() == rows * A and counts.dtype == torch.int32
+    assert A >= 1 and o.shape[1] >= 5 * A and counts.dtype == torch.int32 and counts.numel() == 2
+    labels, lw, bt, bw = _loss_operands(labels, label_weights, bbox_targets, bbox_weights, rows * A)
+    counts = counts.contiguous()
     out2 = torch.empty(2, dtype=torch.float32, device=o.device)
     d_o = torch.empty_like(o)
-    _check(lib().hvr_rpn_loss(_ptr(o), o.shape[1], int(A), rows, _ptr(labels.contiguous()), _ptr(label_weights.contiguous()),
-                              _ptr(bbox_targets.contiguous()), _ptr(bbox_weights.contiguous()), _ptr(counts), float(beta), _ptr(out2),
-                              _ptr(d_o), _stream()), 'hvr_rpn_loss')
+    _check(lib().hvr_rpn_loss(_ptr(o), o.shape[1], int(A), rows, _ptr(labels), _ptr(lw), _ptr(bt), _ptr(bw), _ptr(counts),
+                              float(beta), _ptr(out2), _ptr(d_o), _stream()), 'hvr_rpn_loss')
     return out2, d_o
 
 
@@ -1120,12 +1135,12 @@ def det_loss_sampled(logits, cls_off, reg_off, ncls, labels, label_weights, bbox
     """hvr_det_loss in the OHEM form: weights are zero outside the selected rows, sel_counts int32 [2] their number."""
     _need_cuda(logits, labels, label_weights, bbox_targets, bbox_weights, sel_counts)
     assert logits.dtype == torch.float32 and logits.is_contiguous() and labels.dtype == torch.long and sel_counts.dtype == torch.int32
+    labels, lw, bt, bw = _loss_operands(labels, label_weights, bbox_targets, bbox_weights, logits.shape[0])
     out3 = torch.empty(3, dtype=torch.float32, device=logits.device)
     dlogits = torch.empty_like(logits)
-    _check(lib().hvr_det_loss_sampled(_ptr(logits), logits.shape[1], cls_off, reg_off, ncls, _ptr(labels.contiguous()),
-                                      _ptr(label_weights.float().contiguous()), _ptr(bbox_targets.float().contiguous()),
-                                      _ptr(bbox_weights.float().contiguous()), logits.shape[0], _ptr(sel_counts), float(beta),
-                                      _ptr(out3), _ptr(dlogits), _stream()), 'hvr_det_loss_sampled')
+    _check(lib().hvr_det_loss_sampled(_ptr(logits), logits.shape[1], cls_off, reg_off, ncls, _ptr(labels), _ptr(lw), _ptr(bt), _ptr(bw),
+                                      logits.shape[0], _ptr(sel_counts), float(beta), _ptr(out3), _ptr(dlogits), _stream()),
+           'hvr_det_loss_sampled')
     return out3, dlogits
 
 

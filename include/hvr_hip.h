@@ -246,6 +246,10 @@ int hvr_relation_fwd_grouped(const void* Q, int64_t ldq, int64_t gsq, const void
  *   hvr_relation_probs : P = softmax(scale * Q K^T) as a [Mq][ldp] matrix in `dtype` (ldp = keys padded to 128, padding
  *                        columns zero), the f32 logits never materialised;
  *   hvr_relation_dscore: dS = scale * P * (dP - rowsum(dO * O))  (softmax backward, logit scale folded in).
+ * hvr_relation_probs takes at most 16 384 keys (128 blocks of 128: its normalising sweep keeps one factor per block in a fixed
+ * table); a larger Mk is HVR_EUNSUPPORTED, before anything is launched.  The same limit holds for hvr_relation_fwd /
+ * hvr_relation_fwd_grouped on HVR_F16S operands whenever they normalise P in a sweep of their own (Mq >= 1024, or
+ * HVR_SPLIT_NORMALIZE=1); the other relation paths fold the block factors into the apply pass and have no such limit.
  * With them  dV = P^T dO,  dP = dO V^T,  dQ = dS K,  dK = dS^T Q  are hvr_gemm / hvr_transpose_pad calls
  * (hvrnet_amd/ops.py: RelationFunction). */
 size_t hvr_relation_probs_workspace_bytes(int Mq, int Mk);
@@ -260,7 +264,10 @@ int hvr_relation_dscore(const void* P, const void* dP, const void* dO, int64_t l
  *   hvr_det_loss : BBoxHead.loss for class-agnostic boxes (mmdet/models/bbox_heads/bbox_head.py:100-130 with
  *                  losses/cross_entropy_loss.py:9-20, losses/smooth_l1_loss.py:9-18, losses/accuracy.py:4-21):
  *                  out3 = (loss_cls, loss_bbox, acc) and dlogits = d(w_cls*loss_cls + w_bbox*loss_bbox)/d logits for a
- *                  logit matrix [R][ldl] holding ncls class logits at cls_off and 4 box deltas at reg_off. */
+ *                  logit matrix [R][ldl] holding ncls class logits at cls_off and 4 box deltas at reg_off.
+ *                  PRECONDITION (also hvr_det_loss_sampled and hvr_ce_rows): every labels[r] lies in [0, ncls).  The labels are
+ *                  device memory and are not range-checked (the reference's F.cross_entropy raises); a label outside the
+ *                  range reads logits[r][cls_off + label], whatever lies there. */
 int hvr_relu_bwd(const void* dY, const void* Y, void* dZ, int64_t n, int dtype, void* stream);
 size_t hvr_colsum_workspace_bytes(int M, int N);
 int hvr_colsum(const void* dY, float* db, int M, int N, int64_t ld, int dtype, void* ws, size_t ws_bytes, void* stream);
@@ -421,10 +428,13 @@ int hvr_transpose_pad(const void* in, void* out, int R, int C, int64_t ldx, int6
  *   hvr_rpn_loss       : AnchorHead.loss_single for one level, sigmoid objectness (anchor_head.py:141-160 with
  *                        losses/cross_entropy_loss.py:23-37 and losses/smooth_l1_loss.py:9-18) on the fused RPN head
  *                        output o [rows][ldo] (A logits then 4A deltas per position): out2 = (loss_rpn_cls,
- *                        loss_rpn_bbox), d_o = d(sum of both)/d o; avg_factor = max(counts[0],1) + max(counts[1],1).
- *   hvr_ce_rows        : per-row softmax cross entropy (`reduction_override='none'`, selsa_rcnn.py:209-218).
+ *                        loss_rpn_bbox), d_o = d(sum of both)/d o, every element written (columns 5A .. ldo: zero);
+ *                        avg_factor = max(counts[0],1) + max(counts[1],1).
+ *   hvr_ce_rows        : per-row softmax cross entropy (`reduction_override='none'`, selsa_rcnn.py:209-218); labels in
+ *                        [0, ncls), unchecked (see hvr_det_loss).
  *   hvr_det_loss_sampled: hvr_det_loss in the OHEM form (selsa_rcnn.py:224-232): rows outside cat(pos_inds, neg_inds)
- *                        carry zero weights; smooth-L1 and the accuracy are averaged over sel_counts[0]+sel_counts[1]. */
+ *                        carry zero weights; smooth-L1 and the accuracy are averaged over sel_counts[0]+sel_counts[1]
+ *                        (at least 1); labels in [0, ncls), unchecked (see hvr_det_loss). */
 size_t hvr_max_iou_assign_workspace_bytes(int n, int k);
 int hvr_max_iou_assign(const float* boxes, int ldb, int n, const float* gts, int k, const uint8_t* valid, float pos_iou_thr,
                        float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int64_t* gt_inds, float* max_overlaps, void* ws,
