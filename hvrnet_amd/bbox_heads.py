@@ -93,18 +93,26 @@ class BBoxHead(nn.Module, PackedMixin):
                                  float(scale_factor) if rescale else 0.0)
 
     def _nms(self, boxes, scores, cfg, defer=False):
-        dets, labels, n = native.multiclass_nms(boxes, scores, cfg.score_thr, cfg.nms['iou_thr'], cfg.max_per_img)
+        # the operator cfg.nms['type'] names: greedy ('nms') or Soft-NMS ('soft_nms'); both return the same device triple
+        dets, labels, n = native.readout_nms(boxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
         if defer:  # (dets [max,5], labels [max], n [1]) stay on the device; the caller reads them later in one go
             return (dets, labels, n), None
         k = int(n.item())  # the only host read of the read-out
         return dets[:k], labels[:k]
 
+    def _nms_clips(self, boxes, scores, cfg):
+        """Soft-NMS read-out of W clips' decoded (boxes [R,4], scores [R,ncls]) lists in one launch pair (P = W problems of
+        hvr_multiclass_soft_nms) -> W deferred triples (dets [max,5], labels [max], n [1]), each equal to `_nms(..., defer=True)`'s."""
+        nms = dict(cfg.nms)
+        assert nms.pop('type') == 'soft_nms'
+        dets, labels, n = native.multiclass_soft_nms(torch.stack(boxes), torch.stack(scores), cfg.score_thr, nms.pop('iou_thr'),
+                                                     cfg.max_per_img, **nms)
+        return [(dets[w], labels[w], n[w:w + 1]) for w in range(len(boxes))]
+
     def get_det_bboxes(self, rois, cls_score, bbox_pred, img_shape, scale_factor, rescale=False, cfg=None, defer=False):
         scores, bboxes = self._decode(rois, cls_score, bbox_pred, img_shape, scale_factor, rescale)
         if cfg is None:
             return bboxes, scores
-        if cfg.nms.get('type', 'nms') != 'nms':
-            raise NotImplementedError('only greedy nms is on the HVR hot path')
         return self._nms(bboxes, scores, cfg, defer)
 
 
@@ -514,7 +522,8 @@ class HRNMPBBoxHead(_RelationHead):
 
         pairs = list(zip(cls_scores, bbox_preds))
         # The two branches' read-outs are independent chains of small, latency-bound launches (decode, 30 one-workgroup
-        # class sweeps, a one-workgroup merge: ~150 us each on an otherwise idle chip): with deferred results the second
+        # class sweeps, a one-workgroup merge: 136 us each on an otherwise idle chip with greedy NMS, about 510 us with
+        # Soft-NMS on the benchmark clip -- profiles/softnms_readout.txt): with deferred results the second
         # runs on a side stream beside the first.  Same kernels on the same inputs: identical results.
         if defer and self.readout_streams and len(pairs) == 2 and rois.is_cuda and cfg is not None and hasattr(cfg, 'nms'):
             main = torch.cuda.current_stream(rois.device)

@@ -4,7 +4,7 @@
   delta2bbox           mmdet/core/bbox/transforms.py:34-111          (device kernel)
   bbox2roi             mmdet/core/bbox/transforms.py:149-168         (memory plumbing)
   bbox2result          mmdet/core/bbox/transforms.py:181-199         (D2H + split per class)
-  multiclass_nms       mmdet/core/post_processing/bbox_nms.py:6-66   (device kernel)
+  multiclass_nms       mmdet/core/post_processing/bbox_nms.py:6-66   (device kernels; nms_cfg type 'nms' or 'soft_nms')
   bbox_flip / bbox_mapping / bbox_mapping_back   mmdet/core/bbox/transforms.py:114-146          (device kernels)
   merge_aug_proposals / merge_aug_bboxes / merge_aug_scores   mmdet/core/post_processing/merge_augs.py:8-77   (device kernels)
 """
@@ -91,22 +91,28 @@ def multiclass_nms(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1, s
     if score_factors is not None or multi_bboxes.shape[1] != 4:
         raise NotImplementedError('class-specific boxes / score_factors are outside the HVR hot path')
     nms_cfg_ = dict(nms_cfg)
-    if nms_cfg_.pop('type', 'nms') != 'nms':
-        raise NotImplementedError('only greedy nms is on the HVR hot path (configs use type="nms")')
-    iou_thr = nms_cfg_.pop('iou_thr')
+    kind = nms_cfg_.get('type', 'nms')
+    if kind not in ('nms', 'soft_nms'):
+        raise NotImplementedError('nms type %r is outside the HVR hot path (nms, soft_nms)' % (kind,))
+    if kind == 'soft_nms':
+        native._soft_method(nms_cfg_.get('method', 'linear'))     # ValueError before any launch (nms_wrapper.py:88-90)
     R, nfg = multi_bboxes.shape[0], multi_scores.shape[1] - 1
     boxes, scores = multi_bboxes.float(), multi_scores.float()
+
+    def run(cap):       # the operator the config names (bbox_nms.py:32-34), remaining keys handed on as the reference does
+        return native.readout_nms(boxes, scores, score_thr, nms_cfg_, cap)
+
     if max_num < 0:
         # The reference's default max_num = -1 is not "no cap": `bboxes.shape[0] > max_num` is always true, so the survivors are
         # sorted by score and `inds[:max_num]` drops the last |max_num| of them (bbox_nms.py:55-59).  Reproduced as written:
         # count the survivors first (uncapped pass, class order), then cut to count + max_num in score order.
-        dets, labels, n = native.multiclass_nms(boxes, scores, score_thr, iou_thr, max(R * nfg, 1))
+        dets, labels, n = run(max(R * nfg, 1))
         k = int(n.item()) + int(max_num)
         if k <= 0:
             return dets[:0], labels[:0]
-        dets, labels, n = native.multiclass_nms(boxes, scores, score_thr, iou_thr, k)
+        dets, labels, n = run(k)
         return dets[:k], labels[:k]
-    dets, labels, n = native.multiclass_nms(boxes, scores, score_thr, iou_thr, max(int(max_num), 1))
+    dets, labels, n = run(max(int(max_num), 1))
     k = int(n.item())
     return dets[:k], labels[:k]
 

@@ -78,6 +78,10 @@ hipError_t run_rpn_gather(const float*, const long long*, const int*, int, int, 
 hipError_t run_multiclass_nms(const float*, const float*, int, int, float, float, int, float*, long long*, int*, void*,
                               hipStream_t);
 size_t multiclass_nms_workspace_bytes(int R, int ncls);
+hipError_t run_soft_nms(const float*, int, float, int, float, float, float*, long long*, int*, hipStream_t);
+hipError_t run_multiclass_soft_nms(const float*, const float*, int, int, int, float, float, int, float, float, int, float*, long long*, int*,
+                                   void*, hipStream_t);
+size_t multiclass_soft_nms_workspace_bytes(int P, int R, int ncls);
 hipError_t run_stem_fused(const float*, const void*, const float*, void*, int, int, int, int, hipStream_t);
 }  // namespace hvr
 
@@ -1344,6 +1348,49 @@ int hvr_multiclass_nms(const float* boxes, const float* scores, int R, int ncls,
   return check_launch(run_multiclass_nms(boxes, scores, R, ncls, score_thr, iou_thr, max_num, dets, (long long*)labels, n_out,
                                          ws, (hipStream_t)stream),
                       "hvr_multiclass_nms");
+}
+
+// ---- Soft-NMS read-out (softnms.hip) ----
+size_t hvr_soft_nms_workspace_bytes(int n) { (void)n; return 256; }   // (the single list lives in LDS; kept for the calling convention)
+
+int hvr_soft_nms(const float* dets, int n, float iou_thr, int method, float sigma, float min_score, float* out_dets, int64_t* inds,
+                 int32_t* n_out, void* ws, size_t ws_bytes, void* stream) {
+  (void)ws;
+  if (!n_out) return fail(HVR_EINVAL, "null n_out");
+  if (method != 1 && method != 2) return fail(HVR_EINVAL, "hvr_soft_nms: method is 1 (linear) or 2 (gaussian), got %d", method);
+  if (n == 0) {
+    (void)run_zero_fill(n_out, sizeof(int32_t), (hipStream_t)stream);
+    return HVR_OK;
+  }
+  if (!dets || !out_dets || !inds) return fail(HVR_EINVAL, "null pointer");
+  if (n < 0 || n > 512) return fail(HVR_EUNSUPPORTED, "hvr_soft_nms supports 0 <= n <= 512, got %d", n);
+  if (ws_bytes < hvr_soft_nms_workspace_bytes(n)) return fail(HVR_EWORKSPACE, "soft nms workspace too small");
+  return check_launch(run_soft_nms(dets, n, iou_thr, method, sigma, min_score, out_dets, (long long*)inds, n_out, (hipStream_t)stream),
+                      "hvr_soft_nms");
+}
+
+size_t hvr_multiclass_soft_nms_workspace_bytes(int P, int R, int ncls) {
+  return multiclass_soft_nms_workspace_bytes(P > 0 ? P : 1, R > 0 ? R : 1, ncls > 1 ? ncls : 2);
+}
+
+int hvr_multiclass_soft_nms(const float* boxes, const float* scores, int P, int R, int ncls, float score_thr, float iou_thr, int method,
+                            float sigma, float min_score, int max_num, float* dets, int64_t* labels, int32_t* n_out, void* ws,
+                            size_t ws_bytes, void* stream) {
+  if (!n_out) return fail(HVR_EINVAL, "null n_out");
+  if (P < 1) return fail(HVR_EINVAL, "hvr_multiclass_soft_nms needs P >= 1 problems, got %d", P);
+  if (method != 1 && method != 2) return fail(HVR_EINVAL, "hvr_multiclass_soft_nms: method is 1 (linear) or 2 (gaussian), got %d", method);
+  if (R == 0) {
+    (void)run_zero_fill(n_out, sizeof(int32_t) * (size_t)P, (hipStream_t)stream);
+    return HVR_OK;
+  }
+  if (!boxes || !scores || !dets || !labels || !ws) return fail(HVR_EINVAL, "null pointer");
+  if (R < 0 || R > 512) return fail(HVR_EUNSUPPORTED, "hvr_multiclass_soft_nms supports R <= 512, got %d", R);
+  if (ncls < 2 || ncls - 1 > 128) return fail(HVR_EUNSUPPORTED, "hvr_multiclass_soft_nms supports 1 .. 128 foreground classes");
+  if (max_num <= 0) return fail(HVR_EINVAL, "hvr_multiclass_soft_nms needs max_num > 0");
+  if (ws_bytes < hvr_multiclass_soft_nms_workspace_bytes(P, R, ncls)) return fail(HVR_EWORKSPACE, "multiclass soft nms workspace too small");
+  return check_launch(run_multiclass_soft_nms(boxes, scores, P, R, ncls, score_thr, iou_thr, method, sigma, min_score, max_num, dets,
+                                              (long long*)labels, n_out, ws, (hipStream_t)stream),
+                      "hvr_multiclass_soft_nms");
 }
 
 // ---- plumbing ----

@@ -757,79 +757,7 @@ __global__ __launch_bounds__(1024) void mc_nms_merge_kernel(const float* __restr
     }
   }
   __syncthreads();
-  int nout = total;
-  if (total > max_num && sp2 == 0) {
-    // no LDS for the select stage (max_num close to the list length, e.g. the reference's max_num = -1 quirk): sort the
-    // whole list in place -- same order (score desc, list position asc), the padding entries (key 0) go last
-    bitonic_sort_pairs(key, idx, np2);
-    nout = max_num;
-  } else if (total > max_num) {
-    // top max_num by (score desc, list position asc): radix-select the max_num-th key (4 passes over the LDS list),
-    // gather the entries above it plus the first ties, and sort only those (bbox_nms.py:54-61 sorts everything and
-    // cuts; the survivors and their order are the same)
-    __shared__ int hist[256];
-    __shared__ uint32_t sh_prefix, sh_remaining;
-    __shared__ int sh_count;
-    uint32_t* skey = idx + np2;
-    uint32_t* sidx = skey + sp2;
-    uint32_t prefix = 0u, remaining = (uint32_t)max_num;
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = 24 - 8 * pass;
-      for (int i = threadIdx.x; i < 256; i += blockDim.x) hist[i] = 0;
-      __syncthreads();
-      const uint32_t himask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
-      for (int i = threadIdx.x; i < total; i += blockDim.x) {
-        const uint32_t u = key[i];
-        if ((u & himask) == prefix) atomicAdd(&hist[(u >> shift) & 255], 1);
-      }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        uint32_t rem = remaining;
-        int b = 255;
-        for (; b > 0; --b) {
-          if ((uint32_t)hist[b] >= rem) break;
-          rem -= hist[b];
-        }
-        sh_prefix = prefix | ((uint32_t)b << shift);
-        sh_remaining = rem;
-      }
-      __syncthreads();
-      prefix = sh_prefix;
-      remaining = sh_remaining;
-      __syncthreads();
-    }
-    const uint32_t thr_key = prefix;  // key of the max_num-th entry; `remaining` of the entries equal to it are taken
-    if (threadIdx.x == 0) sh_count = 0;
-    for (int i = threadIdx.x; i < sp2; i += blockDim.x) { skey[i] = 0u; sidx[i] = 0xffffffffu; }
-    __syncthreads();
-    for (int i = threadIdx.x; i < total; i += blockDim.x) {
-      if (key[i] > thr_key) {
-        const int pos = atomicAdd(&sh_count, 1);
-        skey[pos] = key[i];
-        sidx[pos] = idx[i];
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) {  // ties at the threshold, lowest list position first (the list is in ascending idx order)
-      int taken = 0;
-      const int base = sh_count;
-      for (int i0 = 0; i0 < total && taken < (int)remaining; i0 += 64) {
-        const int i = i0 + threadIdx.x;
-        const bool eq = i < total && key[i] == thr_key;
-        const unsigned long long m = __ballot(eq);
-        const int before = __popcll(m & ((1ull << threadIdx.x) - 1ull));
-        if (eq && taken + before < (int)remaining) {
-          skey[base + taken + before] = thr_key;
-          sidx[base + taken + before] = idx[i];
-        }
-        taken += __popcll(m);
-      }
-    }
-    __syncthreads();
-    bitonic_sort_pairs(skey, sidx, sp2);
-    idx = sidx;
-    nout = max_num;
-  }
+  const int nout = mc_cut_to_max_num(key, idx, total, np2, max_num, sp2);
   for (int j = threadIdx.x; j < nout; j += blockDim.x) {
     const uint32_t e = idx[j];
     const int c = e >> 16, r = e & 0xffff;

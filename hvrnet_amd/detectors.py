@@ -336,6 +336,16 @@ class _WindowDetector(TwoStageDetector):
             head = self.bbox_head.forward_from_f1 if from_f1 else self.bbox_head
             cls_score, bbox_pred = head(feats, cur_range, key_dim=self.key_dim, all_res=False, clips=clips)[:2]
         l = int(cur_range['length'])
+        cfg = self.test_cfg.rcnn
+        if clips > 1 and cfg.nms.get('type', 'nms') == 'soft_nms':
+            # Soft-NMS: a class's rounds are serial (one wave per class), so W read-outs one after another queue W such chains;
+            # the decode stays per clip, then a branch's W read-outs go to ONE launch pair (P = W problems, W x 30 one-wave
+            # workgroups side by side).  Same kernels on the same rows: each clip's result equals its own call's bit for bit.
+            lists = [list(cls_score), list(bbox_pred)] if hvr else [[cls_score], [bbox_pred]]
+            dec = [[self.bbox_head._decode(key_rois[w], cs[w * l:(w + 1) * l], bp[w * l:(w + 1) * l], meta0[w]['img_shape'],
+                                           meta0[w]['scale_factor'], rescale) for cs, bp in zip(*lists)] for w in range(clips)]
+            per_branch = [self.bbox_head._nms_clips([d[b][1] for d in dec], [d[b][0] for d in dec], cfg) for b in range(len(lists[0]))]
+            return [[pb[w] for pb in per_branch] for w in range(clips)]
         out = []
         for w in range(clips):
             rows = slice(w * l, (w + 1) * l)
@@ -513,8 +523,6 @@ class _WindowDetector(TwoStageDetector):
             mb, ms = native.merge_aug_dets(torch.stack([b[i] for b in aug_bboxes], 0), torch.stack([s_[i] for s_ in aug_scores], 0),
                                            img_w, scale, flip)
             if rcnn_test_cfg is not None and hasattr(rcnn_test_cfg, 'nms'):
-                if rcnn_test_cfg.nms.get('type', 'nms') != 'nms':
-                    raise NotImplementedError('only greedy nms is on the HVR hot path')
                 outs.append(self.bbox_head._nms(mb, ms, rcnn_test_cfg, defer))
             else:
                 outs.append((mb, ms))

@@ -157,6 +157,10 @@ SYMBOLS = {
     'hvr_det_decode': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp]),
     'hvr_multiclass_nms_workspace_bytes': (_sz, [_i, _i]),
     'hvr_multiclass_nms': (_i, [_vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'hvr_soft_nms_workspace_bytes': (_sz, [_i]),
+    'hvr_soft_nms': (_i, [_vp, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'hvr_multiclass_soft_nms_workspace_bytes': (_sz, [_i, _i, _i]),
+    'hvr_multiclass_soft_nms': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'hvr_cast': (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     'hvr_cast_scaled': (_i, [_vp, _vp, _i64, _i, _i, _f, _vp]),
     'hvr_permute_nchw_nhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -1273,6 +1277,66 @@ def multiclass_nms(boxes, scores, score_thr, iou_thr, max_num):
                                     float(iou_thr), int(max_num), _ptr(dets), _ptr(labels), _ptr(n_out), _ptr(ws),
                                     ws.numel(), _stream()), 'hvr_multiclass_nms')
     return dets, labels, n_out
+
+
+SOFT_NMS_METHODS = {'linear': 1, 'gaussian': 2}     # nms_wrapper.py:87
+
+
+def _soft_method(method):
+    if method not in SOFT_NMS_METHODS:
+        raise ValueError('Invalid method for SoftNMS: {}'.format(method))      # nms_wrapper.py:88-90
+    return SOFT_NMS_METHODS[method]
+
+
+def soft_nms(dets, iou_thr, method='linear', sigma=0.5, min_score=1e-3):
+    """dets [n,5] f32 cuda (n <= 512) -> (out [n,5]: kept boxes with rescored scores in selection order, inds [n] int64,
+    n_out int32[1]) device tensors; rows behind n_out are zero."""
+    code = _soft_method(method)
+    _need_cuda(dets)
+    dets = dets.contiguous().float()
+    n = dets.shape[0]
+    alloc = torch.empty if n > 0 else torch.zeros
+    out = alloc((n, 5), dtype=torch.float32, device=dets.device)
+    inds = alloc(n, dtype=torch.long, device=dets.device)
+    n_out = alloc(1, dtype=torch.int32, device=dets.device)
+    ws = _workspace(lib().hvr_soft_nms_workspace_bytes(n), dets.device, 'softnms1')
+    _check(lib().hvr_soft_nms(_ptr(dets), n, float(iou_thr), code, float(sigma), float(min_score), _ptr(out), _ptr(inds), _ptr(n_out),
+                              _ptr(ws), ws.numel(), _stream()), 'hvr_soft_nms')
+    return out, inds, n_out
+
+
+def multiclass_soft_nms(boxes, scores, score_thr, iou_thr, max_num, method='linear', sigma=0.5, min_score=1e-3):
+    """boxes [R,4] / [P,R,4], scores [R,ncls] / [P,R,ncls] f32 -> (dets [max_num,5], labels [max_num] int64, n int32[1]) device
+    tensors, with a leading P on each for the batched form (P problems, one launch pair)."""
+    code = _soft_method(method)
+    _need_cuda(boxes, scores)
+    batched = scores.dim() == 3
+    P = scores.shape[0] if batched else 1
+    R, ncls = scores.shape[-2:]
+    assert boxes.shape[-2:] == (R, 4) and boxes.dim() == scores.dim() and (not batched or boxes.shape[0] == P)
+    alloc = torch.empty if R > 0 else torch.zeros
+    dets = alloc((P, max_num, 5), dtype=torch.float32, device=boxes.device)
+    labels = alloc((P, max_num), dtype=torch.long, device=boxes.device)
+    n_out = alloc(P, dtype=torch.int32, device=boxes.device)
+    ws = _workspace(lib().hvr_multiclass_soft_nms_workspace_bytes(P, R, ncls), boxes.device, 'mcsoftnms')
+    _check(lib().hvr_multiclass_soft_nms(_ptr(boxes.contiguous().float()), _ptr(scores.contiguous().float()), P, R, ncls, float(score_thr),
+                                         float(iou_thr), code, float(sigma), float(min_score), int(max_num), _ptr(dets), _ptr(labels),
+                                         _ptr(n_out), _ptr(ws), ws.numel(), _stream()), 'hvr_multiclass_soft_nms')
+    if batched:
+        return dets, labels, n_out
+    return dets[0], labels[0], n_out
+
+
+def readout_nms(boxes, scores, score_thr, nms_cfg, max_num):
+    """The multiclass read-out named by an mmdetection nms_cfg (bbox_nms.py:32-34 resolves `type` by name): 'nms' -> multiclass_nms,
+    'soft_nms' -> multiclass_soft_nms with the remaining keys (iou_thr, method, sigma, min_score).  Any other type raises."""
+    cfg = dict(nms_cfg)
+    kind = cfg.pop('type', 'nms')
+    if kind == 'nms':
+        return multiclass_nms(boxes, scores, score_thr, cfg['iou_thr'], max_num)
+    if kind == 'soft_nms':
+        return multiclass_soft_nms(boxes, scores, score_thr, cfg.pop('iou_thr'), max_num, **cfg)
+    raise NotImplementedError('nms type %r is outside the HVR hot path (nms, soft_nms)' % (kind,))
 
 
 def cast(x, dtype, scale=None):

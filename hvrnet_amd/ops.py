@@ -7,6 +7,7 @@ signatures and error behaviour:
   RoIAlign(out_size, spatial_scale, sample_num=0, use_torchvision=False)   roi_align/roi_align.py:59-87
   roi_align(features, rois, out_size, spatial_scale, sample_num)           roi_align/roi_align.py:56
   nms(dets, iou_thr, device_id=None) -> (dets[inds], inds)                  nms/nms_wrapper.py:8-61
+  soft_nms(dets, iou_thr, method='linear', sigma=0.5, min_score=1e-3)      nms/nms_wrapper.py:64-102
 plus `relation(q, k, v, scale)`: the relation core as an autograd Function with a HIP backward (training path).
 CPU tensors raise NotImplementedError exactly like the reference's RoIAlign (roi_align.py:27-28);
 NMS follows the reference's CPU semantics (`IoU >= thr` suppresses, nms_cpu.cpp:55).
@@ -149,3 +150,19 @@ def nms(dets, iou_thr, device_id=None):
     if is_numpy:
         inds = inds.cpu().numpy()
     return dets[inds, :], inds
+
+
+def soft_nms(dets, iou_thr, method='linear', sigma=0.5, min_score=1e-3):
+    """nms_wrapper.soft_nms (nms_wrapper.py:64-102) on the device: (new_dets [k,5] = the kept boxes with their rescored scores in
+    selection order, inds [k] int64).  At most 512 boxes.  One host read (k); the reference copies the list to numpy and back."""
+    if method not in native.SOFT_NMS_METHODS:
+        raise ValueError('Invalid method for SoftNMS: {}'.format(method))
+    if not isinstance(dets, torch.Tensor):
+        raise TypeError('dets must be a Tensor, but got {}'.format(type(dets)))
+    if not dets.is_cuda:
+        raise NotImplementedError('hvr soft_nms runs on the GPU only (no CPU fallback)')
+    if dets.shape[0] == 0:
+        return dets.new_zeros((0, 5)), dets.new_zeros(0, dtype=torch.long)
+    out, inds, n = native.soft_nms(dets, iou_thr, method, sigma, min_score)
+    k = int(n.item())
+    return out[:k].to(dets.dtype), inds[:k]

@@ -395,6 +395,33 @@ int hvr_multiclass_nms(const float* boxes, const float* scores, int R, int ncls,
                        int max_num, float* dets, int64_t* labels, int32_t* n_out, void* ws, size_t ws_bytes,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Soft-NMS read-out (test_cfg.rcnn.nms type='soft_nms').  Replaces soft_nms (mmdet/ops/nms/nms_wrapper.py:64-102) +
+ * soft_nms_cpu (mmdet/ops/nms/src/soft_nms_cpu.pyx:22-127) and multiclass_nms around it
+ * (mmdet/core/post_processing/bbox_nms.py:32-61, which resolves the operator by name) with no host round trip: the reference
+ * goes to numpy once per class (nms_wrapper.py:77-79).  method 1 = linear (weight 1 - IoU above iou_thr), 2 = gaussian
+ * (weight exp(-IoU^2 / sigma)); entries whose rescored value falls below min_score leave the list.  The arithmetic is the
+ * compiled .pyx's mix of f32 and f64 (hvrnet_amd/csrc/softnms.hip).
+ *   hvr_soft_nms:            dets [n][5] f32 (x1,y1,x2,y2,score) -> out_dets [n][5] = the kept boxes with their RESCORED scores in
+ *                            selection order, inds [n] int64 their input indices, *n_out the count (device int32); rows behind it
+ *                            are zeroed.  n <= 512.
+ *   hvr_multiclass_soft_nms: P >= 1 independent problems in one launch pair.  boxes [P][R][4], scores [P][R][ncls] (column 0 =
+ *                            background).  Per foreground class the rows with score > score_thr (ascending row) go through
+ *                            soft-NMS; the classes' lists (selection order, rescored scores) are concatenated in class order
+ *                            and, if more than max_num remain, cut to the max_num highest rescored scores (descending; equal
+ *                            scores: lower position in the concatenated list).  dets [P][max_num][5], labels [P][max_num] int64
+ *                            (0-based foreground class), n_out [P] device int32; rows behind n_out[p] come back zeroed.
+ *                            R <= 512, at most 128 foreground classes, max_num > 0.  R == 0 (and n == 0 above) writes only the
+ *                            counts (zero): dets / labels / inds are not touched.
+ * ---------------------------------------------------------------------------------- */
+size_t hvr_soft_nms_workspace_bytes(int n);
+int hvr_soft_nms(const float* dets, int n, float iou_thr, int method, float sigma, float min_score, float* out_dets, int64_t* inds,
+                 int32_t* n_out, void* ws, size_t ws_bytes, void* stream);
+size_t hvr_multiclass_soft_nms_workspace_bytes(int P, int R, int ncls);
+int hvr_multiclass_soft_nms(const float* boxes, const float* scores, int P, int R, int ncls, float score_thr, float iou_thr, int method,
+                            float sigma, float min_score, int max_num, float* dets, int64_t* labels, int32_t* n_out, void* ws,
+                            size_t ws_bytes, void* stream);
+
 /* ---- layout / dtype plumbing at the API boundary ---- */
 /* any pair of the four dtypes; pairs other than f32 <-> bf16 move 8 elements per thread: n % 8 == 0 and 16-byte aligned buffers
  * (split half: n % 32 == 0 -- a contiguous tensor whose last dimension is a multiple of 32 -- and 128-byte alignment) */
