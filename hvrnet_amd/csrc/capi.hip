@@ -82,6 +82,8 @@ hipError_t run_soft_nms(const float*, int, float, int, float, float, float*, lon
 hipError_t run_multiclass_soft_nms(const float*, const float*, int, int, int, float, float, int, float, float, int, float*, long long*, int*,
                                    void*, hipStream_t);
 size_t multiclass_soft_nms_workspace_bytes(int P, int R, int ncls);
+hipError_t run_seq_nms(const float*, const float*, int, int, int, float, float, float, int, int, float*, long long*, int*, void*, int, hipStream_t);
+size_t seq_nms_workspace_bytes(int F, int R, int ncls);
 hipError_t run_stem_fused(const float*, const void*, const float*, void*, int, int, int, int, hipStream_t);
 }  // namespace hvr
 
@@ -1391,6 +1393,42 @@ int hvr_multiclass_soft_nms(const float* boxes, const float* scores, int P, int 
   return check_launch(run_multiclass_soft_nms(boxes, scores, P, R, ncls, score_thr, iou_thr, method, sigma, min_score, max_num, dets,
                                               (long long*)labels, n_out, ws, (hipStream_t)stream),
                       "hvr_multiclass_soft_nms");
+}
+
+// ---- Seq-NMS read-out of a whole video (seqnms.hip) ----
+size_t hvr_seq_nms_workspace_bytes(int F, int R, int ncls) {
+  return seq_nms_workspace_bytes(F > 0 ? F : 1, R > 0 ? R : 1, ncls > 1 ? ncls : 2);
+}
+
+int hvr_seq_nms(const float* boxes, const float* scores, int F, int R, int ncls, float score_thr, float link_thr, float nms_thr,
+                int rescore, int max_num, float* dets, int64_t* labels, int32_t* n_out, void* ws, size_t ws_bytes, void* stream) {
+  return hvr_seq_nms_phases(boxes, scores, F, R, ncls, score_thr, link_thr, nms_thr, rescore, max_num, dets, labels, n_out, ws, ws_bytes, 7,
+                            stream);
+}
+
+int hvr_seq_nms_phases(const float* boxes, const float* scores, int F, int R, int ncls, float score_thr, float link_thr, float nms_thr,
+                       int rescore, int max_num, float* dets, int64_t* labels, int32_t* n_out, void* ws, size_t ws_bytes, int phases,
+                       void* stream) {
+  if (phases < 1 || phases > 7) return fail(HVR_EINVAL, "hvr_seq_nms_phases: phases is a mask of 1 (link) | 2 (path) | 4 (merge), got %d", phases);
+  if (!n_out) return fail(HVR_EINVAL, "null n_out");
+  if (F < 1) return fail(HVR_EINVAL, "hvr_seq_nms needs F >= 1 frames, got %d", F);
+  if (rescore != 1 && rescore != 2) return fail(HVR_EINVAL, "hvr_seq_nms: rescore is 1 (avg) or 2 (max), got %d", rescore);
+  if (!(score_thr >= 0.f)) return fail(HVR_EINVAL, "hvr_seq_nms needs score_thr >= 0 (path sums must be positive), got %g", (double)score_thr);
+  if (link_thr != link_thr || nms_thr != nms_thr) return fail(HVR_EINVAL, "hvr_seq_nms: NaN threshold");
+  if (max_num <= 0) return fail(HVR_EINVAL, "hvr_seq_nms needs max_num > 0");
+  if (R < 0 || R > 512) return fail(HVR_EUNSUPPORTED, "hvr_seq_nms supports R <= 512, got %d", R);
+  if (F > 65535) return fail(HVR_EUNSUPPORTED, "hvr_seq_nms supports at most 65535 frames per video, got %d", F);
+  if (ncls < 2 || ncls - 1 > 128) return fail(HVR_EUNSUPPORTED, "hvr_seq_nms supports 1 .. 128 foreground classes");
+  if (R == 0) {
+    (void)run_zero_fill(n_out, sizeof(int32_t) * (size_t)F, (hipStream_t)stream);
+    return HVR_OK;
+  }
+  if (!boxes || !scores || !dets || !labels || !ws) return fail(HVR_EINVAL, "null pointer");
+  if (!aligned16(boxes) || !aligned16(ws)) return fail(HVR_EINVAL, "hvr_seq_nms: boxes and workspace must be 16-byte aligned");
+  if (ws_bytes < hvr_seq_nms_workspace_bytes(F, R, ncls)) return fail(HVR_EWORKSPACE, "seq nms workspace too small");
+  return check_launch(run_seq_nms(boxes, scores, F, R, ncls, score_thr, link_thr, nms_thr, rescore == 2, max_num, dets, (long long*)labels,
+                                  n_out, ws, phases, (hipStream_t)stream),
+                      "hvr_seq_nms");
 }
 
 // ---- plumbing ----

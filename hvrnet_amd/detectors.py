@@ -164,6 +164,20 @@ def _sampled_rois(results):
     return torch.cat([col[:, None], allb], 1), n
 
 
+def _pad_rows(x, rows):
+    """[n, k] -> [rows, k], the rows behind n zero (a zero score is never a candidate of the read-outs)."""
+    if x.shape[0] > rows:
+        raise ValueError('a key frame has %d rows, more than test_cfg.rpn.nms_post = %d' % (x.shape[0], rows))
+    return x if x.shape[0] == rows else torch.cat([x, x.new_zeros((rows - x.shape[0], x.shape[1]))], 0)
+
+
+def check_seq_nms_cfg(rcnn_cfg):
+    """Seq-NMS does the suppression itself (greedy within a frame, at rcnn.nms.iou_thr): it does not combine with Soft-NMS."""
+    kind = rcnn_cfg.nms.get('type', 'nms')
+    if kind != 'nms':
+        raise ValueError("seq_nms does the suppression itself: test_cfg.rcnn.nms type must be 'nms', got %r" % (kind,))
+
+
 class PendingWindow(object):
     """A window whose kernels are enqueued but whose results have not been read.  `result()` is the window's single
     host synchronisation: detections, labels, counts and the per-frame proposal counts arrive in one batch of
@@ -403,6 +417,38 @@ class _WindowDetector(TwoStageDetector):
     def simple_test_bboxes(self, x, img_meta, proposals, rcnn_test_cfg, rescale=False):
         raise NotImplementedError
 
+    # ---- raw read-out + Seq-NMS over a whole video (DESIGN.md "Seq-NMS read-out") ---------------------------------------
+    def _raw_readout(self, key_rois, cls_score, bbox_pred, meta0, rescale, counts_dev, full_count, exact):
+        """`raw=True` of forward_feat / forward_feat_frames: the key frame's decoded (boxes [n,4], scores [n,ncls]) device tensors per
+        output branch, before any NMS -> [(boxes, scores)] (SelsaRCNN) or [(boxes, scores)] * 2 (HNMBRCNN).  A speculative window
+        with a short frame (counts_dev != full_count, the window's one host read) is re-run through the exact path, as
+        PendingWindow.result does."""
+        if counts_dev is not None and bool((counts_dev != full_count).any().item()):
+            return exact()
+        boxes, scores = self.bbox_head.get_det_bboxes(key_rois, cls_score, bbox_pred, meta0['img_shape'], meta0['scale_factor'],
+                                                      rescale=rescale, cfg=None)
+        return [(boxes, scores)] if torch.is_tensor(boxes) else list(zip(boxes, scores))
+
+    def seq_nms_video(self, raws, link_iou_thr=0.5, rescore='avg'):
+        """Seq-NMS over one video's key frames.  raws: the raw read-outs (`forward_feat(..., raw=True)`) in frame order.  Per output
+        branch the frames' rows are padded to test_cfg.rpn.nms_post with zero scores, stacked, and go through ONE native.seq_nms call
+        with score_thr = rcnn.score_thr, nms_thr = rcnn.nms.iou_thr, max_num = rcnn.max_per_img.  -> one result per frame in
+        forward_feat's structure (30 per-class arrays, or [branch, final] for HNMBRCNN)."""
+        cfg = self.test_cfg.rcnn
+        check_seq_nms_cfg(cfg)
+        R = int(self.test_cfg.rpn.nms_post)
+        host = []
+        for b in range(len(raws[0])):
+            boxes = torch.stack([_pad_rows(r[b][0].float(), R) for r in raws], 0)
+            scores = torch.stack([_pad_rows(r[b][1].float(), R) for r in raws], 0)
+            host.append([t.cpu() for t in native.seq_nms(boxes, scores, cfg.score_thr, link_iou_thr, cfg.nms.iou_thr, cfg.max_per_img, rescore)])
+        single = isinstance(self, SelsaRCNN)      # one read-out branch, returned bare (subclasses included)
+        results = []
+        for t in range(len(raws)):
+            out = [bbox2result(d[t, :int(n[t])], l[t, :int(n[t])], self.bbox_head.num_classes) for d, l, n in host]
+            results.append(out[0] if single else out)
+        return results
+
     # ---- multi-scale / flip test-time augmentation (hnmb_rcnn.py:104-180, 640-698) ------------------------------------
     # x[t][a] = C4 map of frame t under augmentation a, img_meta[t][a] its meta (the MultiScaleFlipAug order: scale outer, flip
     # inner).  Per augmentation the window runs as forward_feat does; between the stages the boxes of all augmentations meet in
@@ -603,10 +649,14 @@ class SelsaRCNN(_WindowDetector):
             self.bbox_head.t_dim = int(test_cfg.bbox_head.t_dim)
             self.bbox_head.sampler_num = int(test_cfg.bbox_head.sampler_num)
 
-    def forward_feat(self, x=None, img_meta=None, proposals=None, rescale=False, defer=False, speculate=True):
-        """One window -> 30 per-class [k,5] arrays (selsa_rcnn.py:281-338); defer=True -> PendingWindow."""
+    def forward_feat(self, x=None, img_meta=None, proposals=None, rescale=False, defer=False, speculate=True, raw=False):
+        """One window -> 30 per-class [k,5] arrays (selsa_rcnn.py:281-338); defer=True -> PendingWindow; raw=True -> the decoded
+        key frame before NMS, [(boxes [n,4], scores [n,ncls])] device tensors (`_raw_readout`)."""
         w = self.window_tensors(x, img_meta, proposals, rescale, speculate=speculate and proposals is None)
         cls_score, bbox_pred = self.bbox_head(w['roi_feats'], w['cur_range'], key_dim=self.key_dim, all_res=False)[:2]
+        if raw:
+            return self._raw_readout(w['key_rois'], cls_score, bbox_pred, img_meta[0], rescale, w['counts_dev'], w['full_count'],
+                                     lambda: self.forward_feat(x, img_meta, proposals, rescale, speculate=False, raw=True))
         branch, _ = self.bbox_head.get_det_bboxes(w['key_rois'], cls_score, bbox_pred, img_meta[0]['img_shape'],
                                                   img_meta[0]['scale_factor'], rescale=rescale, cfg=self.test_cfg.rcnn,
                                                   defer=True)
@@ -706,12 +756,16 @@ class SelsaRCNN(_WindowDetector):
         losses.update(loss_cls=hl['total'][0], loss_bbox=hl['total'][1], acc=hl['acc'])
         return losses
 
-    def forward_feat_frames(self, entries, c4s=None, rescale=False, defer=False):
+    def forward_feat_frames(self, entries, c4s=None, rescale=False, defer=False, raw=False):
         """forward_feat from T cached `frame_tensors` entries; c4s (the frames' C4 maps) back the exact re-run that
-        replaces the speculative result when some frame kept fewer than nms_post proposals."""
+        replaces the speculative result when some frame kept fewer than nms_post proposals.  raw=True: as in forward_feat."""
         f1, cur_range, key_rois, counts_dev, mx = self._frames_window(entries)
         meta0 = entries[0]['meta']
         cls_score, bbox_pred = self.bbox_head.forward_from_f1(f1, cur_range, key_dim=self.key_dim, all_res=False)[:2]
+        if raw:
+            metas = [e['meta'] for e in entries]
+            return self._raw_readout(key_rois, cls_score, bbox_pred, meta0, rescale, counts_dev, mx,
+                                     lambda: self.forward_feat(c4s, metas, None, rescale, speculate=False, raw=True))
         branch, _ = self.bbox_head.get_det_bboxes(key_rois, cls_score, bbox_pred, meta0['img_shape'], meta0['scale_factor'],
                                                   rescale=rescale, cfg=self.test_cfg.rcnn, defer=True)
         metas = [e['meta'] for e in entries]
@@ -735,11 +789,15 @@ class HNMBRCNN(_WindowDetector):
             self.bbox_head.t_dim = int(test_cfg.bbox_head.t_dim)
             self.bbox_head.sampler_num = int(test_cfg.bbox_head.sampler_num)
 
-    def forward_feat(self, x=None, img_meta=None, proposals=None, rescale=False, defer=False, speculate=True):
+    def forward_feat(self, x=None, img_meta=None, proposals=None, rescale=False, defer=False, speculate=True, raw=False):
         """-> [branch results, final results], each a list of 30 per-class [k,5] arrays (hnmb_rcnn.py:214-218);
-        defer=True -> PendingWindow whose result() is that list."""
+        defer=True -> PendingWindow whose result() is that list; raw=True -> the decoded key frame before NMS, per branch
+        (boxes [n,4], scores [n,ncls]) device tensors (`_raw_readout`)."""
         w = self.window_tensors(x, img_meta, proposals, rescale, speculate=speculate and proposals is None)
         cls_score, bbox_pred = self.bbox_head.forward_test(w['roi_feats'], [w['cur_range']], key_dim=self.key_dim, all_res=False)
+        if raw:
+            return self._raw_readout(w['key_rois'], cls_score, bbox_pred, img_meta[0], rescale, w['counts_dev'], w['full_count'],
+                                     lambda: self.forward_feat(x, img_meta, proposals, rescale, speculate=False, raw=True))
         branches, _ = self.bbox_head.get_det_bboxes(w['key_rois'], cls_score, bbox_pred, img_meta[0]['img_shape'],
                                                     img_meta[0]['scale_factor'], rescale=rescale, cfg=self.test_cfg.rcnn,
                                                     defer=True)
@@ -855,11 +913,15 @@ class HNMBRCNN(_WindowDetector):
         losses.update(self.bbox_head.loss(cls_scores, bbox_preds, *targets))
         return losses
 
-    def forward_feat_frames(self, entries, c4s=None, rescale=False, defer=False):
-        """forward_feat from T cached `frame_tensors` entries (see _WindowDetector.frame_tensors)."""
+    def forward_feat_frames(self, entries, c4s=None, rescale=False, defer=False, raw=False):
+        """forward_feat from T cached `frame_tensors` entries (see _WindowDetector.frame_tensors); raw=True: as in forward_feat."""
         f1, cur_range, key_rois, counts_dev, mx = self._frames_window(entries)
         meta0 = entries[0]['meta']
         cls_score, bbox_pred = self.bbox_head.forward_from_f1(f1, [cur_range], key_dim=self.key_dim, all_res=False)
+        if raw:
+            metas = [e['meta'] for e in entries]
+            return self._raw_readout(key_rois, cls_score, bbox_pred, meta0, rescale, counts_dev, mx,
+                                     lambda: self.forward_feat(c4s, metas, None, rescale, speculate=False, raw=True))
         branches, _ = self.bbox_head.get_det_bboxes(key_rois, cls_score, bbox_pred, meta0['img_shape'], meta0['scale_factor'],
                                                     rescale=rescale, cfg=self.test_cfg.rcnn, defer=True)
         metas = [e['meta'] for e in entries]

@@ -161,6 +161,9 @@ SYMBOLS = {
     'hvr_soft_nms': (_i, [_vp, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     'hvr_multiclass_soft_nms_workspace_bytes': (_sz, [_i, _i, _i]),
     'hvr_multiclass_soft_nms': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'hvr_seq_nms_workspace_bytes': (_sz, [_i, _i, _i]),
+    'hvr_seq_nms': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'hvr_seq_nms_phases': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     'hvr_cast': (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     'hvr_cast_scaled': (_i, [_vp, _vp, _i64, _i, _i, _f, _vp]),
     'hvr_permute_nchw_nhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -1325,6 +1328,42 @@ def multiclass_soft_nms(boxes, scores, score_thr, iou_thr, max_num, method='line
     if batched:
         return dets, labels, n_out
     return dets[0], labels[0], n_out
+
+
+SEQ_NMS_RESCORE = {'avg': 1, 'max': 2}
+
+
+def _seq_rescore(rescore):
+    if rescore not in SEQ_NMS_RESCORE:
+        raise ValueError('Invalid rescore for Seq-NMS: {} (avg, max)'.format(rescore))
+    return SEQ_NMS_RESCORE[rescore]
+
+
+def seq_nms(boxes, scores, score_thr, link_iou_thr=0.5, nms_iou_thr=0.3, max_num=300, rescore='avg', phases=None, out=None):
+    """Seq-NMS over one video: boxes [F,R,4], scores [F,R,ncls] f32 (the F key frames in time order, R <= 512, padding rows all
+    zero scores) -> (dets [F,max_num,5] with the rescored scores, labels [F,max_num] int64, n [F] int32) device tensors; rows
+    behind n[t] are zero.  F = 1 equals multiclass_nms(boxes[0], scores[0], score_thr, nms_iou_thr, max_num).
+    out = a result triple of these shapes to write into instead of allocating one.
+    phases: UNSTABLE measurement hook (tools/seqnms_bench.py), not for products: a mask of 1 link / 2 path / 4 merge -- only those
+    kernels run, on the workspace an earlier call with the SAME arguments on this stream filled; any other seq_nms call on the
+    stream in between overwrites that workspace and the result is then undefined."""
+    code = _seq_rescore(rescore)
+    _need_cuda(boxes, scores)
+    if scores.dim() != 3 or boxes.dim() != 3 or tuple(boxes.shape) != (scores.shape[0], scores.shape[1], 4):
+        raise ValueError('seq_nms takes boxes [F,R,4] and scores [F,R,ncls], got %s and %s' % (tuple(boxes.shape), tuple(scores.shape)))
+    F, R, ncls = scores.shape
+    alloc = torch.empty if R > 0 else torch.zeros
+    dets, labels, n_out = out if out is not None else (alloc((F, max_num, 5), dtype=torch.float32, device=boxes.device),
+                                                       alloc((F, max_num), dtype=torch.long, device=boxes.device),
+                                                       alloc(F, dtype=torch.int32, device=boxes.device))
+    ws = _workspace(lib().hvr_seq_nms_workspace_bytes(F, R, ncls), boxes.device, 'seqnms')
+    args = (_ptr(boxes.contiguous().float()), _ptr(scores.contiguous().float()), F, R, ncls, float(score_thr), float(link_iou_thr),
+            float(nms_iou_thr), code, int(max_num), _ptr(dets), _ptr(labels), _ptr(n_out), _ptr(ws), ws.numel())
+    if phases is None:
+        _check(lib().hvr_seq_nms(*args, _stream()), 'hvr_seq_nms')
+    else:
+        _check(lib().hvr_seq_nms_phases(*args, int(phases), _stream()), 'hvr_seq_nms_phases')
+    return dets, labels, n_out
 
 
 def readout_nms(boxes, scores, score_thr, nms_cfg, max_num):

@@ -29,11 +29,28 @@ class VideoWindowRunner(object):
     the frame arrives (`model.frame_tensors`) and a window runs only the relation stages and the read-out on the
     T cached entries (`model.forward_feat_frames`); same detections, about a third of the work per output frame.
     Test-time augmentation (cache_frames=False only): `img` a list of A tensors and `img_meta` a list of A metas per frame
-    (`pipelines.FrameIngestAug`); the nested metas send every emitted window through `model.forward_feat_aug`."""
+    (`pipelines.FrameIngestAug`); the nested metas send every emitted window through `model.forward_feat_aug`.
+    seq_nms = dict(link_iou_thr=0.5, rescore='avg') (default: test_cfg.rcnn's `seq_nms` key, None = off): every window is read out
+    raw (`forward_feat(..., raw=True)`: decoded boxes and scores, no per-frame NMS) and `run_video` hands the key frames of the whole
+    video, in frame order, to `model.seq_nms_video` once -- Seq-NMS replaces the per-frame NMS; same result structure.  Not
+    combined with nms type 'soft_nms' (ValueError) or test-time augmentation (NotImplementedError)."""
 
-    def __init__(self, model, window, rescale=True, cache_frames=False):
+    def __init__(self, model, window, rescale=True, cache_frames=False, seq_nms=None):
         assert window % 2 == 1, 'window = 2 * frame_interval + 1'
         self.model, self.T, self.rescale, self.cache_frames = model, window, rescale, cache_frames
+        rcnn = getattr(getattr(model, 'test_cfg', None), 'rcnn', None)
+        if seq_nms is None and rcnn is not None:
+            seq_nms = rcnn.get('seq_nms')
+        self.seq_nms = dict(seq_nms) if seq_nms is not None else None   # ({} = Seq-NMS with its defaults)
+        if self.seq_nms is not None:
+            unknown = set(self.seq_nms) - {'link_iou_thr', 'rescore'}
+            if unknown:
+                raise ValueError('seq_nms takes link_iou_thr and rescore, got %s' % sorted(unknown))
+            if self.seq_nms.get('rescore', 'avg') not in ('avg', 'max'):
+                raise ValueError('Invalid rescore for Seq-NMS: {} (avg, max)'.format(self.seq_nms['rescore']))
+            if rcnn is not None:
+                from .detectors import check_seq_nms_cfg
+                check_seq_nms_cfg(rcnn)
         self.center = (window - 1) // 2
         self._reset()
 
@@ -52,17 +69,20 @@ class VideoWindowRunner(object):
         self.entries.append(self._entry)  # the arriving frame's cached per-frame tensors (None without cache_frames)
 
     def _emit(self):
+        raw = dict(raw=True) if self.seq_nms is not None else {}   # (without seq_nms the calls are what they always were)
         if self.cache_frames:
-            result = self.model.forward_feat_frames(list(self.entries), c4s=list(self.feats), rescale=self.rescale)
+            result = self.model.forward_feat_frames(list(self.entries), c4s=list(self.feats), rescale=self.rescale, **raw)
         else:
             result = self.model(x=self.feats, img=None, img_meta=list(self.metas), forward_feat=True, return_loss=False,
-                                rescale=self.rescale)
+                                rescale=self.rescale, **raw)
         return self.offsets[self.center], result
 
     def step(self, img, img_meta, flag, frame_offset, seg_len=None):
         """One loader iteration; returns the list of (frame_offset, result) emitted by it."""
         out = []
         if isinstance(img, (list, tuple)):   # MultiScaleFlipAug form: img = A tensors, img_meta = A metas -> the deque holds A C4 maps per frame
+            if self.seq_nms is not None:
+                raise NotImplementedError('Seq-NMS over test-time-augmentation windows is not implemented')
             if self.cache_frames:
                 raise NotImplementedError('the per-frame cache does not cover test-time augmentation (cache_frames=False does)')
             feat = [f[0] for f in self.model(img=list(img), img_meta=list(img_meta), backbone_feat=True)]
@@ -100,6 +120,9 @@ class VideoWindowRunner(object):
         if len(frames) == 1:  # a one-frame segment is both first and last
             for off, res in self.step(frames[0], metas[0], LAST, 0, seg_len=1):
                 results[off] = res
+        if self.seq_nms is not None and results:   # results holds the raw read-outs: one Seq-NMS over the video's key frames
+            offs = sorted(results)
+            return dict(zip(offs, self.model.seq_nms_video([results[o] for o in offs], **self.seq_nms)))
         return results
 
 

@@ -422,6 +422,35 @@ int hvr_multiclass_soft_nms(const float* boxes, const float* scores, int P, int 
                             float sigma, float min_score, int max_num, float* dets, int64_t* labels, int32_t* n_out, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Seq-NMS read-out of ONE whole video (Han et al. 2016; the reference tree has none: DESIGN.md holds the specification and
+ * tests/seqnms_refs.py its host restatement).  boxes [F][R][4] (x1,y1,x2,y2, +1 pixel convention, class-agnostic), scores
+ * [F][R][ncls] (column 0 = background), the F key frames in time order; padding rows carry score 0 in every column.
+ * Per foreground class: candidates = rows with score > score_thr; (t,i) links to (t+1,j) iff IoU >= link_thr; repeat until no
+ * candidate is alive { best[t,i] = s[t,i] + max over alive linked j of best[t+1,j] (0 if none), backward in time; root = alive
+ * box with the largest best (lowest t, then lowest i); the path follows the lowest j attaining the max; every path box gets the
+ * score best[root] / n (rescore 1 = avg) or the path's largest score (rescore 2 = max), is kept and retired, and so is -- but
+ * dropped -- every alive box of its frame with IoU >= nms_thr to it }.  IoU = the f32 arithmetic of nms_cpu.cpp.
+ * Output per frame as hvr_multiclass_nms: kept rows class-major, ascending row, with the rescored scores; cut to the max_num
+ * highest (descending, list position ascending on ties) if more are kept; dets [F][max_num][5], labels [F][max_num] int64
+ * (0-based), n_out [F] int32, rows behind n_out[t] zeroed.  F = 1 equals hvr_multiclass_nms(score_thr, nms_thr) row for row.
+ * F >= 1, score_thr >= 0, max_num > 0 (else HVR_EINVAL); R <= 512, F <= 65535, at most 128 foreground classes and
+ * (ncls - 1) * R <= 16384 -- the merge keeps a frame's whole candidate list, next_pow2((ncls - 1) * R) entries of 8 bytes, in
+ * LDS; 30 classes x 512 rows fit, 128 x 512 do not -- (else HVR_EUNSUPPORTED); nothing is launched on an error.  R == 0 writes only the counts (zero).  Three launches on `stream`, no
+ * host read: capturable.
+ *   hvr_seq_nms_phases: UNSTABLE measurement hook, not part of the supported interface (it may change or go without an ABI
+ *                       bump): the same call restricted to the kernels named in `phases` (1 link / overlap bits, 2 per-class
+ *                       paths, 4 per-frame merge; 7 = hvr_seq_nms), for timing a kernel alone (tools/seqnms_bench.py).  Phases 2
+ *                       and 4 read what the earlier phases of the SAME arguments left in `ws`: if anything else wrote that
+ *                       workspace in between, the result is undefined (no check is possible).  Products call hvr_seq_nms.
+ * ---------------------------------------------------------------------------------- */
+size_t hvr_seq_nms_workspace_bytes(int F, int R, int ncls);
+int hvr_seq_nms(const float* boxes, const float* scores, int F, int R, int ncls, float score_thr, float link_thr, float nms_thr,
+                int rescore, int max_num, float* dets, int64_t* labels, int32_t* n_out, void* ws, size_t ws_bytes, void* stream);
+int hvr_seq_nms_phases(const float* boxes, const float* scores, int F, int R, int ncls, float score_thr, float link_thr, float nms_thr,
+                       int rescore, int max_num, float* dets, int64_t* labels, int32_t* n_out, void* ws, size_t ws_bytes, int phases,
+                       void* stream);
+
 /* ---- layout / dtype plumbing at the API boundary ---- */
 /* any pair of the four dtypes; pairs other than f32 <-> bf16 move 8 elements per thread: n % 8 == 0 and 16-byte aligned buffers
  * (split half: n % 32 == 0 -- a contiguous tensor whose last dimension is a multiple of 32 -- and 128-byte alignment) */
