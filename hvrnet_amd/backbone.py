@@ -174,25 +174,27 @@ class Bottleneck(nn.Module, PackedMixin):
                          (p['c3'][1] + p['ds'][1]).contiguous())
         return p
 
-    def forward_nhwc(self, x, out=None, h1=None, nxt=None):
+    def forward_nhwc(self, x, out=None, h1=None, nxt=None, compact_in=False):
         """out: where the block's output goes (a contiguous [B,OH,OW,4*planes] tensor), e.g. a frame group's slice of a map.
         h1: this block's conv1 output, when the previous block's tail already computed it.  nxt: the block that consumes
         this one's output; the return value is then (y, h1 of nxt or None) -- nxt's conv1 rides on this block's tail when
-        hvr_bottleneck_tail_next has a kernel for the shapes."""
+        hvr_bottleneck_tail_next has a kernel for the shapes.  compact_in (a caffe-style stride-2 block only): x already holds
+        only the pixels this block's strided 1x1 convs read (forward_sampled_nhwc of the block before), so they run at stride 1."""
         p = self.packed(x.device)
         dst = out
-        out = h1 if h1 is not None else native.conv2d_nhwc(x, p['c1'][0], p['c1'][1], relu=True, stride=self.conv1_stride)
+        stride, conv1_stride = (1, 1) if compact_in else (self.stride, self.conv1_stride)
+        out = h1 if h1 is not None else native.conv2d_nhwc(x, p['c1'][0], p['c1'][1], relu=True, stride=conv1_stride)
         out = native.conv2d_nhwc(out, p['c2'][0], p['c2'][1], relu=True, stride=self.conv2_stride, pad=self.dilation,
                                  dil=self.dilation)
         if nxt is not None and self.fuse_next and nxt.conv1_stride == 1:
             pn = nxt.packed(x.device)
             wn, bn = pn['c1'][0].reshape(pn['c1'][0].shape[0], -1), pn['c1'][1]
             if self.downsample is not None:
-                args = (out, x, None, p['tail'][0], p['tail'][1], self.stride) if self.fuse_tail else None
+                args = (out, x, None, p['tail'][0], p['tail'][1], stride) if self.fuse_tail else None
                 if x.dtype == native.SPLIT:
                     # split half has no second-K-segment tail: the projection is its own conv and enters the fused closing 1x1 +
                     # next conv1 as the residual (the identity form of hvr_bottleneck_tail_next)
-                    ident = native.conv2d_nhwc(x, p['ds'][0], p['ds'][1], relu=False, stride=self.stride)
+                    ident = native.conv2d_nhwc(x, p['ds'][0], p['ds'][1], relu=False, stride=stride)
                     w3, b3 = p['c3'][0].reshape(p['c3'][0].shape[0], -1), p['c3'][1]
                     if native.bottleneck_tail_next_supported(out, None, ident, w3, b3, 1, wn, bn):
                         return native.bottleneck_tail_next(out, None, ident, w3, b3, wn, bn, out=dst)
@@ -202,17 +204,36 @@ class Bottleneck(nn.Module, PackedMixin):
                 args = (out, None, x, p['c3'][0].reshape(p['c3'][0].shape[0], -1), p['c3'][1], 1)
             if args is not None and native.bottleneck_tail_next_supported(*args, wn, bn):
                 return native.bottleneck_tail_next(args[0], args[1], args[2], args[3], args[4], wn, bn, stride2=args[5], out=dst)
-        y = self._tail(x, out, p, dst)
+        y = self._tail(x, out, p, dst, stride)
         return y if nxt is None else (y, None)
 
-    def _tail(self, x, out, p, dst):
+    def _tail(self, x, out, p, dst, stride):
         identity = x
         if self.downsample is not None:
-            if self.fuse_tail and native.bottleneck_tail_supported(out, x, p['tail'][0], p['tail'][1], self.stride):
+            if self.fuse_tail and native.bottleneck_tail_supported(out, x, p['tail'][0], p['tail'][1], stride):
                 # relu(conv3(out) + downsample(x)) in one pass: the identity map is never written (resnet.py:248-264)
-                return native.bottleneck_tail(out, x, p['tail'][0], p['tail'][1], stride2=self.stride, relu=True, out=dst)
-            identity = native.conv2d_nhwc(x, p['ds'][0], p['ds'][1], relu=False, stride=self.stride)
+                return native.bottleneck_tail(out, x, p['tail'][0], p['tail'][1], stride2=stride, relu=True, out=dst)
+            identity = native.conv2d_nhwc(x, p['ds'][0], p['ds'][1], relu=False, stride=stride)
         return native.conv2d_nhwc(out, p['c3'][0], p['c3'][1], resid=identity, relu=True, out=dst)
+
+    def forward_sampled_nhwc(self, x, h1=None, stride=2):
+        """An identity block whose output only a stride-`stride` 1x1 consumer reads (the last block of a stage in front of a
+        caffe-style stage, resnet.py:127-132): conv1 everywhere (the 3x3 reads neighbours), conv2 as a stride-`stride` 3x3, and the
+        closing 1x1 on those pixels with the residual sampled from x (hvr_bottleneck_close_sampled).  -> (y, True) with
+        y [B,(H-1)//stride+1,(W-1)//stride+1,4*planes] = the full-resolution output at [:, ::stride, ::stride] bit for bit, or
+        (the full-resolution output, False) where the sampled close has no kernel for the dtype / shape."""
+        assert self.downsample is None and self.stride == 1
+        p = self.packed(x.device)
+        h = h1 if h1 is not None else native.conv2d_nhwc(x, p['c1'][0], p['c1'][1], relu=True, stride=1)
+        B, H, W, _ = x.shape
+        hs = torch.empty((B, (H - 1) // stride + 1, (W - 1) // stride + 1, self.planes), dtype=x.dtype, device=x.device)
+        w3, b3 = p['c3'][0].reshape(p['c3'][0].shape[0], -1), p['c3'][1]
+        # (the sampled close is the row-panel kernel: the same sums as the full-resolution close only where that one takes it too)
+        full_path = native.conv2d_path(B, H, W, self.planes, 4 * self.planes, dtype=x.dtype, tile=native.TILE_HINT)
+        if full_path != 1 or not native.bottleneck_close_sampled_supported(hs, w3, b3, x, stride):
+            return self.forward_nhwc(x, h1=h), False
+        native.conv2d_nhwc(h, p['c2'][0], p['c2'][1], relu=True, stride=stride, pad=self.dilation, dil=self.dilation, out=hs)
+        return native.bottleneck_close_sampled(hs, w3, b3, x, stride=stride, relu=True), True
 
     fuse_next = True   # class attributes (tests flip them to compare the fused kernels with the per-conv path); no environment switch
     fuse_tail = True
@@ -331,6 +352,26 @@ class ResNet(nn.Module, PackedMixin):
             h, w = (h - 1) // self.strides[i] + 1, (w - 1) // self.strides[i] + 1
         return (B, h, w, 64 * 2 ** last * 4)
 
+    skip_dead_pixels = True   # class attribute (tests flip it to compare with the full-resolution path); no environment switch
+    # Stages that may end compact.  Layer 2 (index 1) qualifies too and is bit-identical as well (tests/test_dead_pixels_gpu.py), but its
+    # closing conv is then the last row-panel conv to leave hvr_conv2d_nhwc in a bf16 window, and the forward-kernel census
+    # (tests/test_forward_kernels_gpu.py) wants that route among the calls it checks against f64: layer 2 stays full by default
+    compact_stages = (0,)
+
+    def _ends_compact(self, i):
+        """True when nothing reads stage i's output but the stride-2 1x1 convs (conv1 and downsample) of a caffe-style stage i + 1
+        (resnet.py:127-132,283-296): three quarters of its pixels are dead, and its last block computes the live quarter only
+        (Bottleneck.forward_sampled_nhwc).  Few-row split-K (native.fewrow_split) picks its K slices by the row count, so the
+        compact 3x3 would sum in another order than the full one: full resolution there."""
+        if not self.skip_dead_pixels or i not in self.compact_stages or i + 1 >= len(self.res_layers) or i in self.out_indices or native.fewrow_enabled():
+            return False
+        blocks, nxt = getattr(self, self.res_layers[i]), getattr(self, self.res_layers[i + 1])[0]
+        last, ds = blocks[-1], nxt.downsample
+        if len(blocks) < 2 or last.downsample is not None or last.stride != 1:
+            return False
+        return (nxt.style == 'caffe' and nxt.conv1_stride == 2 and nxt.conv2_stride == 1 and nxt.conv1.kernel_size == (1, 1)
+                and ds is not None and ds[0].kernel_size == (1, 1) and ds[0].stride == (2, 2))
+
     def forward(self, x, out=None):
         """x [B,3,H,W] f32 -> tuple of logical-NCHW feature maps (resnet.py:522-533).  out: a contiguous NHWC tensor of
         out_shape_nhwc(...) in the compute dtype that receives the (single) returned map, e.g. a slice of a larger batch."""
@@ -349,17 +390,21 @@ class ResNet(nn.Module, PackedMixin):
                 y = native.gemm(cols, p['stem'][0], p['stem'][1], relu=True).view(x.shape[0], OH, OW, 64)
                 y = native.maxpool3x3s2_nhwc(y)
         outs = []
+        compact = False
         if out is not None:
             assert len(self.out_indices) == 1, 'out= needs a single returned map'
         for i, name in enumerate(self.res_layers):
             blocks = list(getattr(self, name))
             h1 = None
+            compact_in, compact = compact, False   # y holds every second pixel of every second row of the previous stage's output
             for j, blk in enumerate(blocks):
                 last = out is not None and i == self.out_indices[0] and j == len(blocks) - 1
                 if j + 1 < len(blocks):  # the next block's conv1 rides on this block's tail where a kernel exists
-                    y, h1 = blk.forward_nhwc(y, h1=h1, nxt=blocks[j + 1])
+                    y, h1 = blk.forward_nhwc(y, h1=h1, nxt=blocks[j + 1], compact_in=compact_in and j == 0)
+                elif self._ends_compact(i):
+                    y, compact = blk.forward_sampled_nhwc(y, h1=h1)
                 else:
-                    y = blk.forward_nhwc(y, out=out if last else None, h1=h1)
+                    y = blk.forward_nhwc(y, out=out if last else None, h1=h1, compact_in=compact_in and j == 0)
             if i in self.out_indices:
                 outs.append(as_logical(y))
             if out is not None and i == self.out_indices[0]:

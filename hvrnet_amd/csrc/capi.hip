@@ -336,6 +336,11 @@ int hvr_gemm_splitk_batched(const hvr_gemm_desc* d, int count, int64_t stride_a,
   return check_launch(e, "hvr_gemm_splitk_batched");
 }
 
+static int expand_enabled() {   // HVR_EXPAND=0: the automatic choice of the row-panel kernels is off
+  static const int on = std::getenv("HVR_EXPAND") ? std::atoi(std::getenv("HVR_EXPAND")) : 1;
+  return on;
+}
+
 // descriptor -> kernel parameters + the path it takes (0 tile engine, 1 expand.hip); a negative return is the error
 static int conv_params(const hvr_conv_desc* d, GemmParams& p, int& path) {
   if (!d) return fail(HVR_EINVAL, "null descriptor");
@@ -365,7 +370,7 @@ static int conv_params(const hvr_conv_desc* d, GemmParams& p, int& path) {
   p.alpha = d->alpha; p.beta = d->beta;
   if (pointwise) p.zero = d->zero;  // (expand.hip reads it in place of a missing shift)
   // the expand convs of a Bottleneck (1x1, K <= 256, + residual) are HBM-bound: row-panel kernel (expand.hip)
-  static const int use_expand = std::getenv("HVR_EXPAND") ? std::atoi(std::getenv("HVR_EXPAND")) : 1;
+  const int use_expand = expand_enabled();
   if (p.tile_hint == kBigForce) {
     path = 0;
     return 0;
@@ -513,6 +518,45 @@ int hvr_bottleneck_tail_next(const hvr_tail_next_desc* d, void* stream) {
   if (!expand_next_supported(p))
     return fail(HVR_EUNSUPPORTED, "no fused tail + next conv kernel for C1=%d C2=%d Cout=%d Cn=%d", d->tail.C1, d->tail.C2, d->tail.Cout, d->Cn);
   return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_tail_next");
+}
+
+// closing 1x1 of a stage's last block on the pixels the next stage's stride-2 1x1 convs read: compact h and y, the residual sampled from the
+// block's full-resolution input (expand.hip / expand_split.hip, GemmParams::rs)
+static int close_sampled_params(const hvr_close_sampled_desc* d, GemmParams& p) {
+  if (!d) return fail(HVR_EINVAL, "null descriptor");
+  if (!valid_dtype(d->dtype)) return fail(HVR_EINVAL, "bad dtype %d", d->dtype);
+  if (d->B <= 0 || d->OH <= 0 || d->OW <= 0 || d->rstride <= 0 || d->RH <= 0 || d->RW <= 0) return fail(HVR_EINVAL, "empty sampled-close problem");
+  if ((long)(d->OH - 1) * d->rstride >= d->RH || (long)(d->OW - 1) * d->rstride >= d->RW) return fail(HVR_EINVAL, "the sampled pixels fall outside resid");
+  const long M = (long)d->B * d->OH * d->OW;
+  if (M > 0x7fffffffL || (long)d->B * d->RH * d->RW > 0x7fffffffL) return fail(HVR_EUNSUPPORTED, "too many pixels");
+  const int rc = fill_linear(p, d->h, d->w, d->y, (int)M, d->Cout, d->C1, d->C1, d->C1, d->Cout, d->dtype, 1);
+  if (rc) return rc;
+  const bool split = d->dtype == HVR_F16S;
+  if (!d->resid || !(split ? aligned128(d->resid) : aligned16(d->resid)))
+    return fail(HVR_EINVAL, "resid must be a 16-byte aligned (split half: 128-byte aligned) device pointer");
+  if (split && (d->Cout % 32 || !aligned128(d->y))) return fail(HVR_EINVAL, "split-half sampled close: Cout %% 32 == 0, 128-byte aligned y");
+  p.bias = d->bias; p.relu = d->relu; p.resid = d->resid; p.ldr = d->Cout;
+  p.rs = d->rstride; p.RH = d->RH; p.RW = d->RW; p.OH = d->OH; p.OW = d->OW;
+  if (split) { p.alpha = d->alpha; p.beta = d->beta; }
+  return 0;
+}
+
+int hvr_bottleneck_close_sampled_supported(const hvr_close_sampled_desc* d) {
+  GemmParams p;
+  if (close_sampled_params(d, p)) return 0;
+  // the row-panel kernels only, and only where hvr_conv2d_nhwc takes them for the same product at full resolution (same sums, bit for bit)
+  return (expand_enabled() && p.N >= 2 * p.K && (expand_supported(p) || expand_split_supported(p))) ? 1 : 0;
+}
+
+int hvr_bottleneck_close_sampled(const hvr_close_sampled_desc* d, void* stream) {
+  GemmParams p;
+  const int rc = close_sampled_params(d, p);
+  if (rc) return rc;
+  if (expand_enabled() && p.N >= 2 * p.K) {
+    if (expand_split_supported(p)) return check_launch(run_expand_split(p, (hipStream_t)stream), "hvr_bottleneck_close_sampled(split half)");
+    if (expand_supported(p)) return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_close_sampled");
+  }
+  return fail(HVR_EUNSUPPORTED, "no sampled-residual closing kernel for C1=%d Cout=%d dtype=%d (%d output pixels)", d->C1, d->Cout, d->dtype, p.M);
 }
 
 int hvr_conv2d_path(const hvr_conv_desc* d) {

@@ -132,11 +132,17 @@ __global__ __launch_bounds__(64 * (X_BM / 16 / RF), RF == 2 ? 2 : 1) void expand
 
   // ---- X fragments: rows m0 + 16 i + q, k = 32 kf + 8 g .. + 8 ----
   xu32x4 x[RF][KF];
-  int mrow[RF];
+  int mrow[RF], rrow[RF];
 #pragma unroll
   for (int i = 0; i < RF; ++i) {
     const int m = m0 + i * 16 + q;
     mrow[i] = m < p.M ? m : p.M - 1;
+    // residual row (p.rs > 0: the row's pixel of the full-resolution residual map, sampled at stride rs)
+    rrow[i] = mrow[i];
+    if (p.rs > 0) {
+      const int ox = mrow[i] % p.OW, t = mrow[i] / p.OW, oy = t % p.OH, b = t / p.OH;
+      rrow[i] = (b * p.RH + oy * p.rs) * p.RW + ox * p.rs;
+    }
     const char* xr = (const char*)p.A + (long)mrow[i] * p.lda * 2 + g * 16;
     // second K segment (p.s2 > 0: the block's projection shortcut): the row's pixel of the block INPUT, sampled at stride s2
     const char* x2r = xr;
@@ -162,7 +168,7 @@ __global__ __launch_bounds__(64 * (X_BM / 16 / RF), RF == 2 ? 2 : 1) void expand
 #endif
 #pragma unroll
       for (int i = 0; i < RF; ++i) {
-        const char* rr = (const char*)p.resid + ((long)mrow[i] * p.ldr + c * BN + g * 4 * FJ) * 2;
+        const char* rr = (const char*)p.resid + ((long)rrow[i] * p.ldr + c * BN + g * 4 * FJ) * 2;
 #pragma unroll
         for (int v = 0; v < NV; ++v) r[i][v] = *reinterpret_cast<const xu32x4*>(rr + v * 16);
       }
@@ -375,6 +381,9 @@ bool expand_supported(const GemmParams& p) {
   if ((p.dtype != DT_BF16 && p.dtype != DT_F16) || p.conv || p.out_f32 || p.ksplit_steps > 0) return false;
   if (!(p.K == 64 || p.K == 128 || p.K == 256 || p.K == 512 || (p.K == 384 && p.s2 > 0))) return false;
   if (p.s2 > 0 && (p.K1 % 32 || p.K1 <= 0 || p.K1 >= p.K || (p.K - p.K1) % 8 || (reinterpret_cast<uintptr_t>(p.A2) & 15) || p.resid)) return false;
+  // sampled residual: every sampled pixel lies inside the residual map, whose rows are counted in 32 bits
+  if (p.rs < 0 || (p.rs > 0 && (!p.resid || p.OH <= 0 || p.OW <= 0 || p.M % (p.OH * p.OW) || (long)(p.OH - 1) * p.rs >= p.RH ||
+                                (long)(p.OW - 1) * p.rs >= p.RW || (long)(p.M / (p.OH * p.OW)) * p.RH * p.RW > 0x7fffffffL))) return false;
   if (p.N % X_BN || p.M < X_BM || expand_nc(p.M, p.N) == 0) return false;
   if (p.lda % 8 || p.ldb % 8 || p.ldc % 8 || (p.resid && p.ldr % 8)) return false;
   const uintptr_t al = reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.B) | reinterpret_cast<uintptr_t>(p.C) |

@@ -115,11 +115,17 @@ __global__ __launch_bounds__(XS_NT, 2) void expand_split_kernel(const GemmParams
 
   // ---- X fragments, both planes: rows m0 + 16 i + q, k = 32 kf + 8 g .. + 8 ----
   xsu32x4 xh[RF][KF], xl[RF][KF];
-  int mrow[RF];
+  int mrow[RF], rrow[RF];
 #pragma unroll
   for (int i = 0; i < RF; ++i) {
     const int m = m0 + i * 16 + q;
     mrow[i] = m < p.M ? m : p.M - 1;
+    // residual row (p.rs > 0: the row's pixel of the full-resolution residual map, sampled at stride rs -- expand.hip)
+    rrow[i] = mrow[i];
+    if (p.rs > 0) {
+      const int ox = mrow[i] % p.OW, t = mrow[i] / p.OW, oy = t % p.OH, b = t / p.OH;
+      rrow[i] = (b * p.RH + oy * p.rs) * p.RW + ox * p.rs;
+    }
     const char* xr = (const char*)p.A + (long)mrow[i] * p.lda * 4 + g * 16;
 #pragma unroll
     for (int kf = 0; kf < KF; ++kf) {
@@ -135,7 +141,7 @@ __global__ __launch_bounds__(XS_NT, 2) void expand_split_kernel(const GemmParams
     if constexpr (RES) {
 #pragma unroll
       for (int i = 0; i < RF; ++i) {
-        const char* rr = (const char*)p.resid + (long)mrow[i] * p.ldr * 4 + c * 256 + lane_col;
+        const char* rr = (const char*)p.resid + (long)rrow[i] * p.ldr * 4 + c * 256 + lane_col;
         r[i][0] = *reinterpret_cast<const xsu32x4*>(rr);
         r[i][1] = *reinterpret_cast<const xsu32x4*>(rr + 16);
         r[i][2] = *reinterpret_cast<const xsu32x4*>(rr + kSplitPlane);
@@ -317,6 +323,8 @@ static int expand_split_nc(int M, int N) {
 bool expand_split_supported(const GemmParams& p) {
   if (p.dtype != DT_F16S || p.conv || p.out_f32 || p.ksplit_steps > 0 || p.s2 > 0) return false;
   if (!(p.K == 64 || p.K == 128)) return false;
+  if (p.rs < 0 || (p.rs > 0 && (!p.resid || p.OH <= 0 || p.OW <= 0 || p.M % (p.OH * p.OW) || (long)(p.OH - 1) * p.rs >= p.RH ||
+                                (long)(p.OW - 1) * p.rs >= p.RW || (long)(p.M / (p.OH * p.OW)) * p.RH * p.RW > 0x7fffffffL))) return false;
   if (p.N % XS_BN || p.M < XS_BM || expand_split_nc(p.M, p.N) == 0) return false;
   if (p.lda % 32 || p.ldb % 32 || p.ldc % 32 || (p.resid && p.ldr % 32)) return false;
   const uintptr_t al = reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.B) | reinterpret_cast<uintptr_t>(p.C) |

@@ -50,6 +50,9 @@ struct GemmParams {
   // columns K1 .. K - 1 of a row come from A2, an NHWC map [.][H2][W2][K - K1] sampled at stride s2 (0 = no second segment)
   const void* A2;
   int K1, H2, W2, s2;
+  // sampled residual of the row-panel kernels (expand.hip / expand_split.hip, hvr_bottleneck_close_sampled): output row (b, oy, ox) of the
+  // compact [.][OH][OW] map adds pixel (oy rs, ox rs) of the full-resolution residual map [.][RH][RW][ldr]; 0 = the residual row is the output row
+  int rs, RH, RW;
   // the NEXT block's reducing 1x1 computed on the expand kernel's output while it is still in registers (expand.hip, NX > 0):
   // Hn [M][Cn] = relu(out Wn^T + bias_n), Wn [Cn][N] (K contiguous), Cn = 64 / 128; null = off
   const void* Wn;

@@ -75,6 +75,14 @@ class TailNextDesc(ctypes.Structure):
                 ('hn', ctypes.c_void_p), ('Cn', ctypes.c_int32), ('alpha', ctypes.c_float), ('beta', ctypes.c_float)]
 
 
+class CloseSampledDesc(ctypes.Structure):
+    _fields_ = [('h', ctypes.c_void_p), ('w', ctypes.c_void_p), ('resid', ctypes.c_void_p), ('y', ctypes.c_void_p),
+                ('B', ctypes.c_int32), ('OH', ctypes.c_int32), ('OW', ctypes.c_int32), ('C1', ctypes.c_int32),
+                ('Cout', ctypes.c_int32), ('RH', ctypes.c_int32), ('RW', ctypes.c_int32), ('rstride', ctypes.c_int32),
+                ('bias', ctypes.c_void_p), ('relu', ctypes.c_int32), ('dtype', ctypes.c_int32),
+                ('alpha', ctypes.c_float), ('beta', ctypes.c_float)]
+
+
 class RpnDesc(ctypes.Structure):
     _fields_ = [('cls', ctypes.c_void_p), ('reg', ctypes.c_void_p),
                 ('T', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32),
@@ -105,6 +113,8 @@ SYMBOLS = {
     'hvr_bottleneck_tail_supported': (_i, [ctypes.POINTER(TailDesc)]),
     'hvr_bottleneck_tail_next': (_i, [ctypes.POINTER(TailNextDesc), _vp]),
     'hvr_bottleneck_tail_next_supported': (_i, [ctypes.POINTER(TailNextDesc)]),
+    'hvr_bottleneck_close_sampled': (_i, [ctypes.POINTER(CloseSampledDesc), _vp]),
+    'hvr_bottleneck_close_sampled_supported': (_i, [ctypes.POINTER(CloseSampledDesc)]),
     'hvr_im2col_stem': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'hvr_maxpool3x3s2_nhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'hvr_stem_fused': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -546,6 +556,52 @@ def bottleneck_tail_next(h, x, resid, w, bias, wn, bias_n, stride2=1, out=None):
     return y, hn
 
 
+def _close_sampled_desc(h, w, bias, resid, stride, relu, y):
+    B, OH, OW, C1 = h.shape
+    _, RH, RW, Cout = resid.shape
+    d = CloseSampledDesc(h=h.data_ptr(), w=w.data_ptr(), resid=resid.data_ptr(), y=y.data_ptr() if y is not None else 1 << 20, B=B, OH=OH, OW=OW,
+                         C1=C1, Cout=Cout, RH=RH, RW=RW, rstride=int(stride), bias=bias.data_ptr(), relu=int(relu), dtype=_dt(h))
+    if h.dtype == SPLIT:
+        d.alpha, d.beta = _split_factors(False, None)
+    return d
+
+
+def bottleneck_close_sampled_supported(h, w, bias, resid, stride):
+    """True when hvr_bottleneck_close_sampled runs these shapes: bf16 / half / split half on the row-panel kernels, contiguous maps,
+    h [B,OH,OW,C1] compact, resid [B,RH,RW,Cout] at full resolution with (OH - 1) stride < RH and (OW - 1) stride < RW."""
+    if not (h.is_cuda and h.dtype in (torch.bfloat16, torch.float16, SPLIT) and resid.dtype == h.dtype and w.dtype == h.dtype
+            and h.is_contiguous() and resid.is_contiguous() and w.is_contiguous() and h.dim() == 4 and resid.dim() == 4):
+        return False
+    if h.shape[0] != resid.shape[0] or w.numel() != resid.shape[3] * h.shape[3] or w.shape[0] != resid.shape[3]:
+        return False
+    return bool(lib().hvr_bottleneck_close_sampled_supported(ctypes.byref(_close_sampled_desc(h, w, bias, resid, stride, True, None))))
+
+
+def bottleneck_close_sampled(h, w, bias, resid, stride=2, relu=True, out=None):
+    """y[b,oy,ox] = act(h[b,oy,ox] W3^T + bias + resid[b, oy stride, ox stride]): the closing 1x1 of a stage's last block on the pixels
+    the next stage's stride-2 1x1 convs read.  h [B,OH,OW,C1] (conv2 run at that stride), resid [B,RH,RW,Cout] the block's
+    full-resolution input, w [Cout,C1] (or [Cout,1,1,C1]), bias f32 [Cout] -> [B,OH,OW,Cout]; bit-identical to
+    conv2d_nhwc(h_full, w, bias, resid=resid, relu=relu)[:, ::stride, ::stride]."""
+    _need_cuda(h, w, bias, resid)
+    B, OH, OW, C1 = h.shape
+    _, RH, RW, Cout = resid.shape
+    assert h.is_contiguous() and resid.is_contiguous() and w.is_contiguous() and resid.dtype == h.dtype and w.dtype == h.dtype
+    assert w.shape[0] == Cout and w.numel() == Cout * C1 and resid.shape[0] == B, (tuple(w.shape), tuple(resid.shape))
+    if out is not None:
+        assert tuple(out.shape) == (B, OH, OW, Cout) and out.dtype == h.dtype and out.is_contiguous()
+        y = out
+    else:
+        y = torch.empty((B, OH, OW, Cout), dtype=h.dtype, device=h.device)
+    d = _close_sampled_desc(h, w, bias, resid, stride, relu, y)
+    # bytes it moves: h, the sampled residual rows and y once, W once
+    tag, work = 'conv_expand', float((B * OH * OW * (C1 + 2 * Cout) + Cout * C1) * h.element_size())
+    if _prof is not None and _prof['detail']:
+        tag = 'conv_expand sampled %dx%d<-%dx%d %d->%d k1+res s%d' % (OH, OW, RH, RW, C1, Cout, stride)
+    with _span(tag, work):
+        _check(lib().hvr_bottleneck_close_sampled(ctypes.byref(d), _stream()), 'hvr_bottleneck_close_sampled')
+    return y
+
+
 def conv2d_path(B, H, W, Cin, Cout, k=1, stride=1, pad=0, dil=1, dtype=torch.bfloat16, resid=True, bias=True, out_f32=False, tile=0):
     """Which kernel hvr_conv2d_nhwc would run for a conv of this shape (0 tile engine, 1 expand.hip panel kernel, < 0 rejected).
     Nothing is launched and no memory is touched: the descriptor carries placeholder (16-byte aligned) addresses."""
@@ -616,6 +672,11 @@ _ws_cache = {}
 # batch bit for bit, a property the cached / look-ahead loops are tested for.  graphs.GraphedStream turns it on for its
 # one-frame graphs (the stream loop's latency case); everything else runs the unsplit kernels.
 _fewrow = [False]
+
+
+def fewrow_enabled():
+    """True inside `fewrow_split(True)`: convs and products may then run K-sliced, in a summation order that depends on the row count."""
+    return _fewrow[0]
 
 
 @contextlib.contextmanager

@@ -203,6 +203,31 @@ typedef struct hvr_tail_next_desc {
 int hvr_bottleneck_tail_next(const hvr_tail_next_desc* d, void* stream);
 int hvr_bottleneck_tail_next_supported(const hvr_tail_next_desc* d);
 
+/* Closing 1x1 conv + residual + ReLU of an identity Bottleneck, computed only on the pixels a stride-s consumer reads (the last
+ * block of a stage whose successor is a caffe-style stage: its first block's conv1 and downsample are both 1x1 with stride 2,
+ * resnet.py:127-132,283-296, and read this block's output at pixels (s oy, s ox) only):
+ *     y[b][oy][ox][:] = relu( h[b][oy][ox][:] W3^T + bias + resid[b][oy s][ox s][:] )
+ * h [B][OH][OW][C1] and y [B][OH][OW][Cout] are COMPACT maps (h = the block's 3x3 conv run at stride s); resid [B][RH][RW][Cout]
+ * is the block's full-resolution input, of which every s-th pixel of every s-th row is read and nothing else;
+ * w [Cout][C1] with the BatchNorm scale folded in, bias f32 [Cout].  (OH - 1) s < RH and (OW - 1) s < RW.
+ * Row-panel kernels only (csrc/expand.hip, csrc/expand_split.hip): HVR_BF16 / HVR_F16 / HVR_F16S, C1 = 64 or 128 (bf16 / half: also
+ * 256, 512), Cout >= 2 C1 in an even number of 64-channel chunks, at least 128 output pixels.  Every output element is the sum
+ * the row-panel kernel forms for the same pixel of the full-resolution product, in the same order (a panel kernel's K order does
+ * not depend on M): where hvr_conv2d_nhwc takes that kernel for the full map (hvr_conv2d_path 1: C1 = 64 / 128, the closing
+ * convs of layers 1 and 2) the result is bit-identical to computing the whole map and sampling it.  alpha / beta: HVR_F16S only,
+ * as in hvr_gemm_desc (0 = 1).
+ * hvr_bottleneck_close_sampled_supported: 1 when this descriptor runs, 0 otherwise (exact f32, fewer than 128 output pixels, other
+ * channel counts: the caller then computes the block at full resolution through hvr_conv2d_nhwc). */
+typedef struct hvr_close_sampled_desc {
+  const void* h; const void* w; const void* resid; void* y;
+  int32_t B, OH, OW, C1, Cout, RH, RW, rstride;
+  const float* bias;
+  int32_t relu, dtype;
+  float alpha, beta;
+} hvr_close_sampled_desc;
+int hvr_bottleneck_close_sampled(const hvr_close_sampled_desc* d, void* stream);
+int hvr_bottleneck_close_sampled_supported(const hvr_close_sampled_desc* d);
+
 /* 7x7/2 stem: gathers img (NCHW f32, the reference's input layout, resnet.py:522-524) into
  * patch rows [B*OH*OW][KP] with k = (ky*7+kx)*3 + c and zeros for k >= 147 (KP = 192). */
 int hvr_im2col_stem(const float* img, void* cols, int B, int H, int W, int KP, int dtype, void* stream);
