@@ -82,8 +82,9 @@ hipError_t run_soft_nms(const float*, int, float, int, float, float, float*, lon
 hipError_t run_multiclass_soft_nms(const float*, const float*, int, int, int, float, float, int, float, float, int, float*, long long*, int*,
                                    void*, hipStream_t);
 size_t multiclass_soft_nms_workspace_bytes(int P, int R, int ncls);
-hipError_t run_seq_nms(const float*, const float*, int, int, int, float, float, float, int, int, float*, long long*, int*, void*, int, hipStream_t);
-size_t seq_nms_workspace_bytes(int F, int R, int ncls);
+hipError_t run_seq_nms(const float*, const float*, int, const int*, int, int, int, float, float, float, int, int, float*, long long*, int*, int*,
+                       int*, float*, int*, int, void*, int, hipStream_t);
+size_t seq_nms_workspace_bytes(int P, int F, int R, int ncls, int tubes);
 hipError_t run_stem_fused(const float*, const void*, const float*, void*, int, int, int, int, hipStream_t);
 }  // namespace hvr
 
@@ -1441,7 +1442,11 @@ int hvr_multiclass_soft_nms(const float* boxes, const float* scores, int P, int 
 
 // ---- Seq-NMS read-out of a whole video (seqnms.hip) ----
 size_t hvr_seq_nms_workspace_bytes(int F, int R, int ncls) {
-  return seq_nms_workspace_bytes(F > 0 ? F : 1, R > 0 ? R : 1, ncls > 1 ? ncls : 2);
+  return seq_nms_workspace_bytes(1, F > 0 ? F : 1, R > 0 ? R : 1, ncls > 1 ? ncls : 2, 0);
+}
+
+size_t hvr_seq_nms_batched_workspace_bytes(int P, int Ftot, int R, int ncls, int tubes) {
+  return seq_nms_workspace_bytes(P > 0 ? P : 1, Ftot > 0 ? Ftot : 1, R > 0 ? R : 1, ncls > 1 ? ncls : 2, tubes != 0);
 }
 
 int hvr_seq_nms(const float* boxes, const float* scores, int F, int R, int ncls, float score_thr, float link_thr, float nms_thr,
@@ -1470,9 +1475,41 @@ int hvr_seq_nms_phases(const float* boxes, const float* scores, int F, int R, in
   if (!boxes || !scores || !dets || !labels || !ws) return fail(HVR_EINVAL, "null pointer");
   if (!aligned16(boxes) || !aligned16(ws)) return fail(HVR_EINVAL, "hvr_seq_nms: boxes and workspace must be 16-byte aligned");
   if (ws_bytes < hvr_seq_nms_workspace_bytes(F, R, ncls)) return fail(HVR_EWORKSPACE, "seq nms workspace too small");
-  return check_launch(run_seq_nms(boxes, scores, F, R, ncls, score_thr, link_thr, nms_thr, rescore == 2, max_num, dets, (long long*)labels,
-                                  n_out, ws, phases, (hipStream_t)stream),
+  return check_launch(run_seq_nms(boxes, scores, 1, nullptr, F, R, ncls, score_thr, link_thr, nms_thr, rescore == 2, max_num, dets,
+                                  (long long*)labels, n_out, nullptr, nullptr, nullptr, nullptr, 0, ws, phases, (hipStream_t)stream),
                       "hvr_seq_nms");
+}
+
+// P problems side by side and, optionally, the tube outputs: the same three kernels (hvr_seq_nms is their P = 1, no-tubes case)
+int hvr_seq_nms_batched(const float* boxes, const float* scores, int P, const int32_t* frame_start, int Ftot, int R, int ncls, float score_thr,
+                        float link_thr, float nms_thr, int rescore, int max_num, float* dets, int64_t* labels, int32_t* n_out,
+                        int32_t* tube_ids, int32_t* tubes, float* tube_scores, int32_t* tube_start, int max_tubes, void* ws, size_t ws_bytes,
+                        void* stream) {
+  const int want = (tube_ids != nullptr) + (tubes != nullptr) + (tube_scores != nullptr) + (tube_start != nullptr);
+  if (want != 0 && want != 4) return fail(HVR_EINVAL, "hvr_seq_nms_batched: the four tube outputs are all NULL or all non-NULL");
+  if (!n_out) return fail(HVR_EINVAL, "null n_out");
+  if (P < 1) return fail(HVR_EINVAL, "hvr_seq_nms_batched needs P >= 1 problems, got %d", P);
+  if (Ftot < P) return fail(HVR_EINVAL, "hvr_seq_nms_batched needs at least one frame per problem, got %d frames for %d problems", Ftot, P);
+  if (rescore != 1 && rescore != 2) return fail(HVR_EINVAL, "hvr_seq_nms_batched: rescore is 1 (avg) or 2 (max), got %d", rescore);
+  if (!(score_thr >= 0.f)) return fail(HVR_EINVAL, "hvr_seq_nms_batched needs score_thr >= 0 (path sums must be positive), got %g", (double)score_thr);
+  if (link_thr != link_thr || nms_thr != nms_thr) return fail(HVR_EINVAL, "hvr_seq_nms_batched: NaN threshold");
+  if (max_num <= 0) return fail(HVR_EINVAL, "hvr_seq_nms_batched needs max_num > 0");
+  if (want && max_tubes < 0) return fail(HVR_EINVAL, "hvr_seq_nms_batched needs max_tubes >= 0, got %d", max_tubes);
+  if (R < 0 || R > 512) return fail(HVR_EUNSUPPORTED, "hvr_seq_nms_batched supports R <= 512, got %d", R);
+  if (Ftot > 65535) return fail(HVR_EUNSUPPORTED, "hvr_seq_nms_batched supports at most 65535 frames per call, got %d", Ftot);
+  if (ncls < 2 || ncls - 1 > 128) return fail(HVR_EUNSUPPORTED, "hvr_seq_nms_batched supports 1 .. 128 foreground classes");
+  if (R == 0) {   // only the counts: no box, no tube
+    (void)run_zero_fill(n_out, sizeof(int32_t) * (size_t)Ftot, (hipStream_t)stream);
+    if (want) (void)run_zero_fill(tube_start, sizeof(int32_t) * ((size_t)P + 1), (hipStream_t)stream);
+    return HVR_OK;
+  }
+  if (!boxes || !scores || !frame_start || !dets || !labels || !ws) return fail(HVR_EINVAL, "null pointer");
+  if (!aligned16(boxes) || !aligned16(ws) || (want && !aligned16(tubes)))
+    return fail(HVR_EINVAL, "hvr_seq_nms_batched: boxes, workspace and the tube table must be 16-byte aligned");
+  if (ws_bytes < hvr_seq_nms_batched_workspace_bytes(P, Ftot, R, ncls, want != 0)) return fail(HVR_EWORKSPACE, "seq nms workspace too small");
+  return check_launch(run_seq_nms(boxes, scores, P, frame_start, Ftot, R, ncls, score_thr, link_thr, nms_thr, rescore == 2, max_num, dets,
+                                  (long long*)labels, n_out, tube_ids, tubes, tube_scores, tube_start, max_tubes, ws, 7, (hipStream_t)stream),
+                      "hvr_seq_nms_batched");
 }
 
 // ---- plumbing ----

@@ -22,6 +22,16 @@
 //   seq_nms_merge_kernel  one workgroup per frame: class-major list of the kept rows (ascending row) with the RESCORED scores, cut
 //                         to max_num with mc_cut_to_max_num, rows behind n_out[t] zeroed -- the contract of mc_nms_merge_kernel.
 //
+// Problems and tubes.  A call takes P >= 1 independent problems (one video's key frames for one read-out branch):
+// problem p owns the frames frame_start[p] .. frame_start[p + 1] - 1 of the stacked inputs.  Every table is indexed by the GLOBAL
+// frame, so the link kernel only has to know the last frame of each problem (no links out of it), the path kernel's grid is
+// (class, problem) with all pointers moved to the problem's first frame, and the merge is per frame as before.  frame_start is a
+// device array of the caller: every kernel clamps what it reads from it to 0 .. Ftot, so a wrong array cannot send a store outside
+// the tables.  hvr_seq_nms is the P = 1 case (frame_start = NULL: the one problem is 0 .. Ftot - 1).  With tube outputs the path
+// kernel also records, for every path box, the round that selected it (= the tube's index within its class and problem) and, at the
+// root, the path length; seq_nms_tube_prefix_kernel turns the per-(problem, class) round counts into id bases; the merge adds the
+// base to get the problem-local tube id of every output row and writes one table row per root box.
+//
 // `phases` of the launcher (1 link, 2 path, 4 merge; hvr_seq_nms runs all three) lets tools/seqnms_bench.py time a kernel alone on
 // the workspace the earlier ones filled.  No host read anywhere; the three launches go to the caller's stream with the caller's workspace.  Built with
 // -ffp-contract=off (w * h must not fuse into the union).  Plain C++: ballots, shuffles and vector stores only.
@@ -36,13 +46,32 @@ constexpr int SQ_MAX_W = SQ_MAX_R / 64;
 constexpr int SQ_MAX_F = 65535;     // frames are the link / merge grids' y / x; (frame, row) packs into 32 bits of the root key
 typedef unsigned long long sq_u64;
 
-__global__ __launch_bounds__(256) void seq_nms_link_kernel(const float4* __restrict__ boxes, int F, int R, int W, float link_thr,
-                                                           float nms_thr, sq_u64* __restrict__ link, sq_u64* __restrict__ ovl) {
+// the problem of global frame t: the largest p with frame_start[p] <= t (a bounded search, whatever the array holds) and its frame
+// range [f0, f1) clamped to 0 .. F.  frame_start == NULL: one problem, all F frames.
+__device__ __forceinline__ int sq_problem_of(const int* __restrict__ frame_start, int P, int F, int t, int& f0, int& f1) {
+  f0 = 0;
+  f1 = F;
+  if (!frame_start) return 0;
+  int lo = 0, hi = P - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (frame_start[mid] <= t) lo = mid; else hi = mid - 1;
+  }
+  f0 = min(max(frame_start[lo], 0), F);
+  f1 = min(max(frame_start[lo + 1], f0), F);
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void seq_nms_link_kernel(const float4* __restrict__ boxes, const int* __restrict__ frame_start, int P,
+                                                           int F, int R, int W, float link_thr, float nms_thr,
+                                                           sq_u64* __restrict__ link, sq_u64* __restrict__ ovl) {
   const int t = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + wave;
   if (i >= R) return;   // wave-uniform
   const float4 a = boxes[(long)t * R + i];
-  const bool has_next = t + 1 < F;
+  int f0, f1;
+  sq_problem_of(frame_start, P, F, t, f0, f1);
+  const bool has_next = t + 1 < f1;   // the last frame of a problem has no links (f1 <= F: the next frame's loads stay inside)
   sq_u64 lw = 0ull, ow = 0ull;   // lane k ends up with word k
   for (int k = 0; k < W; ++k) {
     const int j = k * 64 + lane;
@@ -70,25 +99,39 @@ __device__ __forceinline__ sq_u64 sq_wave_max(sq_u64 v) {
   return v;
 }
 
-// blockDim.x = 64 * W; scores: s[t, i] of class blockIdx.x at scores[((long)t * R + i) * ncls + 1 + blockIdx.x]
-__global__ __launch_bounds__(SQ_MAX_R) void seq_nms_path_kernel(const float* __restrict__ scores, int F, int R, int W, int ncls,
-                                                                float score_thr, int rescore_max, const sq_u64* __restrict__ link,
-                                                                const sq_u64* __restrict__ ovl, float* __restrict__ best_g,
-                                                                short* __restrict__ next_g, float* __restrict__ osc_g,
-                                                                sq_u64* __restrict__ alive_g, sq_u64* __restrict__ keep_g,
-                                                                sq_u64* __restrict__ wmax_g) {
+// grid (class, problem), blockDim.x = 64 * W; scores: s[t, i] of class blockIdx.x at scores[((long)t * R + i) * ncls + 1 + blockIdx.x].
+// Below, F and every frame index are the PROBLEM's: all pointers are moved to its first frame f0 of the Ftot stacked ones.
+// tube_g (NULL = no tube outputs): per path box (round that selected it, path length at the root / 0 elsewhere); tcount: the
+// rounds of this (problem, class).
+__global__ __launch_bounds__(SQ_MAX_R) void seq_nms_path_kernel(const float* __restrict__ scores, const int* __restrict__ frame_start,
+                                                                int Ftot, int R, int W, int ncls, float score_thr, int rescore_max,
+                                                                const sq_u64* __restrict__ link_g, const sq_u64* __restrict__ ovl_g,
+                                                                float* __restrict__ best_g, short* __restrict__ next_g,
+                                                                float* __restrict__ osc_g, sq_u64* __restrict__ alive_g,
+                                                                sq_u64* __restrict__ keep_g, sq_u64* __restrict__ wmax_g,
+                                                                int2* __restrict__ tube_g, int* __restrict__ tcount) {
   __shared__ float bestL[2][SQ_MAX_R];
   __shared__ int chg[3];
   __shared__ sq_u64 red[SQ_MAX_W];
   __shared__ int cnt[SQ_MAX_W];
   const int c = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const float* sc = scores + 1 + c;
-  float* best = best_g + (long)c * F * R;
-  short* next = next_g + (long)c * F * R;
-  float* osc = osc_g + (long)c * F * R;
-  sq_u64* alive = alive_g + (long)c * F * W;
-  sq_u64* keep = keep_g + (long)c * F * W;
-  sq_u64* wmax = wmax_g + (long)c * F * W;
+  int f0 = 0, f1 = Ftot;
+  if (frame_start) {
+    f0 = min(max(frame_start[blockIdx.y], 0), Ftot);
+    f1 = min(max(frame_start[blockIdx.y + 1], f0), Ftot);
+  }
+  const int F = f1 - f0;
+  const long row0 = ((long)c * Ftot + f0) * R, word0 = ((long)c * Ftot + f0) * W;
+  const float* sc = scores + (long)f0 * R * ncls + 1 + c;
+  const sq_u64* link = link_g + (long)f0 * R * W;
+  const sq_u64* ovl = ovl_g + (long)f0 * R * W;
+  float* best = best_g + row0;
+  short* next = next_g + row0;
+  float* osc = osc_g + row0;
+  int2* tube = tube_g ? tube_g + row0 : nullptr;
+  sq_u64* alive = alive_g + word0;
+  sq_u64* keep = keep_g + word0;
+  sq_u64* wmax = wmax_g + word0;
 
   // ---- candidates ----
   int mine = 0;
@@ -108,7 +151,8 @@ __global__ __launch_bounds__(SQ_MAX_R) void seq_nms_path_kernel(const float* __r
 
   int e = F - 1, rt = F;
   bool first = true;
-  for (int it = 0; it < N; ++it) {   // every round retires its root: at most N rounds
+  int it = 0;   // the round counter: a tube's index within its class and problem
+  for (; it < N; ++it) {   // every round retires its root: at most N rounds
     // ---- sums: frames e .. 0, stopping early below the last path's root frame ----
     if (e + 1 < F && tid < R) bestL[(e + 1) & 1][tid] = best[(long)(e + 1) * R + tid];
     if (tid < 3) chg[tid] = 0;
@@ -189,21 +233,61 @@ __global__ __launch_bounds__(SQ_MAX_R) void seq_nms_path_kernel(const float* __r
     tt = rt;
     rr = r0;
     while (rr >= 0 && tt < F) {
-      if (tid == 0) osc[(long)tt * R + rr] = out;
+      if (tid == 0) {
+        osc[(long)tt * R + rr] = out;
+        if (tube) tube[(long)tt * R + rr] = make_int2(it, tt == rt ? n : 0);
+      }
       rr = next[(long)tt * R + rr];
       ++tt;
     }
+  }
+  if (tcount && tid == 0) tcount[(long)blockIdx.y * gridDim.x + c] = it;   // (a round that found nothing alive left the loop before ++it)
+}
+
+// per problem the exclusive prefix of the round counts over its classes (cbase: the first tube id of a class), then the exclusive
+// prefix of the problems' totals (tube_start [P + 1]; the last entry is the true total).  One workgroup.
+__global__ __launch_bounds__(256) void seq_nms_tube_prefix_kernel(const int* __restrict__ tcount, int P, int nfg, int* __restrict__ cbase,
+                                                                  int* __restrict__ tube_start) {
+  for (int p = threadIdx.x; p < P; p += blockDim.x) {
+    int s = 0;
+    for (int c = 0; c < nfg; ++c) {
+      cbase[(long)p * nfg + c] = s;
+      s += tcount[(long)p * nfg + c];
+    }
+    tube_start[p + 1] = s;   // the problem's total, until the scan below replaces it
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int run = 0;
+    for (int p = 0; p < P; ++p) {
+      const int total = tube_start[p + 1];
+      tube_start[p] = run;
+      run += total;
+    }
+    tube_start[P] = run;
   }
 }
 
 __global__ __launch_bounds__(1024) void seq_nms_merge_kernel(const float* __restrict__ boxes, int F, int R, int W, int nfg,
                                                              const float* __restrict__ osc, const sq_u64* __restrict__ keep,
                                                              int max_num, int sp2, float* __restrict__ dets,
-                                                             long long* __restrict__ labels, int* __restrict__ n_out) {
+                                                             long long* __restrict__ labels, int* __restrict__ n_out,
+                                                             const int* __restrict__ frame_start, int P, const int2* __restrict__ tube_g,
+                                                             const int* __restrict__ cbase, const int* __restrict__ tube_start,
+                                                             int* __restrict__ tube_ids, int4* __restrict__ tubes,
+                                                             float* __restrict__ tube_scores, int max_tubes) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ int offs[128], cnts[128];
+  __shared__ int offs[128], cnts[128], cb[128];
   __shared__ int sh_total;
   const int t = blockIdx.x;
+  // tube outputs (tube_ids != NULL): this frame's problem p, its first frame f0, its first table row and its classes' id bases
+  int p = 0, f0 = 0, f1, row0 = 0;
+  if (tube_ids) {
+    p = sq_problem_of(frame_start, P, F, t, f0, f1);
+    row0 = tube_start[p];
+    if ((int)threadIdx.x < nfg) cb[threadIdx.x] = cbase[(long)p * nfg + threadIdx.x];
+    tube_ids += (long)t * max_num;
+  }
   boxes += (long)t * R * 4;
   dets += (long)t * max_num * 5;
   labels += (long)t * max_num;
@@ -235,6 +319,14 @@ __global__ __launch_bounds__(1024) void seq_nms_merge_kernel(const float* __rest
         const int q = pos + (int)__popcll(m & ((1ull << lane) - 1ull));
         key[q] = float_key(osc[((long)c * F + t) * R + r]);
         idx[q] = ((uint32_t)c << 16) | (uint32_t)r;
+        if (tube_ids) {   // a root box writes its tube's table row (every tube has one root: every row is written once)
+          const int2 tu = tube_g[((long)c * F + t) * R + r];
+          const long row = (long)row0 + cb[c] + tu.x;
+          if (tu.y > 0 && row >= 0 && row < (long)max_tubes) {
+            tubes[row] = make_int4(p, c, t - f0, tu.y);
+            tube_scores[row] = osc[((long)c * F + t) * R + r];
+          }
+        }
       }
       pos += (int)__popcll(m);
     }
@@ -250,10 +342,12 @@ __global__ __launch_bounds__(1024) void seq_nms_merge_kernel(const float* __rest
     dets[j * 5 + 3] = boxes[r * 4 + 3];
     dets[j * 5 + 4] = osc[((long)c * F + t) * R + r];
     labels[j] = c;
+    if (tube_ids) tube_ids[j] = cb[c] + tube_g[((long)c * F + t) * R + r].x;
   }
   for (int j = nout + threadIdx.x; j < max_num; j += blockDim.x) {
     dets[j * 5 + 0] = dets[j * 5 + 1] = dets[j * 5 + 2] = dets[j * 5 + 3] = dets[j * 5 + 4] = 0.f;
     labels[j] = 0;
+    if (tube_ids) tube_ids[j] = -1;
   }
   if (threadIdx.x == 0) n_out[t] = nout;
 }
@@ -261,15 +355,21 @@ __global__ __launch_bounds__(1024) void seq_nms_merge_kernel(const float* __rest
 // ---------------- launchers ----------------
 static size_t sq_al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-size_t seq_nms_workspace_bytes(int F, int R, int ncls) {
+// tubes: the per-box (round, length) table, the per-(problem, class) round counts and their prefix
+size_t seq_nms_workspace_bytes(int P, int F, int R, int ncls, int tubes) {
   const size_t W = (size_t)(R + 63) / 64, nfg = (size_t)ncls - 1, f = (size_t)F, r = (size_t)R;
-  return 2 * sq_al256(f * r * W * 8) + 2 * sq_al256(nfg * f * r * 4) + sq_al256(nfg * f * r * 2) + 3 * sq_al256(nfg * f * W * 8) + 256;
+  const size_t base = 2 * sq_al256(f * r * W * 8) + 2 * sq_al256(nfg * f * r * 4) + sq_al256(nfg * f * r * 2) + 3 * sq_al256(nfg * f * W * 8) + 256;
+  return base + (tubes ? sq_al256(nfg * f * r * 8) + 2 * sq_al256((size_t)P * nfg * 4) : 0);
 }
 
-hipError_t run_seq_nms(const float* boxes, const float* scores, int F, int R, int ncls, float score_thr, float link_thr, float nms_thr,
-                       int rescore_max, int max_num, float* dets, long long* labels, int* n_out, void* ws, int phases, hipStream_t s) {
+// P problems of frame_start [P + 1] (device; NULL: one problem of all F frames), F frames in all.  tube_ids != NULL: the four tube
+// outputs (all four non-NULL then).
+hipError_t run_seq_nms(const float* boxes, const float* scores, int P, const int* frame_start, int F, int R, int ncls, float score_thr,
+                       float link_thr, float nms_thr, int rescore_max, int max_num, float* dets, long long* labels, int* n_out,
+                       int* tube_ids, int* tubes, float* tube_scores, int* tube_start, int max_tubes, void* ws, int phases, hipStream_t s) {
   const int nfg = ncls - 1;
-  if (R > SQ_MAX_R || R <= 0 || nfg > 128 || nfg < 1 || F <= 0 || F > SQ_MAX_F || max_num <= 0) return hipErrorInvalidValue;
+  if (R > SQ_MAX_R || R <= 0 || nfg > 128 || nfg < 1 || F <= 0 || F > SQ_MAX_F || max_num <= 0 || P < 1 || P > F || (!frame_start && P != 1))
+    return hipErrorInvalidValue;
   const int W = (R + 63) / 64;
   const size_t f = (size_t)F, r = (size_t)R, w = (size_t)W, g = (size_t)nfg;
   char* p = (char*)ws;
@@ -280,7 +380,14 @@ hipError_t run_seq_nms(const float* boxes, const float* scores, int F, int R, in
   short* next = (short*)p;     p += sq_al256(g * f * r * 2);
   sq_u64* alive = (sq_u64*)p;  p += sq_al256(g * f * w * 8);
   sq_u64* keep = (sq_u64*)p;   p += sq_al256(g * f * w * 8);
-  sq_u64* wmax = (sq_u64*)p;
+  sq_u64* wmax = (sq_u64*)p;   p += sq_al256(g * f * w * 8) + 256;
+  int2* tube = nullptr;
+  int *tcount = nullptr, *cbase = nullptr;
+  if (tube_ids) {
+    tube = (int2*)p;           p += sq_al256(g * f * r * 8);
+    tcount = (int*)p;          p += sq_al256((size_t)P * g * 4);
+    cbase = (int*)p;
+  }
   // the merge's LDS as for the other read-outs: the longest possible list (every candidate of every class kept) + the select list
   int np2 = 1;
   while (np2 < nfg * R) np2 <<= 1;
@@ -294,10 +401,13 @@ hipError_t run_seq_nms(const float* boxes, const float* scores, int F, int R, in
   per_device_once(attr_dev, [&] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_nms_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
   });
-  if (phases & 1) hipLaunchKernelGGL(seq_nms_link_kernel, dim3((R + 3) / 4, F), dim3(256), 0, s, (const float4*)boxes, F, R, W, link_thr, nms_thr, link, ovl);
-  if (phases & 2) hipLaunchKernelGGL(seq_nms_path_kernel, dim3(nfg), dim3(64 * W), 0, s, scores, F, R, W, ncls, score_thr, rescore_max, link, ovl, best,
-                     next, osc, alive, keep, wmax);
-  if (phases & 4) hipLaunchKernelGGL(seq_nms_merge_kernel, dim3(F), dim3(1024), lds, s, boxes, F, R, W, nfg, osc, keep, max_num, sp2, dets, labels, n_out);
+  if (phases & 1) hipLaunchKernelGGL(seq_nms_link_kernel, dim3((R + 3) / 4, F), dim3(256), 0, s, (const float4*)boxes, frame_start, P, F, R, W, link_thr, nms_thr,
+                     link, ovl);
+  if (phases & 2) hipLaunchKernelGGL(seq_nms_path_kernel, dim3(nfg, P), dim3(64 * W), 0, s, scores, frame_start, F, R, W, ncls, score_thr, rescore_max, link,
+                     ovl, best, next, osc, alive, keep, wmax, tube, tcount);
+  if ((phases & 4) && tube_ids) hipLaunchKernelGGL(seq_nms_tube_prefix_kernel, dim3(1), dim3(256), 0, s, tcount, P, nfg, cbase, tube_start);
+  if (phases & 4) hipLaunchKernelGGL(seq_nms_merge_kernel, dim3(F), dim3(1024), lds, s, boxes, F, R, W, nfg, osc, keep, max_num, sp2, dets, labels, n_out,
+                     frame_start, P, tube, cbase, tube_start, tube_ids, (int4*)tubes, tube_scores, max_tubes);
   return hipGetLastError();
 }
 

@@ -429,25 +429,60 @@ class _WindowDetector(TwoStageDetector):
                                                       rescale=rescale, cfg=None)
         return [(boxes, scores)] if torch.is_tensor(boxes) else list(zip(boxes, scores))
 
-    def seq_nms_video(self, raws, link_iou_thr=0.5, rescore='avg'):
+    def seq_nms_video(self, raws, link_iou_thr=0.5, rescore='avg', tubes=False, frame_offsets=None):
         """Seq-NMS over one video's key frames.  raws: the raw read-outs (`forward_feat(..., raw=True)`) in frame order.  Per output
-        branch the frames' rows are padded to test_cfg.rpn.nms_post with zero scores, stacked, and go through ONE native.seq_nms call
-        with score_thr = rcnn.score_thr, nms_thr = rcnn.nms.iou_thr, max_num = rcnn.max_per_img.  -> one result per frame in
-        forward_feat's structure (30 per-class arrays, or [branch, final] for HNMBRCNN)."""
+        branch the frames' rows are padded to test_cfg.rpn.nms_post with zero scores and stacked; the branches (two for HNMBRCNN) are
+        the problems of ONE native.seq_nms_batched call with score_thr = rcnn.score_thr, nms_thr = rcnn.nms.iou_thr, max_num =
+        rcnn.max_per_img.  -> one result per frame in forward_feat's structure (30 per-class arrays, or [branch, final] for HNMBRCNN).
+        tubes=True: -> (results, tube data), see seq_nms_videos; frame_offsets (default 0, 1, ...) are the frames' offsets in the
+        video, which the tube table's start frames are translated to."""
+        out = self.seq_nms_videos([raws], link_iou_thr, rescore, tubes, None if frame_offsets is None else [frame_offsets])
+        return (out[0][0], out[1][0]) if tubes else out[0]
+
+    def seq_nms_videos(self, videos, link_iou_thr=0.5, rescore='avg', tubes=False, frame_offsets=None):
+        """seq_nms_video for several videos in ONE native.seq_nms_batched call: the problems are (video, branch) pairs, video-major,
+        side by side on the device.  videos: one list of raw read-outs per video -> one list of per-frame results per video.
+        tubes=True: -> (results, tube data); the tube data of a video is one dict per read-out branch (a bare dict for SelsaRCNN):
+          ids     per frame, per class: int32 array of tube ids aligned with the result's per-class detection array
+          tubes   [n,4] int32: (branch, 0-based label, start frame as its offset from frame_offsets, length in boxes selected)
+          scores  [n] f32: the rescored value every member received
+        Tube ids are local to (video, branch) and index the rows of `tubes`."""
         cfg = self.test_cfg.rcnn
         check_seq_nms_cfg(cfg)
         R = int(self.test_cfg.rpn.nms_post)
-        host = []
-        for b in range(len(raws[0])):
-            boxes = torch.stack([_pad_rows(r[b][0].float(), R) for r in raws], 0)
-            scores = torch.stack([_pad_rows(r[b][1].float(), R) for r in raws], 0)
-            host.append([t.cpu() for t in native.seq_nms(boxes, scores, cfg.score_thr, link_iou_thr, cfg.nms.iou_thr, cfg.max_per_img, rescore)])
+        videos = [list(v) for v in videos]
+        if not videos or any(not v for v in videos):
+            raise ValueError('seq_nms_videos needs at least one key frame per video')
+        nb = len(videos[0][0])
+        counts = [len(v) for v in videos for _ in range(nb)]
+        boxes = torch.stack([_pad_rows(r[b][0].float(), R) for v in videos for b in range(nb) for r in v], 0)
+        scores = torch.stack([_pad_rows(r[b][1].float(), R) for v in videos for b in range(nb) for r in v], 0)
+        host = [t.cpu() for t in native.seq_nms_batched(boxes, scores, counts, cfg.score_thr, link_iou_thr, cfg.nms.iou_thr, cfg.max_per_img,
+                                                         rescore, tubes=tubes)]
+        d, l, n = host[:3]
         single = isinstance(self, SelsaRCNN)      # one read-out branch, returned bare (subclasses included)
-        results = []
-        for t in range(len(raws)):
-            out = [bbox2result(d[t, :int(n[t])], l[t, :int(n[t])], self.bbox_head.num_classes) for d, l, n in host]
-            results.append(out[0] if single else out)
-        return results
+        ncl = self.bbox_head.num_classes
+        results, tube_data, f0 = [], [], 0
+        for v, raws in enumerate(videos):
+            Fv = len(raws)
+            offs = list(range(Fv)) if frame_offsets is None else list(frame_offsets[v])
+            per_frame, per_branch = [], []
+            for b in range(nb):
+                lo = f0 + b * Fv
+                per_frame.append([bbox2result(d[lo + t, :int(n[lo + t])], l[lo + t, :int(n[lo + t])], ncl) for t in range(Fv)])
+                if tubes:
+                    ids, table, tsc, start = host[3:]
+                    p = v * nb + b
+                    rows = table[int(start[p]):int(start[p + 1])].numpy().copy()
+                    rows[:, 0] = b
+                    rows[:, 2] = [offs[t] for t in rows[:, 2]]
+                    per_branch.append(dict(ids=[[ids[lo + t, :int(n[lo + t])][l[lo + t, :int(n[lo + t])] == c].numpy() for c in range(ncl - 1)]
+                                                for t in range(Fv)],
+                                           tubes=rows, scores=tsc[int(start[p]):int(start[p + 1])].numpy().copy()))
+            results.append([per_frame[0][t] if single else [pf[t] for pf in per_frame] for t in range(Fv)])
+            tube_data.append(per_branch[0] if single and tubes else per_branch)
+            f0 += nb * Fv
+        return (results, tube_data) if tubes else results
 
     # ---- multi-scale / flip test-time augmentation (hnmb_rcnn.py:104-180, 640-698) ------------------------------------
     # x[t][a] = C4 map of frame t under augmentation a, img_meta[t][a] its meta (the MultiScaleFlipAug order: scale outer, flip

@@ -174,6 +174,8 @@ SYMBOLS = {
     'hvr_seq_nms_workspace_bytes': (_sz, [_i, _i, _i]),
     'hvr_seq_nms': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'hvr_seq_nms_phases': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    'hvr_seq_nms_batched_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'hvr_seq_nms_batched': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     'hvr_cast': (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     'hvr_cast_scaled': (_i, [_vp, _vp, _i64, _i, _i, _f, _vp]),
     'hvr_permute_nchw_nhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -1425,6 +1427,69 @@ def seq_nms(boxes, scores, score_thr, link_iou_thr=0.5, nms_iou_thr=0.3, max_num
     else:
         _check(lib().hvr_seq_nms_phases(*args, int(phases), _stream()), 'hvr_seq_nms_phases')
     return dets, labels, n_out
+
+
+_FRAME_STARTS = {}      # (device, frame counts) -> device int32 [P+1]: a repeated (also a captured) call uploads nothing
+
+
+def _frame_start(frame_counts, Ftot, device):
+    try:
+        counts = tuple(int(c) for c in frame_counts)
+    except TypeError:
+        raise ValueError('frame_counts is a host list of frame counts, got %r' % (frame_counts,))
+    if not counts or min(counts) < 1 or sum(counts) != Ftot:
+        raise ValueError('frame_counts must hold one count >= 1 per problem and sum to the %d stacked frames, got %s' % (Ftot, list(counts)))
+    key = (str(device), counts)
+    if key not in _FRAME_STARTS:
+        if len(_FRAME_STARTS) >= 256:
+            _FRAME_STARTS.clear()
+        starts = [0]
+        for c in counts:
+            starts.append(starts[-1] + c)
+        _FRAME_STARTS[key] = torch.tensor(starts, dtype=torch.int32, device=device)
+    return counts, _FRAME_STARTS[key]
+
+
+def seq_nms_batched(boxes, scores, frame_counts, score_thr, link_iou_thr=0.5, nms_iou_thr=0.3, max_num=300, rescore='avg', tubes=False,
+                    max_tubes=None, out=None):
+    """Seq-NMS over P independent problems (one video's key frames for one read-out branch each) in ONE call: boxes [Ftot,R,4],
+    scores [Ftot,R,ncls] f32 are the problems' frames stacked, frame_counts the host list of their P frame counts (each >= 1, summing
+    to Ftot; ValueError otherwise).  -> (dets [Ftot,max_num,5], labels [Ftot,max_num] int64, n [Ftot] int32), problem by problem
+    bit-identical to seq_nms on the slices: nothing crosses a problem boundary.
+    tubes=True appends (tube_ids [Ftot,max_num] int32: the problem-local tube of each output row, -1 behind n[t];
+    tubes [max_tubes,4] int32: (problem, label, start frame within the problem, length) problem-major then in id order;
+    tube_scores [max_tubes] f32; tube_start [P+1] int32, tube_start[P] = the true total).  max_tubes defaults to the candidate bound
+    (ncls-1) * Ftot * R; with a smaller one only the first max_tubes rows are written (the rest stays as it was), ids and tube_start
+    stay exact.  out = a result tuple of these shapes (3 or 7 tensors) to write into instead of allocating one."""
+    code = _seq_rescore(rescore)
+    _need_cuda(boxes, scores)
+    if scores.dim() != 3 or boxes.dim() != 3 or tuple(boxes.shape) != (scores.shape[0], scores.shape[1], 4):
+        raise ValueError('seq_nms takes boxes [F,R,4] and scores [F,R,ncls], got %s and %s' % (tuple(boxes.shape), tuple(scores.shape)))
+    Ftot, R, ncls = scores.shape
+    counts, starts = _frame_start(frame_counts, Ftot, boxes.device)
+    P = len(counts)
+    dev = boxes.device
+    alloc = torch.empty if R > 0 else torch.zeros
+    if max_tubes is None:
+        max_tubes = max(ncls - 1, 0) * Ftot * R
+    if out is not None:
+        if len(out) != (7 if tubes else 3):
+            raise ValueError('out holds %d tensors, the call returns %d' % (len(out), 7 if tubes else 3))
+        res = tuple(out)
+    else:
+        res = (alloc((Ftot, max_num, 5), dtype=torch.float32, device=dev), alloc((Ftot, max_num), dtype=torch.long, device=dev),
+               alloc(Ftot, dtype=torch.int32, device=dev))
+        if tubes:
+            ids = alloc((Ftot, max_num), dtype=torch.int32, device=dev) if R > 0 else torch.full((Ftot, max_num), -1, dtype=torch.int32, device=dev)
+            res += (ids, alloc((int(max_tubes), 4), dtype=torch.int32, device=dev), alloc(int(max_tubes), dtype=torch.float32, device=dev),
+                    alloc(P + 1, dtype=torch.int32, device=dev))
+    ws = _workspace(lib().hvr_seq_nms_batched_workspace_bytes(P, Ftot, R, ncls, int(bool(tubes))), dev, 'seqnms')
+    tube_ptrs = [_ptr(t) if t.numel() else _ptr(_workspace(16, dev, 'seqnms_none')) for t in res[3:]] if tubes else [None] * 4
+    _check(lib().hvr_seq_nms_batched(_ptr(boxes.contiguous().float()), _ptr(scores.contiguous().float()), P, _ptr(starts), Ftot, R, ncls,
+                                     float(score_thr), float(link_iou_thr), float(nms_iou_thr), code, int(max_num), _ptr(res[0]), _ptr(res[1]),
+                                     _ptr(res[2]), tube_ptrs[0], tube_ptrs[1], tube_ptrs[2], tube_ptrs[3], int(max_tubes) if tubes else 0,
+                                     _ptr(ws), ws.numel(), _stream()), 'hvr_seq_nms_batched')
+    return res
 
 
 def readout_nms(boxes, scores, score_thr, nms_cfg, max_num):

@@ -8,7 +8,7 @@ signatures and error behaviour:
   roi_align(features, rois, out_size, spatial_scale, sample_num)           roi_align/roi_align.py:56
   nms(dets, iou_thr, device_id=None) -> (dets[inds], inds)                  nms/nms_wrapper.py:8-61
   soft_nms(dets, iou_thr, method='linear', sigma=0.5, min_score=1e-3)      nms/nms_wrapper.py:64-102
-  seq_nms(boxes, scores, score_thr, link_iou_thr=0.5, nms_iou_thr=0.3, max_num=300, rescore='avg')   (no reference counterpart:
+  seq_nms(boxes, scores, score_thr, link_iou_thr=0.5, nms_iou_thr=0.3, max_num=300, rescore='avg', *, frame_counts=None, tubes=False)   (no reference counterpart:
                                                                            Seq-NMS over one video, specified in DESIGN.md)
 plus `relation(q, k, v, scale)`: the relation core as an autograd Function with a HIP backward (training path).
 CPU tensors raise NotImplementedError exactly like the reference's RoIAlign (roi_align.py:27-28);
@@ -170,17 +170,24 @@ def soft_nms(dets, iou_thr, method='linear', sigma=0.5, min_score=1e-3):
     return out[:k].to(dets.dtype), inds[:k]
 
 
-def seq_nms(boxes, scores, score_thr, link_iou_thr=0.5, nms_iou_thr=0.3, max_num=300, rescore='avg'):
+def seq_nms(boxes, scores, score_thr, link_iou_thr=0.5, nms_iou_thr=0.3, max_num=300, rescore='avg', *, frame_counts=None, tubes=False):
     """Seq-NMS (Han et al. 2016) over the key frames of ONE video on the device: boxes [F,R,4] (class-agnostic), scores [F,R,ncls]
     (column 0 = background), frames in time order -> (dets [F,max_num,5], labels [F,max_num] int64, n [F] int32) device tensors.
     Per class, boxes of adjacent frames link at IoU >= link_iou_thr; the highest-scoring sequence is selected, its boxes rescored
     ('avg': sum / length, 'max': the sequence's best score) and kept, their in-frame overlaps at IoU >= nms_iou_thr dropped, until
     no box with score > score_thr is left; per frame the kept boxes come out as multiclass_nms lists them (class-major, cut to the
-    max_num best).  DESIGN.md holds the exact specification; one frame gives per-class greedy NMS."""
+    max_num best).  DESIGN.md holds the exact specification; one frame gives per-class greedy NMS.
+    frame_counts = [F_0, F_1, ...] (host list summing to F): the frames are those of several independent problems (videos, read-out
+    branches) stacked, processed side by side in one call; nothing links across a boundary.  tubes=True appends (tube_ids
+    [F,max_num] int32, tubes [n,4] int32 = (problem, label, start frame within the problem, length), tube_scores [n] f32, tube_start
+    [P+1] int32): which selected sequence every output row belongs to (native.seq_nms_batched)."""
     if rescore not in native.SEQ_NMS_RESCORE:
         raise ValueError('Invalid rescore for Seq-NMS: {} (avg, max)'.format(rescore))
     if not isinstance(boxes, torch.Tensor) or not isinstance(scores, torch.Tensor):
         raise TypeError('boxes and scores must be Tensors, but got {} and {}'.format(type(boxes), type(scores)))
     if not boxes.is_cuda or not scores.is_cuda:
         raise NotImplementedError('hvr seq_nms runs on the GPU only (no CPU fallback)')
-    return native.seq_nms(boxes, scores, score_thr, link_iou_thr, nms_iou_thr, max_num, rescore)
+    if frame_counts is None and not tubes:
+        return native.seq_nms(boxes, scores, score_thr, link_iou_thr, nms_iou_thr, max_num, rescore)
+    return native.seq_nms_batched(boxes, scores, [scores.shape[0]] if frame_counts is None else frame_counts, score_thr, link_iou_thr,
+                                  nms_iou_thr, max_num, rescore, tubes=tubes)

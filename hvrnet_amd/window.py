@@ -33,7 +33,10 @@ class VideoWindowRunner(object):
     seq_nms = dict(link_iou_thr=0.5, rescore='avg') (default: test_cfg.rcnn's `seq_nms` key, None = off): every window is read out
     raw (`forward_feat(..., raw=True)`: decoded boxes and scores, no per-frame NMS) and `run_video` hands the key frames of the whole
     video, in frame order, to `model.seq_nms_video` once -- Seq-NMS replaces the per-frame NMS; same result structure.  Not
-    combined with nms type 'soft_nms' (ValueError) or test-time augmentation (NotImplementedError)."""
+    combined with nms type 'soft_nms' (ValueError) or test-time augmentation (NotImplementedError).  The dict also takes
+    tubes=True: `run_video` returns what it returns without it and leaves the tube data of the video (`model.seq_nms_video(...,
+    tubes=True)`: which selected sequence every detection belongs to) in `runner.tubes`.  `run_videos(videos, metas)` runs the
+    windows video by video and ONE batched Seq-NMS over all of them at the end (`model.seq_nms_videos`)."""
 
     def __init__(self, model, window, rescale=True, cache_frames=False, seq_nms=None):
         assert window % 2 == 1, 'window = 2 * frame_interval + 1'
@@ -43,15 +46,16 @@ class VideoWindowRunner(object):
             seq_nms = rcnn.get('seq_nms')
         self.seq_nms = dict(seq_nms) if seq_nms is not None else None   # ({} = Seq-NMS with its defaults)
         if self.seq_nms is not None:
-            unknown = set(self.seq_nms) - {'link_iou_thr', 'rescore'}
+            unknown = set(self.seq_nms) - {'link_iou_thr', 'rescore', 'tubes'}
             if unknown:
-                raise ValueError('seq_nms takes link_iou_thr and rescore, got %s' % sorted(unknown))
+                raise ValueError('seq_nms takes link_iou_thr and rescore (and tubes), got %s' % sorted(unknown))
             if self.seq_nms.get('rescore', 'avg') not in ('avg', 'max'):
                 raise ValueError('Invalid rescore for Seq-NMS: {} (avg, max)'.format(self.seq_nms['rescore']))
             if rcnn is not None:
                 from .detectors import check_seq_nms_cfg
                 check_seq_nms_cfg(rcnn)
         self.center = (window - 1) // 2
+        self.tubes = None   # seq_nms with tubes=True: the tube data of the last run_video (of every video after run_videos)
         self._reset()
 
     _entry = None
@@ -109,8 +113,50 @@ class VideoWindowRunner(object):
             raise ValueError('bad key_frame_flag %r' % (flag,))
         return out
 
+    def _seq_nms_args(self):
+        """keyword arguments of model.seq_nms_video(s): the dict as given, `tubes` only when it is set (-> want tubes, kwargs)"""
+        kw = dict(self.seq_nms)
+        tubes = bool(kw.pop('tubes', False))
+        return tubes, dict(kw, tubes=True) if tubes else kw
+
     def run_video(self, frames, metas):
         """frames: iterable of [1,3,H,W] tensors of one video. Returns {frame_offset: result}."""
+        results = self._run_windows(frames, metas)
+        if self.seq_nms is not None and results:   # results holds the raw read-outs: one Seq-NMS over the video's key frames
+            offs = sorted(results)
+            tubes, kw = self._seq_nms_args()
+            if tubes:
+                out, self.tubes = self.model.seq_nms_video([results[o] for o in offs], frame_offsets=offs, **kw)
+            else:
+                out = self.model.seq_nms_video([results[o] for o in offs], **kw)
+            return dict(zip(offs, out))
+        return results
+
+    def run_videos(self, videos, metas):
+        """videos: a list of frame lists, metas: their meta lists.  The windows run video by video; with seq_nms the raw read-outs of
+        ALL videos go through one batched Seq-NMS at the end (their read-out branches side by side on the device).  Returns one
+        {frame_offset: result} per video, equal to run_video on each; with tubes=True `runner.tubes` holds one entry per video."""
+        raws = [self._run_windows(f, m) for f, m in zip(videos, metas)]
+        if self.seq_nms is None or not any(raws):
+            return raws
+        live = [v for v, r in enumerate(raws) if r]
+        offs = [sorted(raws[v]) for v in live]
+        tubes, kw = self._seq_nms_args()
+        args = [[raws[v][o] for o in off] for v, off in zip(live, offs)]
+        if tubes:
+            out, data = self.model.seq_nms_videos(args, frame_offsets=offs, **kw)
+            self.tubes = [None] * len(raws)
+            for v, t in zip(live, data):
+                self.tubes[v] = t
+        else:
+            out = self.model.seq_nms_videos(args, **kw)
+        results = [{} for _ in raws]
+        for v, off, res in zip(live, offs, out):
+            results[v] = dict(zip(off, res))
+        return results
+
+    def _run_windows(self, frames, metas):
+        """The window loop over one video -> {frame_offset: what the windows returned} (the raw read-outs with seq_nms)."""
         frames = list(frames)
         flags = frame_flags(len(frames))
         results = {}
@@ -120,9 +166,6 @@ class VideoWindowRunner(object):
         if len(frames) == 1:  # a one-frame segment is both first and last
             for off, res in self.step(frames[0], metas[0], LAST, 0, seg_len=1):
                 results[off] = res
-        if self.seq_nms is not None and results:   # results holds the raw read-outs: one Seq-NMS over the video's key frames
-            offs = sorted(results)
-            return dict(zip(offs, self.model.seq_nms_video([results[o] for o in offs], **self.seq_nms)))
         return results
 
 

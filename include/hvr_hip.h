@@ -475,6 +475,26 @@ int hvr_seq_nms(const float* boxes, const float* scores, int F, int R, int ncls,
 int hvr_seq_nms_phases(const float* boxes, const float* scores, int F, int R, int ncls, float score_thr, float link_thr, float nms_thr,
                        int rescore, int max_num, float* dets, int64_t* labels, int32_t* n_out, void* ws, size_t ws_bytes, int phases,
                        void* stream);
+/* Several problems per launch and tube outputs: the same kernels, hvr_seq_nms being their P = 1, no-tubes case.
+ * A problem is one video's key frames for one read-out branch: problem p owns the frames frame_start[p] .. frame_start[p+1]-1 of
+ * boxes [Ftot][R][4] / scores [Ftot][R][ncls]; frame_start is a DEVICE int32 [P+1] array the caller builds (frame_start[0] = 0,
+ * frame_start[P] = Ftot, every problem at least one frame; the kernels clamp what they read from it to 0 .. Ftot).  Nothing crosses
+ * a problem boundary: dets / labels / n_out ([Ftot]...) are, problem by problem, bit-identical to P calls of hvr_seq_nms on the slices.
+ * Tube outputs (all four pointers NULL = none; any other mix: HVR_EINVAL): every selected path is a tube (singletons count), ids are
+ * problem-local, 0-based, class-major and within a class in selection order.  tube_ids [Ftot][max_num] int32: the tube of each
+ * output row, -1 behind n_out[t].  The table is concatenated problem-major, then in id order: tubes [max_tubes][4] int32 =
+ * (problem, 0-based label, start frame relative to the problem, length -- the boxes selected on the path, also those the per-frame
+ * max_num cut removed from their frame's list), tube_scores [max_tubes] f32 the rescored value of every member, tube_start [P+1]
+ * int32 the prefix counts (tube_start[P] = the true total).  Only the first min(total, max_tubes) rows are written, the rows
+ * behind stay untouched; tube_start and all ids stay exact.  The table is 16-byte aligned.
+ * Limits as hvr_seq_nms, and P >= 1, Ftot >= P, max_tubes >= 0 with tubes (else HVR_EINVAL), Ftot <= 65535 (else HVR_EUNSUPPORTED);
+ * nothing is launched on an error.  R == 0 writes only the counts (n_out, tube_start: zero).  Three launches on `stream` (four
+ * with tubes), no host read: capturable. */
+size_t hvr_seq_nms_batched_workspace_bytes(int P, int Ftot, int R, int ncls, int tubes);
+int hvr_seq_nms_batched(const float* boxes, const float* scores, int P, const int32_t* frame_start, int Ftot, int R, int ncls, float score_thr,
+                        float link_thr, float nms_thr, int rescore, int max_num, float* dets, int64_t* labels, int32_t* n_out,
+                        int32_t* tube_ids, int32_t* tubes, float* tube_scores, int32_t* tube_start, int max_tubes, void* ws, size_t ws_bytes,
+                        void* stream);
 
 /* ---- layout / dtype plumbing at the API boundary ---- */
 /* any pair of the four dtypes; pairs other than f32 <-> bf16 move 8 elements per thread: n % 8 == 0 and 16-byte aligned buffers
