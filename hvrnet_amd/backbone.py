@@ -148,15 +148,26 @@ def enable_training(module):
 class Bottleneck(nn.Module, PackedMixin):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, style='pytorch', norm_cfg=None):
+    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, style='pytorch', norm_cfg=None, dcn=None):
         super(Bottleneck, self).__init__()
         assert style in ['pytorch', 'caffe']
+        assert dcn is None or isinstance(dcn, dict)
         self.inplanes, self.planes, self.stride, self.dilation, self.style = inplanes, planes, stride, dilation, style
         # caffe: stride on the first 1x1 (resnet.py:127-132)
         self.conv1_stride, self.conv2_stride = (1, stride) if style == 'pytorch' else (stride, 1)
         eps = (norm_cfg or {}).get('eps', 1e-5)
         self.conv1 = nn.Conv2d(inplanes, planes, 1, stride=self.conv1_stride, bias=False)
         self.bn1 = nn.BatchNorm2d(planes, eps=eps)
+        # resnet.py:147-186: conv2 is a (modulated) deformable 3x3 whose offsets (and mask logits) come from conv2_offset, a plain
+        # biased 3x3 on the same input; fallback_on_stride keeps the plain conv where conv2 carries a stride
+        self.dcn = dcn
+        self.with_dcn = dcn is not None and not (dcn.get('fallback_on_stride', False) and self.conv2_stride > 1)
+        self.with_modulated_dcn = self.with_dcn and bool(dcn.get('modulated', False))
+        self.deformable_groups = int(dcn.get('deformable_groups', 1)) if self.with_dcn else 1
+        if self.with_dcn:
+            offset_channels = 27 if self.with_modulated_dcn else 18
+            self.conv2_offset = nn.Conv2d(planes, self.deformable_groups * offset_channels, 3, stride=self.conv2_stride, padding=dilation,
+                                          dilation=dilation)
         self.conv2 = nn.Conv2d(planes, planes, 3, stride=self.conv2_stride, padding=dilation, dilation=dilation, bias=False)
         self.bn2 = nn.BatchNorm2d(planes, eps=eps)
         self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
@@ -167,6 +178,15 @@ class Bottleneck(nn.Module, PackedMixin):
     def _pack(self, dtype):
         p = dict(c1=fold_conv_bn(self.conv1, self.bn1, dtype), c2=fold_conv_bn(self.conv2, self.bn2, dtype),
                  c3=fold_conv_bn(self.conv3, self.bn3, dtype))
+        if self.with_dcn:
+            # the offset conv: Cout padded with zero rows to a multiple the engine takes (N % 4); its output stays f32 in every mode
+            wo, bo = fold_conv_bn(self.conv2_offset, None, torch.float32)
+            n = wo.shape[0]
+            npad = (n + 3) // 4 * 4
+            wp = torch.zeros((npad,) + tuple(wo.shape[1:]), dtype=torch.float32, device=wo.device)
+            bp = torch.zeros((npad,), dtype=torch.float32, device=wo.device)
+            wp[:n], bp[:n] = wo, bo
+            p['off'] = (native.as_operand(wp, dtype), bp)
         if self.downsample is not None:
             p['ds'] = fold_conv_bn(self.downsample[0], self.downsample[1], dtype)
             # the projection shortcut as a second K segment of the closing 1x1 (hvr_bottleneck_tail): rows [W3 | Wd]
@@ -184,8 +204,14 @@ class Bottleneck(nn.Module, PackedMixin):
         dst = out
         stride, conv1_stride = (1, 1) if compact_in else (self.stride, self.conv1_stride)
         out = h1 if h1 is not None else native.conv2d_nhwc(x, p['c1'][0], p['c1'][1], relu=True, stride=conv1_stride)
-        out = native.conv2d_nhwc(out, p['c2'][0], p['c2'][1], relu=True, stride=self.conv2_stride, pad=self.dilation,
-                                 dil=self.dilation)
+        if self.with_dcn:
+            om = native.conv2d_nhwc(out, p['off'][0], p['off'][1], relu=False, stride=self.conv2_stride, pad=self.dilation, dil=self.dilation,
+                                    out_f32=True)
+            out = native.deform_conv2d_nhwc(out, om, p['c2'][0], p['c2'][1], True, self.conv2_stride, self.dilation, self.dilation,
+                                            self.deformable_groups, self.with_modulated_dcn)
+        else:
+            out = native.conv2d_nhwc(out, p['c2'][0], p['c2'][1], relu=True, stride=self.conv2_stride, pad=self.dilation,
+                                     dil=self.dilation)
         if nxt is not None and self.fuse_next and nxt.conv1_stride == 1:
             pn = nxt.packed(x.device)
             wn, bn = pn['c1'][0].reshape(pn['c1'][0].shape[0], -1), pn['c1'][1]
@@ -222,7 +248,7 @@ class Bottleneck(nn.Module, PackedMixin):
         closing 1x1 on those pixels with the residual sampled from x (hvr_bottleneck_close_sampled).  -> (y, True) with
         y [B,(H-1)//stride+1,(W-1)//stride+1,4*planes] = the full-resolution output at [:, ::stride, ::stride] bit for bit, or
         (the full-resolution output, False) where the sampled close has no kernel for the dtype / shape."""
-        assert self.downsample is None and self.stride == 1
+        assert self.downsample is None and self.stride == 1 and not self.with_dcn
         p = self.packed(x.device)
         h = h1 if h1 is not None else native.conv2d_nhwc(x, p['c1'][0], p['c1'][1], relu=True, stride=1)
         B, H, W, _ = x.shape
@@ -244,6 +270,8 @@ class Bottleneck(nn.Module, PackedMixin):
     def forward_train_nhwc(self, x):
         """The block as an autograd graph of HIP convs (train_ops.conv_bn): frozen BatchNorm statistics and affine
         (norm_eval=True, requires_grad=False in both configs), trainable conv weights; f32, physical NHWC."""
+        if self.with_dcn:
+            raise NotImplementedError('deformable convs are inference only: no backward (col2im + coordinate gradients) is implemented')
         from . import train_ops as TO
         out = TO.conv_bn(x, self.conv1, self.bn1, relu=True)
         out = TO.conv_bn(out, self.conv2, self.bn2, relu=True)
@@ -251,16 +279,17 @@ class Bottleneck(nn.Module, PackedMixin):
         return TO.conv_bn(out, self.conv3, self.bn3, resid=identity, relu=True)
 
 
-def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style='pytorch', norm_cfg=None, **_unused):
+def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style='pytorch', norm_cfg=None, dcn=None, **_unused):
     downsample = None
     eps = (norm_cfg or {}).get('eps', 1e-5)
     if stride != 1 or inplanes != planes * block.expansion:
         downsample = nn.Sequential(nn.Conv2d(inplanes, planes * block.expansion, 1, stride=stride, bias=False),
                                    nn.BatchNorm2d(planes * block.expansion, eps=eps))
-    layers = [block(inplanes, planes, stride, dilation, downsample, style=style, norm_cfg=norm_cfg)]
+    extra = {} if dcn is None else dict(dcn=dcn)
+    layers = [block(inplanes, planes, stride, dilation, downsample, style=style, norm_cfg=norm_cfg, **extra)]
     inplanes = planes * block.expansion
     for _ in range(1, blocks):
-        layers.append(block(inplanes, planes, 1, dilation, style=style, norm_cfg=norm_cfg))
+        layers.append(block(inplanes, planes, 1, dilation, style=style, norm_cfg=norm_cfg, **extra))
     return nn.Sequential(*layers)
 
 
@@ -272,8 +301,8 @@ def _freeze(module):
 
 @BACKBONES.register_module
 class ResNet(nn.Module, PackedMixin):
-    """Same kwargs as the reference ResNet (resnet.py:372-395); dcn / gcb / gen_attention must be None
-    (both hot-path configs leave them unset)."""
+    """Same kwargs as the reference ResNet (resnet.py:372-395); dcn / stage_with_dcn as there (deformable conv2 in the marked
+    stages, inference only); gcb / gen_attention / conv_cfg must be None."""
     arch_settings = {d: (Bottleneck, s) for d, s in ARCH_SETTINGS.items()}
 
     def __init__(self, depth, in_channels=3, num_stages=4, strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1),
@@ -284,8 +313,11 @@ class ResNet(nn.Module, PackedMixin):
         super(ResNet, self).__init__()
         if depth not in self.arch_settings:
             raise KeyError('invalid depth {} for resnet'.format(depth))
-        if dcn is not None or gcb is not None or gen_attention is not None or conv_cfg is not None:
-            raise NotImplementedError('dcn / gcb / gen_attention / conv_cfg are outside the HVR hot path')
+        if gcb is not None or gen_attention is not None or conv_cfg is not None:
+            raise NotImplementedError('gcb / gen_attention / conv_cfg are outside the HVR hot path')
+        if dcn is not None:
+            assert len(stage_with_dcn) == num_stages
+        self.dcn, self.stage_with_dcn = dcn, stage_with_dcn
         if norm_cfg.get('type', 'BN') != 'BN':
             raise NotImplementedError('only frozen BatchNorm is supported')
         assert 1 <= num_stages <= 4 and len(strides) == len(dilations) == num_stages and max(out_indices) < num_stages
@@ -302,8 +334,9 @@ class ResNet(nn.Module, PackedMixin):
         for i, nb in enumerate(self.stage_blocks):
             planes = 64 * 2 ** i
             name = 'layer{}'.format(i + 1)
+            stage_dcn = dcn if dcn is not None and stage_with_dcn[i] else None
             self.add_module(name, make_res_layer(block, inplanes, planes, nb, stride=strides[i], dilation=dilations[i],
-                                                 style=style, norm_cfg=norm_cfg))
+                                                 style=style, norm_cfg=norm_cfg, dcn=stage_dcn))
             inplanes = planes * block.expansion
             self.res_layers.append(name)
         self.feat_dim = block.expansion * 64 * 2 ** (len(self.stage_blocks) - 1)
@@ -321,6 +354,11 @@ class ResNet(nn.Module, PackedMixin):
             elif isinstance(m, nn.BatchNorm2d):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
+        if self.dcn is not None:   # resnet.py:507-511: a deformable conv starts as the plain conv (zero offsets; modulated: mask 0.5)
+            for m in self.modules():
+                if isinstance(m, Bottleneck) and m.with_dcn:
+                    nn.init.constant_(m.conv2_offset.weight, 0)
+                    nn.init.constant_(m.conv2_offset.bias, 0)
         if self.zero_init_residual:
             for m in self.modules():
                 if isinstance(m, Bottleneck):
@@ -367,7 +405,7 @@ class ResNet(nn.Module, PackedMixin):
             return False
         blocks, nxt = getattr(self, self.res_layers[i]), getattr(self, self.res_layers[i + 1])[0]
         last, ds = blocks[-1], nxt.downsample
-        if len(blocks) < 2 or last.downsample is not None or last.stride != 1:
+        if len(blocks) < 2 or last.downsample is not None or last.stride != 1 or last.with_dcn:
             return False
         return (nxt.style == 'caffe' and nxt.conv1_stride == 2 and nxt.conv2_stride == 1 and nxt.conv1.kernel_size == (1, 1)
                 and ds is not None and ds[0].kernel_size == (1, 1) and ds[0].stride == (2, 2))
@@ -446,8 +484,7 @@ class ResLayer(nn.Module, PackedMixin):
     def __init__(self, depth, stage=3, stride=2, dilation=1, style='pytorch', norm_cfg=dict(type='BN', requires_grad=True),
                  norm_eval=True, with_cp=False, external_conv=False, dcn=None):
         super(ResLayer, self).__init__()
-        if dcn is not None:
-            raise NotImplementedError('dcn is outside the HVR hot path')
+        self.dcn = dcn
         self.norm_eval, self.norm_cfg, self.stage, self.external_conv = norm_eval, norm_cfg, stage, external_conv
         self.fp16_enabled = False
         stage_block = ARCH_SETTINGS[depth][stage]
@@ -455,7 +492,7 @@ class ResLayer(nn.Module, PackedMixin):
         inplanes = 64 * 2 ** (stage - 1) * Bottleneck.expansion
         self.add_module('layer{}'.format(stage + 1),
                         make_res_layer(Bottleneck, inplanes, planes, stage_block, stride=stride, dilation=dilation, style=style,
-                                       norm_cfg=norm_cfg))
+                                       norm_cfg=norm_cfg, dcn=dcn))
         if external_conv:
             # ConvModule(2048, 256, 1): conv + bias + ReLU, parameters under new_layer_1.conv.*
             self.new_layer_1 = nn.Module()

@@ -66,6 +66,8 @@ hipError_t run_det_decode(const float*, int, int, int, int, const float*, int, c
 hipError_t run_roi_align_fwd(const void*, const float*, void*, int, int, int, int, int, int, int, float, int, int, int,
                              hipStream_t);
 hipError_t run_roi_align_bwd(const float*, const float*, float*, int, int, int, int, int, int, float, int, int, hipStream_t);
+hipError_t run_deform_im2col(const void*, const float*, void*, int, int, int, int, int, int, int, int, int, int, int, int, long, int, int,
+                             hipStream_t);
 size_t nms_workspace_bytes(int P, int n);
 hipError_t run_nms_batched(const float*, int, int, float, int, int, int, long long*, int*, void*, hipStream_t, int band = 0,
                            int* band_done = nullptr);
@@ -1278,6 +1280,37 @@ int hvr_roi_align_bwd(const float* grad_out, const float* rois, float* grad_feat
   return check_launch(run_roi_align_bwd(grad_out, rois, grad_feat, C, H, W, K, PH, PW, spatial_scale, sample_num, layout,
                                         (hipStream_t)stream),
                       "hvr_roi_align_bwd");
+}
+
+// ---- deformable im2col (dcn.hip) ----
+int hvr_deform_im2col_supported(int Cin, int deformable_groups, int dtype) {
+  if (!valid_dtype(dtype) || Cin <= 0 || deformable_groups <= 0) return 0;
+  return Cin % kstep_elems(dtype) == 0 && Cin % deformable_groups == 0 && (Cin / deformable_groups) % 8 == 0;
+}
+
+int hvr_deform_im2col(const void* x, const float* om, void* col, int B, int H, int W, int Cin, int KH, int KW, int stride, int pad, int dil,
+                      int deformable_groups, int modulated, int64_t ldo, int dtype, void* stream) {
+  if (!valid_dtype(dtype)) return fail(HVR_EINVAL, "hvr_deform_im2col: bad dtype %d", dtype);
+  if (!x || !om || !col) return fail(HVR_EINVAL, "hvr_deform_im2col: null pointer");
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || dil <= 0 || deformable_groups <= 0)
+    return fail(HVR_EINVAL, "hvr_deform_im2col: bad shape B=%d H=%d W=%d Cin=%d k=%dx%d stride=%d pad=%d dil=%d groups=%d", B, H, W, Cin, KH, KW,
+                stride, pad, dil, deformable_groups);
+  if (Cin % kstep_elems(dtype)) return fail(HVR_EINVAL, "hvr_deform_im2col: Cin=%d is not a multiple of the %d-element K-step", Cin, kstep_elems(dtype));
+  if (Cin % deformable_groups || (Cin / deformable_groups) % 8)
+    return fail(HVR_EINVAL, "hvr_deform_im2col: Cin=%d over %d deformable groups is not a multiple of 8 channels per group", Cin, deformable_groups);
+  const long OH = ((long)H + 2L * pad - (long)dil * (KH - 1) - 1) / stride + 1, OW = ((long)W + 2L * pad - (long)dil * (KW - 1) - 1) / stride + 1;
+  if ((long)H + 2L * pad - (long)dil * (KH - 1) - 1 < 0 || (long)W + 2L * pad - (long)dil * (KW - 1) - 1 < 0)
+    return fail(HVR_EINVAL, "hvr_deform_im2col: empty output");
+  const long need = (long)(modulated ? 3 : 2) * deformable_groups * KH * KW;
+  if (ldo < need) return fail(HVR_EINVAL, "hvr_deform_im2col: ldo=%ld is below the %ld offset%s channels", (long)ldo, need, modulated ? " + mask" : "");
+  if (dtype == HVR_F16S ? (!aligned128(x) || !aligned128(col)) : (!aligned16(x) || !aligned16(col)))
+    return fail(HVR_EINVAL, "hvr_deform_im2col: x and col must be 16-byte (split half: 128-byte) aligned");
+  if ((reinterpret_cast<uintptr_t>(om) & 3) != 0) return fail(HVR_EINVAL, "hvr_deform_im2col: om must be 4-byte aligned");
+  const long M = (long)B * OH * OW;
+  if (M > 0x7fffffffL || (long)KH * KW > 4096) return fail(HVR_EUNSUPPORTED, "hvr_deform_im2col: too many output pixels or taps");
+  return check_launch(run_deform_im2col(x, om, col, B, H, W, Cin, (int)OH, (int)OW, KH, KW, stride, pad, dil, deformable_groups, (long)ldo,
+                                        modulated != 0, dtype, (hipStream_t)stream),
+                      "hvr_deform_im2col");
 }
 
 // ---- NMS ----

@@ -158,6 +158,8 @@ SYMBOLS = {
     'hvr_mining_argreduce': (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp]),
     'hvr_roi_align_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp]),
     'hvr_roi_align_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
+    'hvr_deform_im2col_supported': (_i, [_i, _i, _i]),
+    'hvr_deform_im2col': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i, _vp]),
     'hvr_nms_workspace_bytes': (_sz, [_i]),
     'hvr_nms_first': (_i, [_vp, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'hvr_nms': (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -1248,6 +1250,70 @@ def roi_align_bwd(grad_out, rois, feat_shape, spatial_scale, sample_num, layout)
     _check(lib().hvr_roi_align_bwd(_ptr(grad_out), _ptr(rois), _ptr(grad_in), B, C, H, W, K, PH, PW, float(spatial_scale),
                                    int(sample_num), layout, _stream()), 'hvr_roi_align_bwd')
     return grad_in
+
+
+def _deform_out_hw(H, W, KH, KW, stride, pad, dil):
+    return (H + 2 * pad - dil * (KH - 1) - 1) // stride + 1, (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1
+
+
+def deform_im2col(x, om, KH, KW, stride, pad, dil, deformable_groups, modulated, out=None):
+    """The sampler of a (modulated) deformable conv (hvr_deform_im2col): x [B,H,W,Cin] physical NHWC in an operand dtype,
+    om [B,OH,OW,ldo] f32 = the raw output of the offset conv (offsets, then mask logits when modulated; ldo may exceed the
+    channel count) -> col [B*OH*OW, KH*KW*Cin] of x's dtype, K order [kh][kw][cin].  out: a contiguous tensor of that shape
+    to write into."""
+    _need_cuda(x, om)
+    B, H, W, Cin = x.shape
+    OH, OW = _deform_out_hw(H, W, KH, KW, stride, pad, dil)
+    assert x.is_contiguous() and om.dtype == torch.float32 and om.is_contiguous() and tuple(om.shape[:3]) == (B, OH, OW), \
+        (tuple(x.shape), tuple(om.shape), (B, OH, OW))
+    M, K = B * OH * OW, KH * KW * Cin
+    if out is None:
+        out = torch.empty((M, K), dtype=x.dtype, device=x.device)
+    else:
+        assert tuple(out.shape) == (M, K) and out.dtype == x.dtype and out.is_contiguous() and out.device == x.device, (tuple(out.shape), (M, K))
+    # bytes: four corner vectors read and one written per (pixel, tap), the offsets once per pixel
+    with _span('deform_im2col', float(5 * M * K * x.element_size() + M * om.shape[3] * 4)):
+        _check(lib().hvr_deform_im2col(_ptr(x), _ptr(om), _ptr(out), B, H, W, Cin, KH, KW, int(stride), int(pad), int(dil),
+                                       int(deformable_groups), int(bool(modulated)), om.shape[3], _dt(x), _stream()), 'hvr_deform_im2col')
+    return out
+
+
+# Rows of col (output pixels) one sampler + GEMM round of deform_conv2d_nhwc handles, rounded down to whole frames (one frame at
+# least): the col scratch stays at about DEFORM_CHUNK_ROWS * 9 * Cin elements however many frames a call carries.  Measured
+# (DESIGN.md 8f, profiles/dcn_bench.txt): 60 frames of 38 x 63 cost the same within 8 % for chunks of 15, 30 or 60 frames and 1.2 - 1.4 x
+# as much in chunks of 4; 36 864 rows keep a 15-frame window of that size (35 910 rows) in one chunk.
+DEFORM_CHUNK_ROWS = 36864
+
+
+def deform_conv2d_nhwc(x, om, w, bias, relu, stride, pad, dil, deformable_groups, modulated, out=None, chunk_rows=None):
+    """act(deformable conv of x [B,H,W,Cin] with w [Cout,KH,KW,Cin] (the packed layout of conv2d_nhwc) + bias) -> [B,OH,OW,Cout]:
+    the sampler (deform_im2col) and the unchanged GEMM, over chunks of whole frames that share one per-stream col scratch.
+    A chunk is a set of whole rows of the GEMM's M and the few-row K-sliced route (fewrow_split) is kept off inside, so every
+    output row is the same sum whatever the chunking: chunked == unchunked bit for bit.  chunk_rows: None = DEFORM_CHUNK_ROWS,
+    0 = one chunk (as few as keep col below the product's 2 GiB operand limit)."""
+    _need_cuda(x, om, w, bias)
+    B, H, W, Cin = x.shape
+    Cout, KH, KW, _ = w.shape
+    OH, OW = _deform_out_hw(H, W, KH, KW, stride, pad, dil)
+    if out is None:
+        out = torch.empty((B, OH, OW, Cout), dtype=x.dtype, device=x.device)
+    else:
+        assert tuple(out.shape) == (B, OH, OW, Cout) and out.dtype == x.dtype and out.is_contiguous() and out.device == x.device
+    rows = DEFORM_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)
+    K = KH * KW * Cin
+    fpc = B if rows <= 0 else max(1, min(B, rows // (OH * OW)))   # frames per chunk
+    fpc = max(1, min(fpc, (2 ** 31 - 1) // (OH * OW * K * x.element_size())))   # (hvr_gemm takes operands below 2 GiB)
+    ws = _workspace(fpc * OH * OW * K * x.element_size(), x.device, 'deform_col')
+    w2 = w.reshape(Cout, K)
+    y2 = out.view(B * OH * OW, Cout)
+    with fewrow_split(False):
+        for b0 in range(0, B, fpc):
+            nb = min(fpc, B - b0)
+            m = nb * OH * OW
+            col = ws[:m * K * x.element_size()].view(x.dtype).view(m, K)
+            deform_im2col(x[b0:b0 + nb], om[b0:b0 + nb], KH, KW, stride, pad, dil, deformable_groups, modulated, out=col)
+            gemm(col, w2, bias, relu=relu, out=y2[b0 * OH * OW:b0 * OH * OW + m])
+    return out
 
 
 def nms_first(dets, iou_thr, max_keep, ge_semantics=True):

@@ -357,6 +357,27 @@ int hvr_roi_align_bwd(const float* grad_out, const float* rois, float* grad_feat
                       int K, int PH, int PW, float spatial_scale, int sample_num, int layout, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Deformable im2col: the sampler of a deformable convolution (DCN v1) / modulated deformable convolution (v2), forward only.
+ * Replaces mmdet/ops/dcn/src/deform_conv_cuda_kernel.cu:63-114 (bilinear rule), :190-242 (deformable_im2col_gpu_kernel)
+ * and :570-640 (modulated_deformable_im2col_gpu_kernel).
+ *   x   [B][H][W][Cin]      physical NHWC, operand format `dtype` (split half: the container, activations as stored)
+ *   om  [B][OH][OW][ldo]    f32, the raw output of the offset conv, pixel-major, ldo >= (modulated ? 3 : 2) * dg * KH * KW:
+ *                           group g, tap k = kh * KW + kw: off_h = om[g*2*KH*KW + 2k], off_w = om[g*2*KH*KW + 2k + 1],
+ *                           mask logit (modulated) = om[2*dg*KH*KW + g*KH*KW + k]; the mask is its sigmoid
+ *   col [B*OH*OW][KH*KW*Cin] `dtype`, K order [kh][kw][cin] -- the order of packed conv weights [Cout][KH][KW][Cin], so the
+ *                           deformable conv is hvr_gemm(col, w) with the usual epilogue.  The caller allocates it.
+ * OH = (H + 2 pad - dil (KH-1) - 1) / stride + 1, OW alike.  Channel c belongs to group c / (Cin / dg).
+ * Sample position h = float(oy*stride - pad + kh*dil) + off_h (one f32 add), w alike; the sample is 0 unless h > -1, w > -1,
+ * h < H, w < W; else bilinear over floor and floor + 1, a corner outside the map contributing 0 (no edge clamp, unlike
+ * RoIAlign); times the mask when modulated.  Interpolated in f32, rounded once to `dtype`.
+ * Cin % K-step == 0 (32: f32 / split half, 64: bf16 / half) and (Cin / dg) % 8 == 0, x / col 16-byte (split half: 128-byte)
+ * aligned, else HVR_EINVAL; hvr_deform_im2col_supported answers 1 / 0 for those shape rules.  No host synchronisation.
+ * ---------------------------------------------------------------------------------- */
+int hvr_deform_im2col_supported(int Cin, int deformable_groups, int dtype);
+int hvr_deform_im2col(const void* x, const float* om, void* col, int B, int H, int W, int Cin, int KH, int KW, int stride, int pad,
+                      int dil, int deformable_groups, int modulated, int64_t ldo, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Greedy NMS.  Replaces nms_cpu.nms / nms_cuda.nms (mmdet/ops/nms/src/nms_cpu.cpp:5-71,
  * nms_kernel.cu:24-136) with no host round trip.  dets [n][5] f32 (x1,y1,x2,y2,score);
  * ge_semantics != 0 suppresses at IoU >= thr (the CPU reference), 0 at IoU > thr (the CUDA
