@@ -1216,19 +1216,24 @@ def det_loss_sampled(logits, cls_off, reg_off, ncls, labels, label_weights, bbox
     return out3, dlogits
 
 
-def roi_align_fwd(feat, rois, out_h, out_w, spatial_scale, sample_num, layout):
-    """layout NCHW: feat [B,C,H,W] -> [K,C,oh,ow]; NHWC: feat [B,H,W,C] -> [K,oh,ow,C] (physical shapes)."""
+def roi_align_fwd(feat, rois, out_h, out_w, spatial_scale, sample_num, layout, out=None):
+    """layout NCHW: feat [B,C,H,W] -> [K,C,oh,ow]; NHWC: feat [B,H,W,C] -> [K,oh,ow,C] (physical shapes).
+    out: a contiguous tensor of that shape and feat's dtype to write into (not for split-half maps)."""
     _need_cuda(feat, rois)
     if feat.dtype == SPLIT:   # interpolated in f32, handed back in the split format
+        assert out is None
         return cast(roi_align_fwd(cast(feat, torch.float32), rois, out_h, out_w, spatial_scale, sample_num, layout), SPLIT)
     rois = rois.contiguous().float()
     K = rois.shape[0]
     if layout == LAYOUT_NCHW:
         B, C, H, W = feat.shape
-        out = torch.empty((K, C, out_h, out_w), dtype=feat.dtype, device=feat.device)
+        shape = (K, C, out_h, out_w)
     else:
         B, H, W, C = feat.shape
-        out = torch.empty((K, out_h, out_w, C), dtype=feat.dtype, device=feat.device)
+        shape = (K, out_h, out_w, C)
+    if out is None:
+        out = torch.empty(shape, dtype=feat.dtype, device=feat.device)
+    assert tuple(out.shape) == shape and out.dtype == feat.dtype and out.device == feat.device and out.is_contiguous()
     assert feat.is_contiguous()
     with _span('roi_align', float((feat.numel() + out.numel()) * feat.element_size() + rois.numel() * 4)):
         _check(lib().hvr_roi_align_fwd(_ptr(feat), _ptr(rois), _ptr(out), B, C, H, W, K, out_h, out_w, float(spatial_scale),
