@@ -41,7 +41,7 @@ hipError_t run_det_loss(const float*, int, int, int, int, const long long*, cons
 size_t assign_workspace_bytes(int n, int k);
 hipError_t run_max_iou_assign(const float*, int, int, const float*, int, const uint8_t*, float, float, float, float, long long*, float*,
                               void*, hipStream_t);
-hipError_t run_sample(const long long*, const float*, int, int, int, float, long long*, int*, hipStream_t);
+hipError_t run_sample(const long long*, const float*, int, int, int, double, long long*, int*, hipStream_t);
 hipError_t run_box_targets(const float*, int, int, const float*, const long long*, const long long*, const long long*, const int*, int,
                            const float*, const float*, float, int, long long*, float*, float*, float*, hipStream_t);
 hipError_t run_rpn_loss(const float*, int, int, int, const long long*, const float*, const float*, const float*, const int*, float, float*,
@@ -117,7 +117,7 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 
 extern "C" {
 
-int hvr_abi_version(void) { return 6; }  // 2: hvr_gemm_desc / hvr_conv_desc carry the few-row split-K scratch (ws, ws_bytes); 3: HVR_F16 / HVR_F16S; 4: hvr_tail_next_desc carries alpha / beta
+int hvr_abi_version(void) { return 7; }  // 2: hvr_gemm_desc / hvr_conv_desc carry the few-row split-K scratch (ws, ws_bytes); 3: HVR_F16 / HVR_F16S; 4: hvr_tail_next_desc carries alpha / beta; 5: hvr_relation_fwd_grouped; 6: hvr_gemm_splitk_batched / hvr_unpack_conv_wgrads_multi; 7: hvr_sample_pos_neg takes neg_pos_ub as a double
 const char* hvr_last_error(void) { return g_err.c_str(); }
 
 static int fill_linear(GemmParams& p, const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb,
@@ -1129,7 +1129,7 @@ int hvr_max_iou_assign(const float* boxes, int ldb, int n, const float* gts, int
                       "hvr_max_iou_assign");
 }
 
-int hvr_sample_pos_neg(const int64_t* cls, const float* keys, int n, int num, int num_expected_pos, float neg_pos_ub, int64_t* inds,
+int hvr_sample_pos_neg(const int64_t* cls, const float* keys, int n, int num, int num_expected_pos, double neg_pos_ub, int64_t* inds,
                        int32_t* counts, void* stream) {
   if (!cls || !keys || !inds || !counts) return fail(HVR_EINVAL, "null pointer");
   if (n <= 0 || num <= 0 || num_expected_pos < 0 || num_expected_pos > num) return fail(HVR_EINVAL, "bad sampler sizes");

@@ -90,11 +90,15 @@ __global__ __launch_bounds__(256) void assign_final_kernel(const float* __restri
 // sampler: one workgroup.  Group "pos" = cls > 0, "neg" = cls == 0.  From each group the `expected` members with the
 // smallest keys are taken (all of them when the group is not larger), ties by lower index; output in ascending index
 // order, positives first -- SamplingResult.bboxes' order after the reference's `.unique()` (base_sampler.py:62-75).
+// Keys compare NUMERICALLY: -0.0 and +0.0 tie (as in the reference's topk), +-inf are ordinary values.  NaN keys are
+// unspecified.  The negatives' cap is int(neg_pos_ub * max(1, np)) evaluated in double on the caller's double, the
+// reference's own Python arithmetic (base_sampler.py:70): an f32 product rounds to the other side of an integer for
+// ordinary values (0.29 x 100, 1.16 x 25, 0.21 x 300).
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
 __device__ __forceinline__ unsigned key_order(float f) {
-  const unsigned u = __float_as_uint(f);
+  const unsigned u = f == 0.f ? 0u : __float_as_uint(f);   // -0.0 ranks with +0.0
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -215,13 +219,13 @@ __device__ int sample_group(const long long* cls, const float* keys, int n, bool
 }  // namespace
 
 __global__ __launch_bounds__(1024) void sample_kernel(const long long* __restrict__ cls, const float* __restrict__ keys, int n, int num,
-                                                      int expected_pos, float neg_pos_ub, long long* __restrict__ inds,
+                                                      int expected_pos, double neg_pos_ub, long long* __restrict__ inds,
                                                       int* __restrict__ counts) {
   __shared__ SampleShared sh;
   const int np = sample_group(cls, keys, n, true, expected_pos, inds, sh);
   int expected_neg = num - np;
-  if (neg_pos_ub >= 0.f) {
-    const int ub = (int)(neg_pos_ub * (float)max(1, np));
+  if (neg_pos_ub >= 0.0) {
+    const int ub = (int)fmin(neg_pos_ub * (double)max(1, np), 2147483647.0);   // (a cap beyond int is no cap)
     expected_neg = min(expected_neg, ub);
   }
   const int nn = sample_group(cls, keys, n, false, expected_neg, inds + np, sh);
@@ -325,7 +329,9 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
 //   out[r][1] = argmin over keys with the row's label                 (`inds_for_pos_nsm`, topk(1, largest=False))
 //   out[r][2..3] = the two largest among keys whose label differs     (`inds_for_bg`, topk(2); used for label-0 rows)
 // Masked-out keys count as -inf (+inf for the minimum), ties go to the lower index: a row without candidates answers 0
-// (0, 1 for the pair).  One wavefront per row.
+// (0, 1 for the pair); a row with one candidate has the lowest other index as its second pick (0 when Mk == 1).  +-inf
+// affinities are ordinary values.  NaN affinities are unspecified: no comparison here ever selects one, whereas the
+// reference's topk ranks NaN highest.  One wavefront per row.
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -487,7 +493,7 @@ hipError_t run_max_iou_assign(const float* boxes, int ldb, int n, const float* g
   return hipGetLastError();
 }
 
-hipError_t run_sample(const long long* cls, const float* keys, int n, int num, int expected_pos, float neg_pos_ub, long long* inds,
+hipError_t run_sample(const long long* cls, const float* keys, int n, int num, int expected_pos, double neg_pos_ub, long long* inds,
                       int* counts, hipStream_t s) {
   hipLaunchKernelGGL(sample_kernel, dim3(1), dim3(1024), 0, s, cls, keys, n, num, expected_pos, neg_pos_ub, inds, counts);
   return hipGetLastError();

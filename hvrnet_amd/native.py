@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(_HERE, 'libhvr_hip.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'hvr_hip.h')
 
 HVR_F32, HVR_BF16, HVR_F16, HVR_F16S = 0, 1, 2, 3
-ABI_VERSION = 6
+ABI_VERSION = 7
 # Split-half tensors (HVR_F16S, include/hvr_hip.h: [32 hi | 32 lo] half groups, 4 bytes per logical element) travel through
 # torch as int32 tensors of the LOGICAL shape: element size, strides, row / 32-column slicing, cat, clone and zeros all mean
 # the right thing on the container, and nothing but this library ever interprets the bytes.  `SPLIT` is the dtype sentinel
@@ -144,7 +144,7 @@ SYMBOLS = {
     'hvr_det_loss_sampled': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp]),
     'hvr_max_iou_assign_workspace_bytes': (_sz, [_i, _i]),
     'hvr_max_iou_assign': (_i, [_vp, _i, _i, _vp, _i, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _sz, _vp]),
-    'hvr_sample_pos_neg': (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    'hvr_sample_pos_neg': (_i, [_vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp]),
     'hvr_box_targets': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     'hvr_rpn_loss': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     'hvr_ce_rows': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
@@ -1040,7 +1040,10 @@ def max_iou_assign(boxes, gts, pos_iou_thr, neg_iou_thr, min_pos_iou, valid=None
 
 
 def sample_pos_neg(cls, keys, num, num_expected_pos, neg_pos_ub=-1.0):
-    """cls int64 [n] (>0 positive, ==0 negative), keys f32 [n] -> (inds int64 [num]: positives then negatives, counts int32 [2])."""
+    """cls int64 [n] (>0 positive, ==0 negative), keys f32 [n] -> (inds int64 [num]: positives then negatives, counts int32 [2]).
+    The smallest keys win, compared numerically (-0.0 ties with +0.0; ties go to the lower index; +-inf are ordinary values);
+    NaN keys are unspecified.  Rows of inds behind counts[0] + counts[1] are left unwritten.  neg_pos_ub >= 0 caps the negatives
+    at int(neg_pos_ub * max(1, counts[0])), evaluated in double on this Python float (base_sampler.py:70)."""
     _need_cuda(cls, keys)
     assert cls.dtype == torch.long and cls.is_contiguous() and keys.dtype == torch.float32 and keys.is_contiguous()
     assert cls.numel() == keys.numel()
@@ -1191,7 +1194,10 @@ def merge_aug_dets(boxes, scores, img_w, scale_factor, flip):
 
 def mining_argreduce(aff, labels, all_labels):
     """aff f32 [Mq, Mk] (row stride >= Mk), labels int64 [Mq], all_labels int64 [Mk] -> int64 [Mq, 4]:
-    (argmax over different-label keys, argmin over same-label keys, top-2 over different-label keys)."""
+    (argmax over different-label keys, argmin over same-label keys, top-2 over different-label keys).
+    Ties go to the lower index; a row without candidates answers 0 (0, 1 for the pair), a row with one candidate the lowest
+    other index as its second pick (0 when Mk == 1).  +-inf affinities are ordinary values.  NaN affinities are unspecified: the
+    kernel never selects one, whereas the reference's topk ranks NaN highest."""
     _need_cuda(aff, labels, all_labels)
     assert aff.dtype == torch.float32 and aff.dim() == 2 and aff.stride(1) == 1
     assert labels.dtype == torch.long and all_labels.dtype == torch.long

@@ -69,7 +69,7 @@ extern "C" {
 #define HVR_LAYOUT_NCHW 0 /* reference layout */
 #define HVR_LAYOUT_NHWC 1 /* native layout of this library */
 
-int hvr_abi_version(void);   /* 2 since the descriptors of hvr_gemm / hvr_conv2d_nhwc grew the split-K scratch fields; 3: HVR_F16 / HVR_F16S; 4: hvr_tail_next_desc carries alpha / beta (split-half operands); 5: hvr_relation_fwd_grouped; 6: hvr_gemm_splitk_batched / hvr_unpack_conv_wgrads_multi */
+int hvr_abi_version(void);   /* 2 since the descriptors of hvr_gemm / hvr_conv2d_nhwc grew the split-K scratch fields; 3: HVR_F16 / HVR_F16S; 4: hvr_tail_next_desc carries alpha / beta (split-half operands); 5: hvr_relation_fwd_grouped; 6: hvr_gemm_splitk_batched / hvr_unpack_conv_wgrads_multi; 7: hvr_sample_pos_neg takes neg_pos_ub as a double */
 const char* hvr_last_error(void);
 
 /* ------------------------------------------------------------------------------------
@@ -544,6 +544,11 @@ int hvr_transpose_pad(const void* in, void* out, int R, int C, int64_t ldx, int6
  *                        (random_sampler.py:37-53 shuffles on the host instead), OHEMHNLSampler.get_ohem_weights =
  *                        keys -loss (ohem_hnl_sampler.py:50-113).  inds[0..counts[0]) positives, then counts[1]
  *                        negatives, each ascending -- SamplingResult's order (sampling_result.py:9-12 after .unique()).
+ *                        Keys compare numerically (-0.0 ties with +0.0, +-inf are ordinary values); NaN keys are
+ *                        unspecified.  Rows of inds behind counts[0] + counts[1] are not written.  neg_pos_ub < 0: no
+ *                        cap; otherwise at most int(neg_pos_ub * max(1, counts[0])) negatives, the product taken in
+ *                        double on the caller's double as base_sampler.py:70 takes it (a float argument would round
+ *                        0.29 x 100 up to 29 where the reference gets 28).
  *   hvr_box_targets    : regression / classification targets of the sampled boxes (transforms.py:6-31 bbox2delta).
  *                        scatter = 1: [n]-row outputs, row inds[j]  (anchor_target.py:121-155 after `unmap`);
  *                        scatter = 0: [num]-row outputs, row j      (bbox_target.py:35-62).  gt_labels null: label 1.
@@ -561,7 +566,7 @@ size_t hvr_max_iou_assign_workspace_bytes(int n, int k);
 int hvr_max_iou_assign(const float* boxes, int ldb, int n, const float* gts, int k, const uint8_t* valid, float pos_iou_thr,
                        float neg_iou_lo, float neg_iou_hi, float min_pos_iou, int64_t* gt_inds, float* max_overlaps, void* ws,
                        size_t ws_bytes, void* stream);
-int hvr_sample_pos_neg(const int64_t* cls, const float* keys, int n, int num, int num_expected_pos, float neg_pos_ub, int64_t* inds,
+int hvr_sample_pos_neg(const int64_t* cls, const float* keys, int n, int num, int num_expected_pos, double neg_pos_ub, int64_t* inds,
                        int32_t* counts, void* stream);
 int hvr_box_targets(const float* boxes, int ldb, int n, const float* gts, const int64_t* gt_labels, const int64_t* gt_inds,
                     const int64_t* inds, const int32_t* counts, int num, const float* means4, const float* stds4, float pos_weight,
@@ -574,7 +579,9 @@ int hvr_ce_rows(const float* logits, int ldl, int cls_off, int ncls, const int64
  *   out4[r][0] argmax over keys with a different label  (the reference's masked_fill(-inf) + topk(1), `inds_for_pos_sm`)
  *   out4[r][1] argmin over keys with the same label     (masked_fill(+inf) + topk(1, largest=False), `inds_for_pos_nsm`)
  *   out4[r][2], out4[r][3] the two largest among keys with a different label (topk(2), `inds_for_bg`, used for label-0 rows)
- * ties to the lower index; a row without candidates gets index 0 (0, 1). */
+ * ties to the lower index; a row without candidates gets index 0 (0, 1); a row with one candidate gets the lowest other index as
+ * its second pick (0 when Mk == 1).  +-inf affinities are ordinary values.  NaN affinities are unspecified: the kernel never selects
+ * one, whereas the reference's topk ranks NaN highest. */
 /* STAND-IN for the triplet loss over the mined triples: the reference calls TripletNonLocalLoss(margin).compute_loss(q, k, labels,
  * [anchor_idx, pos_idx, neg_idx]) (hrnmp_bbox_head.py:555-561) from a pytorch_metric_learning fork that is NOT in the reference tree.
  * This is the library's published TripletMarginLoss with anchors from q and positives / negatives from k:

@@ -170,7 +170,7 @@ def test_new_exports_are_declared_bound_and_present():
         assert re.search(r'\b%s\(' % sym, capi), '%s is not defined in capi.hip' % sym
         assert sym in native.SYMBOLS, '%s is not bound in native.py' % sym
         assert hasattr(native.lib(), sym)
-    assert native.ABI_VERSION == native.lib().hvr_abi_version() == 6           # additions only
+    assert native.ABI_VERSION == native.lib().hvr_abi_version() == 7           # 7: hvr_sample_pos_neg's neg_pos_ub is a double
     assert callable(native.seq_nms_batched) and hvrnet_amd.seq_nms is ops.seq_nms
     ws, wsb = native.lib().hvr_seq_nms_workspace_bytes, native.lib().hvr_seq_nms_batched_workspace_bytes
     assert wsb(1, 60, 300, 31, 0) == ws(60, 300, 31)                           # the P = 1, no-tubes case is today's call

@@ -139,7 +139,7 @@ def test_new_exports_are_declared_bound_and_present():
         assert re.search(r'\b%s\(' % sym, capi), '%s is not defined in capi.hip' % sym
         assert sym in native.SYMBOLS, '%s is not bound in native.py' % sym
         assert hasattr(native.lib(), sym)
-    assert native.ABI_VERSION == native.lib().hvr_abi_version() == 6          # additions only
+    assert native.ABI_VERSION == native.lib().hvr_abi_version() == 7          # 7: hvr_sample_pos_neg's neg_pos_ub is a double
     assert native.SYMBOLS['hvr_ingest_frame'] == (native._i, [native._vp, native._i, native._i, native._i64, native._vp, native._i, native._i,
                                                               native._i, native._i, native._vp, native._vp, native._i, native._vp])
     for name in ('bbox_flip', 'bbox_mapping', 'bbox_mapping_back', 'merge_aug_proposals', 'merge_aug_bboxes', 'merge_aug_scores',
