@@ -194,12 +194,15 @@ class Bottleneck(nn.Module, PackedMixin):
                          (p['c3'][1] + p['ds'][1]).contiguous())
         return p
 
-    def forward_nhwc(self, x, out=None, h1=None, nxt=None, compact_in=False):
+    def forward_nhwc(self, x, out=None, h1=None, nxt=None, compact_in=False, live_stride=None):
         """out: where the block's output goes (a contiguous [B,OH,OW,4*planes] tensor), e.g. a frame group's slice of a map.
         h1: this block's conv1 output, when the previous block's tail already computed it.  nxt: the block that consumes
         this one's output; the return value is then (y, h1 of nxt or None) -- nxt's conv1 rides on this block's tail when
         hvr_bottleneck_tail_next has a kernel for the shapes.  compact_in (a caffe-style stride-2 block only): x already holds
-        only the pixels this block's strided 1x1 convs read (forward_sampled_nhwc of the block before), so they run at stride 1."""
+        only the pixels this block's strided 1x1 convs read (forward_sampled_nhwc of the block before), so they run at stride 1.
+        live_stride (with nxt, an identity block): nothing but nxt's conv1 and a stride-`live_stride` consumer reads this block's output
+        (the block before the last of a stage that ends compact); where hvr_bottleneck_tail_next_live has a kernel the return value is
+        (y_live, h1 of nxt) with y_live [B,(H-1)//s+1,(W-1)//s+1,4*planes] = the output at [:, ::s, ::s], otherwise as without it."""
         p = self.packed(x.device)
         dst = out
         stride, conv1_stride = (1, 1) if compact_in else (self.stride, self.conv1_stride)
@@ -228,6 +231,8 @@ class Bottleneck(nn.Module, PackedMixin):
                     return y, None
             else:
                 args = (out, None, x, p['c3'][0].reshape(p['c3'][0].shape[0], -1), p['c3'][1], 1)
+                if live_stride is not None and dst is None and native.bottleneck_tail_next_live_supported(out, x, args[3], args[4], wn, bn, live_stride):
+                    return native.bottleneck_tail_next_live(out, x, args[3], args[4], wn, bn, live_stride=live_stride)
             if args is not None and native.bottleneck_tail_next_supported(*args, wn, bn):
                 return native.bottleneck_tail_next(args[0], args[1], args[2], args[3], args[4], wn, bn, stride2=args[5], out=dst)
         y = self._tail(x, out, p, dst, stride)
@@ -242,13 +247,25 @@ class Bottleneck(nn.Module, PackedMixin):
             identity = native.conv2d_nhwc(x, p['ds'][0], p['ds'][1], relu=False, stride=stride)
         return native.conv2d_nhwc(out, p['c3'][0], p['c3'][1], resid=identity, relu=True, out=dst)
 
-    def forward_sampled_nhwc(self, x, h1=None, stride=2):
+    def forward_sampled_nhwc(self, x, h1=None, stride=2, resid_compact=None, plain_close=False):
         """An identity block whose output only a stride-`stride` 1x1 consumer reads (the last block of a stage in front of a
         caffe-style stage, resnet.py:127-132): conv1 everywhere (the 3x3 reads neighbours), conv2 as a stride-`stride` 3x3, and the
         closing 1x1 on those pixels with the residual sampled from x (hvr_bottleneck_close_sampled).  -> (y, True) with
         y [B,(H-1)//stride+1,(W-1)//stride+1,4*planes] = the full-resolution output at [:, ::stride, ::stride] bit for bit, or
-        (the full-resolution output, False) where the sampled close has no kernel for the dtype / shape."""
+        (the full-resolution output, False) where the sampled close has no kernel for the dtype / shape.
+        resid_compact (with h1; x is not read and may be None): the block input at [:, ::stride, ::stride] only, as the block before
+        left it (forward_nhwc with live_stride) -- the close is then a dense conv on the compact map: hvr_bottleneck_close_sampled at
+        stride 1, or with plain_close hvr_conv2d_nhwc (the same row-panel kernel and sums either way).  The caller has asked
+        live_close_supported first: there is no full-resolution input to fall back on.  -> (y, True)"""
         assert self.downsample is None and self.stride == 1 and not self.with_dcn
+        if resid_compact is not None:
+            assert h1 is not None and tuple(resid_compact.shape[1:3]) == ((h1.shape[1] - 1) // stride + 1, (h1.shape[2] - 1) // stride + 1)
+            p = self.packed(h1.device)
+            hs = native.conv2d_nhwc(h1, p['c2'][0], p['c2'][1], relu=True, stride=stride, pad=self.dilation, dil=self.dilation)
+            if plain_close:
+                return native.conv2d_nhwc(hs, p['c3'][0], p['c3'][1], resid=resid_compact, relu=True), True
+            w3, b3 = p['c3'][0].reshape(p['c3'][0].shape[0], -1), p['c3'][1]
+            return native.bottleneck_close_sampled(hs, w3, b3, resid_compact, stride=1, relu=True), True
         p = self.packed(x.device)
         h = h1 if h1 is not None else native.conv2d_nhwc(x, p['c1'][0], p['c1'][1], relu=True, stride=1)
         B, H, W, _ = x.shape
@@ -260,6 +277,19 @@ class Bottleneck(nn.Module, PackedMixin):
             return self.forward_nhwc(x, h1=h), False
         native.conv2d_nhwc(h, p['c2'][0], p['c2'][1], relu=True, stride=stride, pad=self.dilation, dil=self.dilation, out=hs)
         return native.bottleneck_close_sampled(hs, w3, b3, x, stride=stride, relu=True), True
+
+    def live_close_supported(self, B, H, W, dtype, stride=2, plain_close=False):
+        """Whether forward_sampled_nhwc(resid_compact=...) can close this block on the compact map of a [B,H,W] input and equal the
+        full-resolution block at [:, ::stride, ::stride] bit for bit: the row-panel kernel takes the close at both sizes (its K order
+        does not depend on the row count), and the compact map has the 128 pixels of one panel."""
+        if self.downsample is not None or self.stride != 1 or self.with_dcn:
+            return False
+        LH, LW = (H - 1) // stride + 1, (W - 1) // stride + 1
+        if B * LH * LW < 128 or native.conv2d_path(B, H, W, self.planes, 4 * self.planes, dtype=dtype, tile=native.TILE_HINT) != 1:
+            return False
+        if plain_close:
+            return native.conv2d_path(B, LH, LW, self.planes, 4 * self.planes, dtype=dtype, tile=native.TILE_HINT) == 1
+        return native.close_sampled_path(B, LH, LW, self.planes, 4 * self.planes, LH, LW, 1, dtype)
 
     fuse_next = True   # class attributes (tests flip them to compare the fused kernels with the per-conv path); no environment switch
     fuse_tail = True
@@ -391,17 +421,38 @@ class ResNet(nn.Module, PackedMixin):
         return (B, h, w, 64 * 2 ** last * 4)
 
     skip_dead_pixels = True   # class attribute (tests flip it to compare with the full-resolution path); no environment switch
-    # Stages that may end compact.  Layer 2 (index 1) qualifies too and is bit-identical as well (tests/test_dead_pixels_gpu.py), but its
-    # closing conv is then the last row-panel conv to leave hvr_conv2d_nhwc in a bf16 window, and the forward-kernel census
-    # (tests/test_forward_kernels_gpu.py) wants that route among the calls it checks against f64: layer 2 stays full by default
+    # Stages that end compact through hvr_bottleneck_close_sampled.  Layer 2 (index 1) qualifies too and is bit-identical as well
+    # (tests/test_dead_pixels_gpu.py), but its closing conv is then the last row-panel conv to leave hvr_conv2d_nhwc in a bf16 window, and
+    # the forward-kernel census (tests/test_forward_kernels_gpu.py) wants that route among the calls it checks against f64: layer 2 is
+    # not listed here and ends compact through live_store_stages instead, with a close that stays on hvr_conv2d_nhwc
     compact_stages = (0,)
+    # Stages whose block before the last writes only the live quarter of its output (hvr_bottleneck_tail_next_live), so that the last block
+    # closes densely on the compact map.  A stage listed here and in compact_stages closes through hvr_bottleneck_close_sampled (stride 1);
+    # a stage listed here alone -- layer 2 -- ends compact only this way and closes through hvr_conv2d_nhwc, the route the census checks
+    live_store_stages = (0, 1)
 
     def _ends_compact(self, i):
+        return i in self.compact_stages and self._dead_pixels(i)
+
+    def _live_store(self, i, blk, last, y):
+        """True when stage i ends compact through the live-store form: blk, the block before the last, is an identity block whose output
+        y-shaped map only `last` reads (conv1 from registers, the residual at the live pixels), both kernels exist for the shapes, and
+        the compact map has at least 128 pixels."""
+        if i not in self.live_store_stages or not self._dead_pixels(i) or not blk.fuse_next:
+            return False
+        if blk.downsample is not None or blk.stride != 1 or blk.with_dcn or last.conv1_stride != 1 or y.dtype not in (torch.bfloat16, torch.float16, native.SPLIT):
+            return False
+        B, H, W, _ = y.shape
+        if not native.tail_next_live_path(B, H, W, blk.planes, 4 * blk.planes, last.planes, 2, y.dtype):
+            return False
+        return last.live_close_supported(B, H, W, y.dtype, 2, plain_close=i not in self.compact_stages)
+
+    def _dead_pixels(self, i):
         """True when nothing reads stage i's output but the stride-2 1x1 convs (conv1 and downsample) of a caffe-style stage i + 1
         (resnet.py:127-132,283-296): three quarters of its pixels are dead, and its last block computes the live quarter only
         (Bottleneck.forward_sampled_nhwc).  Few-row split-K (native.fewrow_split) picks its K slices by the row count, so the
         compact 3x3 would sum in another order than the full one: full resolution there."""
-        if not self.skip_dead_pixels or i not in self.compact_stages or i + 1 >= len(self.res_layers) or i in self.out_indices or native.fewrow_enabled():
+        if not self.skip_dead_pixels or i + 1 >= len(self.res_layers) or i in self.out_indices or native.fewrow_enabled():
             return False
         blocks, nxt = getattr(self, self.res_layers[i]), getattr(self, self.res_layers[i + 1])[0]
         last, ds = blocks[-1], nxt.downsample
@@ -435,10 +486,17 @@ class ResNet(nn.Module, PackedMixin):
             blocks = list(getattr(self, name))
             h1 = None
             compact_in, compact = compact, False   # y holds every second pixel of every second row of the previous stage's output
+            live = False   # y holds the live quarter of the block input only (the block before the last stored nothing else)
             for j, blk in enumerate(blocks):
                 last = out is not None and i == self.out_indices[0] and j == len(blocks) - 1
-                if j + 1 < len(blocks):  # the next block's conv1 rides on this block's tail where a kernel exists
+                if j >= 1 and j + 2 == len(blocks) and self._live_store(i, blk, blocks[j + 1], y):
+                    full_hw = tuple(y.shape[1:3])
+                    y, h1 = blk.forward_nhwc(y, h1=h1, nxt=blocks[j + 1], live_stride=2)
+                    live = tuple(y.shape[1:3]) != full_hw
+                elif j + 1 < len(blocks):  # the next block's conv1 rides on this block's tail where a kernel exists
                     y, h1 = blk.forward_nhwc(y, h1=h1, nxt=blocks[j + 1], compact_in=compact_in and j == 0)
+                elif live:
+                    y, compact = blk.forward_sampled_nhwc(None, h1=h1, resid_compact=y, plain_close=i not in self.compact_stages)
                 elif self._ends_compact(i):
                     y, compact = blk.forward_sampled_nhwc(y, h1=h1)
                 else:

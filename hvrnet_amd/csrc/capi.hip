@@ -523,6 +523,34 @@ int hvr_bottleneck_tail_next(const hvr_tail_next_desc* d, void* stream) {
   return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_tail_next");
 }
 
+// the identity form with only the pixels (s oy, s ox) of y written, as a compact map (expand.hip / expand_split.hip, LIVE)
+static int tail_next_live_params(const hvr_tail_next_live_desc* d, GemmParams& p) {
+  if (!d) return fail(HVR_EINVAL, "null descriptor");
+  const hvr_tail_desc& t = d->next.tail;
+  if (t.C2 != 0) return fail(HVR_EUNSUPPORTED, "hvr_bottleneck_tail_next_live is the identity form (tail.C2 == 0)");
+  if (d->live_stride <= 0) return fail(HVR_EINVAL, "live_stride must be positive");
+  const int rc = tail_next_params(&d->next, p);
+  if (rc) return rc;
+  p.live = d->live_stride; p.OH = t.OH; p.OW = t.OW;
+  return 0;
+}
+
+int hvr_bottleneck_tail_next_live_supported(const hvr_tail_next_live_desc* d) {
+  GemmParams p;
+  if (tail_next_live_params(d, p)) return 0;
+  return (expand_next_live_supported(p) || expand_split_next_live_supported(p)) ? 1 : 0;
+}
+
+int hvr_bottleneck_tail_next_live(const hvr_tail_next_live_desc* d, void* stream) {
+  GemmParams p;
+  const int rc = tail_next_live_params(d, p);
+  if (rc) return rc;
+  if (expand_split_next_live_supported(p)) return check_launch(run_expand_split(p, (hipStream_t)stream), "hvr_bottleneck_tail_next_live(split half)");
+  if (!expand_next_live_supported(p))
+    return fail(HVR_EUNSUPPORTED, "no live-store tail + next conv kernel for C1=%d Cout=%d Cn=%d dtype=%d", d->next.tail.C1, d->next.tail.Cout, d->next.Cn, d->next.tail.dtype);
+  return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_tail_next_live");
+}
+
 // closing 1x1 of a stage's last block on the pixels the next stage's stride-2 1x1 convs read: compact h and y, the residual sampled from the
 // block's full-resolution input (expand.hip / expand_split.hip, GemmParams::rs)
 static int close_sampled_params(const hvr_close_sampled_desc* d, GemmParams& p) {

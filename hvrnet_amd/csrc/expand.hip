@@ -53,6 +53,18 @@ template <int N> __device__ __forceinline__ void x_wait_vm() {
 
 typedef uint32_t xu32x4 __attribute__((ext_vector_type(4)));
 
+// A 16-byte store that EVERY wave issues and only the lanes of `mask` perform (the live-store kernels): one asm statement -- the compiler
+// cannot branch around it -- that narrows EXEC for the one instruction.  A vector-memory instruction is issued and counted in vmcnt
+// whatever EXEC holds (an empty EXEC sends it down the memory pipeline with no lane to serve: that is why the compiler keeps its
+// s_cbranch_execz in front of exec-masked VMEM as a mere optimisation, and why its own wait counts include such stores), so the hand-counted
+// waits of the chunk loop see the same number of operations behind the DMA as in the plain form.  The compiler's bookkeeping does not see
+// the store: its own waits can only come out stricter, never looser.
+template <int OFF> __device__ __forceinline__ void x_masked_store128(char* dst, const xu32x4& v, uint64_t mask) {
+  uint64_t save;
+  asm volatile("s_mov_b64 %0, exec\n\ts_and_b64 exec, exec, %1\n\tglobal_store_dwordx4 %2, %3, off offset:%4\n\ts_mov_b64 exec, %0"
+               : "=&s"(save) : "s"(mask), "v"(dst), "v"(v), "n"(OFF) : "memory", "scc");
+}
+
 constexpr int X_FJ = 4, X_BN = 16 * X_FJ, X_BM = 128, X_NT = 256;
 
 // 16-byte chunk position of global chunk c of W row `row` (row inside the 64-channel LDS chunk): the 16 lanes of a
@@ -79,7 +91,11 @@ __device__ __forceinline__ int nswz_key(int row) { return (((row >> 5) & 1) * 6)
 // B fragments of that product (k-slot e of lane group g <-> channel 16 g + e, + 8 for the second MFMA); Wn streams
 // through the LDS in 64-input-channel chunks beside W.  The next block then never reads this block's output for its conv1.
 // HT: bf16_t or f16_t -- the operands move as raw 16-bit words; only the MFMA opcode and the pack / unpack of outputs and residual differ
-template <typename HT, int KF, bool RES, int NC, int RF, int NX>
+// LIVE (NX > 0, hvr_bottleneck_tail_next_live): the rows are the pixels of a [.][OH][OW] map of which only a stride-`live` consumer reads the
+// block output: C is the COMPACT map [.][(OH-1)/live+1][(OW-1)/live+1][N] and receives the pixels (live oy, live ox); every other pixel's output
+// feeds the next conv from registers as before and is not stored: its lanes are masked out of the store (x_masked_store128) -- address and lane
+// mask are chosen once per row fragment, every wave still issues every store instruction, so the top-of-chunk vmcnt count below holds unchanged
+template <typename HT, int KF, bool RES, int NC, int RF, int NX, bool LIVE = false>
 __global__ __launch_bounds__(64 * (X_BM / 16 / RF), RF == 2 ? 2 : 1) void expand_res_kernel(const GemmParams p) {
   constexpr int K = KF * 32, FJ = X_FJ, BN = X_BN, BM = X_BM, NT = 64 * (X_BM / 16 / RF);
   constexpr int CHUNK = BN * K * 2;               // bytes of one W chunk
@@ -133,10 +149,22 @@ __global__ __launch_bounds__(64 * (X_BM / 16 / RF), RF == 2 ? 2 : 1) void expand
   // ---- X fragments: rows m0 + 16 i + q, k = 32 kf + 8 g .. + 8 ----
   xu32x4 x[RF][KF];
   int mrow[RF], rrow[RF];
+  char* crow[LIVE ? RF : 1];       // (LIVE) the row's pixel of the compact map (a dead pixel's: an address inside the map, never used)
+  uint64_t amask[LIVE ? RF : 1];   // (LIVE) the lanes of this wave whose pixel is live
+  static_assert(!LIVE || NX > 0, "the live-store form belongs to the kernels with the next conv");
 #pragma unroll
   for (int i = 0; i < RF; ++i) {
     const int m = m0 + i * 16 + q;
     mrow[i] = m < p.M ? m : p.M - 1;
+    if constexpr (LIVE) {
+      // (a row clamped to M - 1 takes row M - 1's address and liveness: the same bytes from several lanes, as in the plain form)
+      const int ox = mrow[i] % p.OW, t = mrow[i] / p.OW, oy = t % p.OH, b = t / p.OH;
+      const int cy = oy / p.live, cx = ox / p.live;
+      const bool alive = cy * p.live == oy && cx * p.live == ox;
+      const long lrow = ((long)b * ((p.OH - 1) / p.live + 1) + cy) * ((p.OW - 1) / p.live + 1) + cx;
+      crow[i] = (char*)p.C + lrow * p.ldc * 2;
+      amask[i] = __builtin_amdgcn_ballot_w64(alive);
+    }
     // residual row (p.rs > 0: the row's pixel of the full-resolution residual map, sampled at stride rs)
     rrow[i] = mrow[i];
     if (p.rs > 0) {
@@ -277,7 +305,9 @@ __global__ __launch_bounds__(64 * (X_BM / 16 / RF), RF == 2 ? 2 : 1) void expand
     for (int i = 0; i < RF; ++i) {
       // a lane whose row is past M was given row M - 1's X and residual: it holds row M - 1's outputs bit for bit and
       // stores them where row M - 1 goes (same bytes from several lanes), so no store is ever skipped
-      char* dst = (char*)p.C + ((long)mrow[i] * p.ldc + nb) * 2;
+      char* dst;
+      if constexpr (LIVE) dst = crow[i] + nb * 2;
+      else dst = (char*)p.C + ((long)mrow[i] * p.ldc + nb) * 2;
 #pragma unroll
       for (int v = 0; v < NV; ++v) {
         uint32_t o[4];
@@ -299,6 +329,10 @@ __global__ __launch_bounds__(64 * (X_BM / 16 / RF), RF == 2 ? 2 : 1) void expand
 #ifdef HVR_DBG_X_NOSTORE
         if (o[0] == 0x12345678u && o[3] == 0x9abcdef0u)
 #endif
+        if constexpr (LIVE) {
+          if (v == 0) x_masked_store128<0>(dst, xu32x4{o[0], o[1], o[2], o[3]}, amask[i]);
+          else x_masked_store128<16>(dst, xu32x4{o[0], o[1], o[2], o[3]}, amask[i]);
+        } else
         *reinterpret_cast<uint4*>(dst + v * 16) = make_uint4(o[0], o[1], o[2], o[3]);
         if constexpr (NX > 0) yv[i][v] = make_uint4(o[0], o[1], o[2], o[3]);
       }
@@ -393,14 +427,14 @@ bool expand_supported(const GemmParams& p) {
   return true;
 }
 
-template <typename T, int KF, bool RES, int NC, int NX = 0>
+template <typename T, int KF, bool RES, int NC, int NX = 0, bool LIVE = false>
 static hipError_t launch_expand_nc(const GemmParams& p, hipStream_t stream) {
   // (NX = 16 -- layer 3's closing 1x1 with the next block's 1024 -> 256 conv1: 64 next-conv accumulator registers per row fragment -- takes
   // the 8-wave form too: one row fragment per wave, one workgroup per CU)
   constexpr int RF = (KF > 8 || NX >= 16) ? 1 : 2;
   constexpr int lds = 2 * X_BN * KF * 32 * 2 + NC * X_BN * 4 + 2 * NX * 16 * 128;  // two W chunks + shifts (+ two Wn chunks)
   static_assert(lds <= (RF == 2 ? 80 : 160) * 1024, "two workgroups per CU (one with 8 waves at K = 512)");
-  auto kern = expand_res_kernel<T, KF, RES, NC, RF, NX>;
+  auto kern = expand_res_kernel<T, KF, RES, NC, RF, NX, LIVE>;
   static std::atomic<unsigned> attr_set_dev{0};   // (the attribute is per device)
   per_device_once(attr_set_dev, [&] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -431,6 +465,11 @@ static hipError_t launch_expand(const GemmParams& p, hipStream_t stream) {
 // (N = 512, Cn = 128) of the R-101, with or without the projection-shortcut segment
 template <typename T>
 static hipError_t run_expand_next(const GemmParams& p, hipStream_t stream) {
+  if (p.live > 0) {   // the live-store form: the identity blocks of stages 1 and 2 only (expand_next_live_supported)
+    if (p.N == 256 && p.Cn == 64 && p.K == 64 && p.resid) return launch_expand_nc<T, 2, true, 4, 4, true>(p, stream);
+    if (p.N == 512 && p.Cn == 128 && p.K == 128 && p.resid) return launch_expand_nc<T, 4, true, 8, 8, true>(p, stream);
+    return hipErrorInvalidValue;
+  }
   if (p.N == 256 && p.Cn == 64) {
     if (p.K == 64 && p.resid) return launch_expand_nc<T, 2, true, 4, 4>(p, stream);
     if (p.K == 128 && !p.resid) return launch_expand_nc<T, 4, false, 4, 4>(p, stream);
@@ -458,6 +497,15 @@ bool expand_next_supported(const GemmParams& p) {
   // 240 us against 260 - 298 for the two launches; 15 frames = 281 panels: 86 against 67 - 78, profiles/r06_l3_fused.txt)
   if (p.N == 1024 && p.Cn == 256) return p.K == 256 && p.resid && p.s2 == 0 && p.M >= 512 * X_BM;
   return false;
+}
+
+// the live-store form of the above (p.live > 0: C is the compact map of the pixels (live oy, live ox), no other pixel is stored):
+// the identity blocks of stages 1 and 2, rows = whole [OH][OW] frames
+bool expand_next_live_supported(const GemmParams& p) {
+  if (p.live <= 0 || p.rs != 0 || p.s2 != 0 || !p.resid) return false;
+  if (p.OH <= 0 || p.OW <= 0 || p.M % (p.OH * p.OW)) return false;
+  if (!expand_next_supported(p)) return false;
+  return (p.N == 256 && p.Cn == 64 && p.K == 64) || (p.N == 512 && p.Cn == 128 && p.K == 128);
 }
 
 template <typename T>

@@ -48,6 +48,13 @@ __device__ __forceinline__ f32x4 xs_mma(const uint4& w, const uint4& x, const f3
 
 typedef uint32_t xsu32x4 __attribute__((ext_vector_type(4)));
 
+// a 16-byte store that every wave issues and only the lanes of `mask` perform (expand.hip: x_masked_store128 -- counted in vmcnt whatever EXEC holds)
+template <int OFF> __device__ __forceinline__ void xs_masked_store128(char* dst, const xsu32x4& v, uint64_t mask) {
+  uint64_t save;
+  asm volatile("s_mov_b64 %0, exec\n\ts_and_b64 exec, exec, %1\n\tglobal_store_dwordx4 %2, %3, off offset:%4\n\ts_mov_b64 exec, %0"
+               : "=&s"(save) : "s"(mask), "v"(dst), "v"(v), "n"(OFF) : "memory", "scc");
+}
+
 constexpr int XS_FJ = 4, XS_BN = 16 * XS_FJ, XS_BM = 128, XS_NT = 256, XS_RF = 2;
 
 // W chunk image [k-step][row][128 B]: the 16-byte piece at position pos of row `row` holds global chunk pos ^ key(row) -- expand.hip's
@@ -62,7 +69,10 @@ __device__ __forceinline__ int xs_nkey(int row) { return (((row >> 4) & 3) << 2)
 
 // KF: K / 32; RES: a residual is added; NC: chunks of 64 output channels per workgroup (blockIdx.y selects the range);
 // NX: 16-channel fragments of the next conv's output (0 = off; then NC = N / 64 and gridDim.y = 1)
-template <int KF, bool RES, int NC, int NX>
+// LIVE (NX > 0): expand.hip's live-store form -- C is the compact map of the pixels (live oy, live ox), every other pixel's lanes are masked
+// out of the stores; address and lane mask are chosen once per row fragment and every wave issues every store instruction (the vmcnt count at
+// the top of a chunk is unchanged)
+template <int KF, bool RES, int NC, int NX, bool LIVE = false>
 __global__ __launch_bounds__(XS_NT, 2) void expand_split_kernel(const GemmParams p) {
   constexpr int K = KF * 32, FJ = XS_FJ, BN = XS_BN, BM = XS_BM, NT = XS_NT, RF = XS_RF;
   constexpr int CHUNK = BN * K * 4;               // bytes of one W chunk: [KF][64 rows][128 B]
@@ -116,10 +126,21 @@ __global__ __launch_bounds__(XS_NT, 2) void expand_split_kernel(const GemmParams
   // ---- X fragments, both planes: rows m0 + 16 i + q, k = 32 kf + 8 g .. + 8 ----
   xsu32x4 xh[RF][KF], xl[RF][KF];
   int mrow[RF], rrow[RF];
+  char* crow[LIVE ? RF : 1];       // (LIVE) the row's pixel of the compact map (a dead pixel's: an address inside the map, never used)
+  uint64_t amask[LIVE ? RF : 1];   // (LIVE) the lanes of this wave whose pixel is live
+  static_assert(!LIVE || NX > 0, "the live-store form belongs to the kernel with the next conv");
 #pragma unroll
   for (int i = 0; i < RF; ++i) {
     const int m = m0 + i * 16 + q;
     mrow[i] = m < p.M ? m : p.M - 1;
+    if constexpr (LIVE) {
+      const int ox = mrow[i] % p.OW, t = mrow[i] / p.OW, oy = t % p.OH, b = t / p.OH;
+      const int cy = oy / p.live, cx = ox / p.live;
+      const bool alive = cy * p.live == oy && cx * p.live == ox;
+      const long lrow = ((long)b * ((p.OH - 1) / p.live + 1) + cy) * ((p.OW - 1) / p.live + 1) + cx;
+      crow[i] = (char*)p.C + lrow * p.ldc * 4;
+      amask[i] = __builtin_amdgcn_ballot_w64(alive);
+    }
     // residual row (p.rs > 0: the row's pixel of the full-resolution residual map, sampled at stride rs -- expand.hip)
     rrow[i] = mrow[i];
     if (p.rs > 0) {
@@ -233,7 +254,9 @@ __global__ __launch_bounds__(XS_NT, 2) void expand_split_kernel(const GemmParams
 #pragma unroll
     for (int i = 0; i < RF; ++i) {
       // (a lane whose row is past M holds row M - 1's outputs bit for bit and stores them where row M - 1 goes: no store is skipped)
-      char* dst = (char*)p.C + (long)mrow[i] * p.ldc * 4 + c * 256 + lane_col;
+      char* dst;
+      if constexpr (LIVE) dst = crow[i] + c * 256 + lane_col;
+      else dst = (char*)p.C + (long)mrow[i] * p.ldc * 4 + c * 256 + lane_col;
       uint32_t oh[8], ol[8];
 #pragma unroll
       for (int w = 0; w < 8; ++w) {   // word w: channels 2 w, 2 w + 1 of the lane's 16 = fragment w / 2, r = 2 (w & 1)
@@ -250,10 +273,17 @@ __global__ __launch_bounds__(XS_NT, 2) void expand_split_kernel(const GemmParams
         if (p.relu) { a = fmaxf(a, 0.f); b = fmaxf(b, 0.f); }
         split2(a, b, oh[w], ol[w]);
       }
-      *reinterpret_cast<uint4*>(dst) = make_uint4(oh[0], oh[1], oh[2], oh[3]);
-      *reinterpret_cast<uint4*>(dst + 16) = make_uint4(oh[4], oh[5], oh[6], oh[7]);
-      *reinterpret_cast<uint4*>(dst + kSplitPlane) = make_uint4(ol[0], ol[1], ol[2], ol[3]);
-      *reinterpret_cast<uint4*>(dst + kSplitPlane + 16) = make_uint4(ol[4], ol[5], ol[6], ol[7]);
+      if constexpr (LIVE) {
+        xs_masked_store128<0>(dst, xsu32x4{oh[0], oh[1], oh[2], oh[3]}, amask[i]);
+        xs_masked_store128<16>(dst, xsu32x4{oh[4], oh[5], oh[6], oh[7]}, amask[i]);
+        xs_masked_store128<kSplitPlane>(dst, xsu32x4{ol[0], ol[1], ol[2], ol[3]}, amask[i]);
+        xs_masked_store128<kSplitPlane + 16>(dst, xsu32x4{ol[4], ol[5], ol[6], ol[7]}, amask[i]);
+      } else {
+        *reinterpret_cast<uint4*>(dst) = make_uint4(oh[0], oh[1], oh[2], oh[3]);
+        *reinterpret_cast<uint4*>(dst + 16) = make_uint4(oh[4], oh[5], oh[6], oh[7]);
+        *reinterpret_cast<uint4*>(dst + kSplitPlane) = make_uint4(ol[0], ol[1], ol[2], ol[3]);
+        *reinterpret_cast<uint4*>(dst + kSplitPlane + 16) = make_uint4(ol[4], ol[5], ol[6], ol[7]);
+      }
       if constexpr (NX > 0) {
         yh[i][0] = make_uint4(oh[0], oh[1], oh[2], oh[3]); yh[i][1] = make_uint4(oh[4], oh[5], oh[6], oh[7]);
         yl[i][0] = make_uint4(ol[0], ol[1], ol[2], ol[3]); yl[i][1] = make_uint4(ol[4], ol[5], ol[6], ol[7]);
@@ -343,11 +373,17 @@ bool expand_split_next_supported(const GemmParams& p) {
   return p.N == 256 && p.Cn == 64 && p.K == 64;
 }
 
-template <int KF, bool RES, int NC, int NX = 0>
+// the live-store form (expand.hip: expand_next_live_supported), stage 1 only
+bool expand_split_next_live_supported(const GemmParams& p) {
+  if (p.live <= 0 || p.rs != 0 || p.OH <= 0 || p.OW <= 0 || p.M % (p.OH * p.OW)) return false;
+  return expand_split_next_supported(p);
+}
+
+template <int KF, bool RES, int NC, int NX = 0, bool LIVE = false>
 static hipError_t launch_expand_split(const GemmParams& p, hipStream_t stream) {
   constexpr int lds = 2 * XS_BN * KF * 32 * 4 + NC * XS_BN * 4 + 2 * NX * 16 * 256;
   static_assert(lds <= 80 * 1024, "two workgroups per CU");
-  auto kern = expand_split_kernel<KF, RES, NC, NX>;
+  auto kern = expand_split_kernel<KF, RES, NC, NX, LIVE>;
   static std::atomic<unsigned> attr_set{0};   // (the attribute is per device)
   per_device_once(attr_set, [&] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -368,6 +404,7 @@ static hipError_t launch_expand_split_nc(const GemmParams& p, hipStream_t stream
 
 hipError_t run_expand_split(const GemmParams& p, hipStream_t stream) {
   if (p.Wn) {
+    if (p.live > 0) return expand_split_next_live_supported(p) ? launch_expand_split<2, true, 4, 4, true>(p, stream) : hipErrorInvalidValue;
     if (expand_split_next_supported(p)) return launch_expand_split<2, true, 4, 4>(p, stream);
     return hipErrorInvalidValue;
   }

@@ -75,6 +75,10 @@ class TailNextDesc(ctypes.Structure):
                 ('hn', ctypes.c_void_p), ('Cn', ctypes.c_int32), ('alpha', ctypes.c_float), ('beta', ctypes.c_float)]
 
 
+class TailNextLiveDesc(ctypes.Structure):
+    _fields_ = [('next', TailNextDesc), ('live_stride', ctypes.c_int32)]
+
+
 class CloseSampledDesc(ctypes.Structure):
     _fields_ = [('h', ctypes.c_void_p), ('w', ctypes.c_void_p), ('resid', ctypes.c_void_p), ('y', ctypes.c_void_p),
                 ('B', ctypes.c_int32), ('OH', ctypes.c_int32), ('OW', ctypes.c_int32), ('C1', ctypes.c_int32),
@@ -113,6 +117,8 @@ SYMBOLS = {
     'hvr_bottleneck_tail_supported': (_i, [ctypes.POINTER(TailDesc)]),
     'hvr_bottleneck_tail_next': (_i, [ctypes.POINTER(TailNextDesc), _vp]),
     'hvr_bottleneck_tail_next_supported': (_i, [ctypes.POINTER(TailNextDesc)]),
+    'hvr_bottleneck_tail_next_live': (_i, [ctypes.POINTER(TailNextLiveDesc), _vp]),
+    'hvr_bottleneck_tail_next_live_supported': (_i, [ctypes.POINTER(TailNextLiveDesc)]),
     'hvr_bottleneck_close_sampled': (_i, [ctypes.POINTER(CloseSampledDesc), _vp]),
     'hvr_bottleneck_close_sampled_supported': (_i, [ctypes.POINTER(CloseSampledDesc)]),
     'hvr_im2col_stem': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -560,6 +566,67 @@ def bottleneck_tail_next(h, x, resid, w, bias, wn, bias_n, stride2=1, out=None):
     return y, hn
 
 
+def _tail_next_live_desc(h, resid, w, bias, wn, bias_n, live_stride, y, hn):
+    return TailNextLiveDesc(next=_tail_next_desc(h, None, resid, w, bias, 1, wn, bias_n, y, hn), live_stride=int(live_stride))
+
+
+def bottleneck_tail_next_live_supported(h, resid, w, bias, wn, bias_n, live_stride=2):
+    """True when hvr_bottleneck_tail_next_live runs these shapes: an identity block, (Cout, Cn, C1) = (256, 64, 64) / (512, 128, 128) in
+    bf16 / half, (256, 64, 64) in split half, contiguous maps, at least 128 pixels."""
+    if not all(t.is_cuda and t.dtype in (torch.bfloat16, torch.float16, SPLIT) and t.dtype == h.dtype and t.is_contiguous() for t in (h, resid, w, wn)):
+        return False
+    if h.dim() != 4 or resid.dim() != 4 or wn.dim() != 2 or w.dim() != 2 or wn.shape[1] != w.shape[0] or int(live_stride) < 1:
+        return False
+    if tuple(resid.shape) != tuple(h.shape[:3]) + (w.shape[0],) or w.shape[1] != h.shape[3]:
+        return False
+    return tail_next_live_path(h.shape[0], h.shape[1], h.shape[2], h.shape[3], w.shape[0], wn.shape[0], live_stride, h.dtype)
+
+
+def tail_next_live_path(B, OH, OW, C1, Cout, Cn, live_stride=2, dtype=torch.bfloat16):
+    """Whether hvr_bottleneck_tail_next_live has a kernel for an identity block of these shapes (the query by shape, as conv2d_path: nothing
+    is launched and no memory is touched, the descriptor carries placeholder addresses)."""
+    fake = 1 << 20
+    code = {torch.bfloat16: HVR_BF16, torch.float16: HVR_F16, SPLIT: HVR_F16S}.get(dtype, HVR_F32)
+    t = TailDesc(h=fake, x=None, w=fake, y=fake, B=B, OH=OH, OW=OW, C1=C1, H2=OH, W2=OW, C2=0, stride2=1, Cout=Cout, bias=fake, relu=1, dtype=code)
+    nd = TailNextDesc(tail=t, resid=fake, wn=fake, bias_n=fake, hn=fake, Cn=Cn)
+    if dtype == SPLIT:
+        nd.alpha, nd.beta = _split_factors(False, None)
+    d = TailNextLiveDesc(next=nd, live_stride=int(live_stride))
+    return bool(lib().hvr_bottleneck_tail_next_live_supported(ctypes.byref(d)))
+
+
+def bottleneck_tail_next_live(h, resid, w3, b3, wn, bn, live_stride=2, out=None, out_hn=None):
+    """bottleneck_tail_next's identity form for a block whose output only a stride-`live_stride` consumer reads besides the next block's
+    conv1: y = relu(h W3^T + b3 + resid) is computed everywhere and written at pixels (s oy, s ox) only, as the compact map
+    y_live [B,(OH-1)//s+1,(OW-1)//s+1,Cout] = bottleneck_tail_next(...)[0][:, ::s, ::s] bit for bit; hn = relu(y wn^T + bn) [B,OH,OW,Cn]
+    at full resolution, bit for bit as well.  The dead pixels are computed and not stored (their lanes are masked out of the stores), so
+    there is no scratch and nothing to allocate inside a captured region but the two outputs.  -> (y_live, hn)"""
+    _need_cuda(h, resid, w3, b3, wn, bn)
+    B, OH, OW, C1 = h.shape
+    Cout, Cn, s = w3.shape[0], wn.shape[0], int(live_stride)
+    LH, LW = (OH - 1) // s + 1, (OW - 1) // s + 1
+    assert h.is_contiguous() and resid.is_contiguous() and tuple(resid.shape) == (B, OH, OW, Cout) and resid.dtype == h.dtype
+    if out is not None:
+        assert tuple(out.shape) == (B, LH, LW, Cout) and out.dtype == h.dtype and out.is_contiguous()
+        y = out
+    else:
+        y = torch.empty((B, LH, LW, Cout), dtype=h.dtype, device=h.device)
+    if out_hn is not None:
+        assert tuple(out_hn.shape) == (B, OH, OW, Cn) and out_hn.dtype == h.dtype and out_hn.is_contiguous()
+        hn = out_hn
+    else:
+        hn = torch.empty((B, OH, OW, Cn), dtype=h.dtype, device=h.device)
+    d = _tail_next_live_desc(h, resid, w3, b3, wn, bn, s, y, hn)
+    tag = 'conv_expand'
+    # bytes it moves: h, the residual and hn at every pixel, y at the live ones, W3 and Wn once
+    work = float((h.numel() + resid.numel() + y.numel() + hn.numel() + w3.numel() + wn.numel()) * h.element_size())
+    if _prof is not None and _prof['detail']:
+        tag = 'conv_expand tail+next live/%d %dx%d %d+0->%d->%d' % (s, OH, OW, C1, Cout, Cn)
+    with _span(tag, work):
+        _check(lib().hvr_bottleneck_tail_next_live(ctypes.byref(d), _stream()), 'hvr_bottleneck_tail_next_live')
+    return y, hn
+
+
 def _close_sampled_desc(h, w, bias, resid, stride, relu, y):
     B, OH, OW, C1 = h.shape
     _, RH, RW, Cout = resid.shape
@@ -579,6 +646,17 @@ def bottleneck_close_sampled_supported(h, w, bias, resid, stride):
     if h.shape[0] != resid.shape[0] or w.numel() != resid.shape[3] * h.shape[3] or w.shape[0] != resid.shape[3]:
         return False
     return bool(lib().hvr_bottleneck_close_sampled_supported(ctypes.byref(_close_sampled_desc(h, w, bias, resid, stride, True, None))))
+
+
+def close_sampled_path(B, OH, OW, C1, Cout, RH, RW, stride=2, dtype=torch.bfloat16):
+    """Whether hvr_bottleneck_close_sampled has a kernel for these shapes (the query by shape: placeholder addresses, nothing is launched)."""
+    fake = 1 << 20
+    code = {torch.bfloat16: HVR_BF16, torch.float16: HVR_F16, SPLIT: HVR_F16S}.get(dtype, HVR_F32)
+    d = CloseSampledDesc(h=fake, w=fake, resid=fake, y=fake, B=B, OH=OH, OW=OW, C1=C1, Cout=Cout, RH=RH, RW=RW, rstride=int(stride), bias=fake,
+                         relu=1, dtype=code)
+    if dtype == SPLIT:
+        d.alpha, d.beta = _split_factors(False, None)
+    return bool(lib().hvr_bottleneck_close_sampled_supported(ctypes.byref(d)))
 
 
 def bottleneck_close_sampled(h, w, bias, resid, stride=2, relu=True, out=None):

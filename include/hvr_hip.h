@@ -203,6 +203,28 @@ typedef struct hvr_tail_next_desc {
 int hvr_bottleneck_tail_next(const hvr_tail_next_desc* d, void* stream);
 int hvr_bottleneck_tail_next_supported(const hvr_tail_next_desc* d);
 
+/* The identity form of hvr_bottleneck_tail_next for a block whose output map only a stride-s consumer reads besides the next block's
+ * conv1 -- the block BEFORE the last of a stage that ends compact (hvr_bottleneck_close_sampled): the last block's residual is read
+ * at pixels (s oy, s ox) only, so three quarters of y are stores nobody loads.  Same products, same order:
+ *   y  = relu(h W3^T + bias + resid)      computed at every pixel, WRITTEN only at pixels (s oy, s ox), as a compact map
+ *                                         y [B][(OH-1)/s+1][(OW-1)/s+1][Cout]  (s = live_stride >= 1)
+ *   hn = relu(y wn^T + bias_n)            [B][OH][OW][Cn], full resolution, from the rounded y in registers as before
+ * tail.C2 == 0 (tail.x ignored), tail.relu == 1, resid [B][OH][OW][Cout] = the block input.  The bits of y's pixels and of all of hn
+ * equal what hvr_bottleneck_tail_next writes for the same operands.  The last block then closes on (compact h, y) with
+ * hvr_bottleneck_close_sampled at rstride 1 or hvr_conv2d_nhwc: a dense residual instead of a stride-s gather.
+ * Dead pixels are computed (the next conv needs them) and not stored.  The kernel's vmcnt waits count the stores in flight, so its
+ * instruction stream stays uniform: every wave issues every store instruction, and the lanes of dead pixels are masked out of it in EXEC
+ * (a vector-memory instruction is issued and counted whatever EXEC holds).  Nothing is written outside y and hn.
+ * (Cout, Cn, C1) = (256, 64, 64) / (512, 128, 128) in HVR_BF16 / HVR_F16, (256, 64, 64) in HVR_F16S (alpha / beta as in
+ * hvr_tail_next_desc); B OH OW >= 128.  hvr_bottleneck_tail_next_live_supported: 1 when this descriptor runs, 0 otherwise (projection
+ * blocks, exact f32, layer 3's 1024 / 256: the caller then uses hvr_bottleneck_tail_next and a full-resolution y). */
+typedef struct hvr_tail_next_live_desc {
+  hvr_tail_next_desc next;   /* next.tail.y: the COMPACT map */
+  int32_t live_stride;
+} hvr_tail_next_live_desc;
+int hvr_bottleneck_tail_next_live(const hvr_tail_next_live_desc* d, void* stream);
+int hvr_bottleneck_tail_next_live_supported(const hvr_tail_next_live_desc* d);
+
 /* Closing 1x1 conv + residual + ReLU of an identity Bottleneck, computed only on the pixels a stride-s consumer reads (the last
  * block of a stage whose successor is a caffe-style stage: its first block's conv1 and downsample are both 1x1 with stride 2,
  * resnet.py:127-132,283-296, and read this block's output at pixels (s oy, s ox) only):
