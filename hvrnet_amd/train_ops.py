@@ -520,7 +520,8 @@ class ConvFunction(Function):
     BatchNorm (scale s, shift t per output channel; pass s = ones / t = bias for a plain conv with bias) and optionally the
     residual add and ReLU of a Bottleneck (resnet.py:220-266).  x [B,H,W,Cin], w [Cout,Cin,KH,KW] (the nn.Conv2d
     parameter), stride 1 for KxK kernels; a strided 1x1 conv is a row subset followed by a linear layer.
-    Backward: ReLU mask, dX by the same implicit-GEMM conv kernel on the rotated weights (or a GEMM for 1x1), dW^T as a
+    Backward: ReLU mask, dX by the same implicit-GEMM conv kernel on the rotated weights (or a GEMM for 1x1; either way Cout,
+    the reduction's channel count, is zero-padded to the K-step), dW^T as a
     GEMM of dZ^T with the patch matrix, both scaled by s; s and t are frozen and get no gradient.
     x's dtype is the compute dtype (bf16 activations: the scaled f32 master weight is rounded to bf16 on the way in, dX is
     bf16, dW accumulates and is returned in f32); out_f32 asks for an f32 output from bf16 operands (the RPN's 1x1 heads)."""
@@ -580,7 +581,14 @@ class ConvFunction(Function):
                 dxs = native.gemm(_pad_cols(dz2, ldn), wt).view(B, OH, OW, Cin)  # dz W
             else:
                 w_rot = aux if aux is not None else w_eff.flip(1, 2).permute(3, 1, 2, 0).contiguous()   # [Cin][KH][KW][Cout], taps reversed
-                dxs = native.conv2d_nhwc(dz, w_rot, None, None, relu=False, pad=dil * (KH - 1) - pad, dil=dil)
+                ldn = (Cout + step - 1) // step * step
+                dzc = dz
+                if ldn != Cout:     # Cout is the dX conv's input-channel count: zero channels up to its K-step, in both operands
+                    dzc = _pad_cols(dz2, ldn).view(B, OH, OW, ldn)
+                    w_pad = w_rot.new_zeros((Cin, KH, KW, ldn))
+                    w_pad[..., :Cout] = w_rot
+                    w_rot = w_pad
+                dxs = native.conv2d_nhwc(dzc, w_rot, None, None, relu=False, pad=dil * (KH - 1) - pad, dil=dil)
             if stride > 1:
                 dx = dxs.new_zeros(x_shape)
                 dx[:, ::stride, ::stride, :] = dxs
