@@ -13,6 +13,9 @@ forward pass runs on packed device buffers:
 Inference only: BN layers are always treated as frozen (both configs set norm_eval=True,
 requires_grad=False).  There is no CPU path (native.py raises on CPU tensors).
 """
+import collections
+import itertools
+
 import torch
 import torch.nn as nn
 
@@ -24,11 +27,13 @@ STEM_KP = 192  # 7*7*3 = 147 patch elements padded to a K-step multiple
 
 
 def as_nhwc(x, dtype):
-    """Logical [B,C,H,W] tensor -> physical [B,H,W,C] contiguous tensor of `dtype` (no copy when it already is)."""
+    """Logical [B,C,H,W] tensor -> physical [B,H,W,C] contiguous tensor of `dtype` (no copy when it already is) at a 128-byte aligned
+    address, which the routes planned by shape assume of a block input (16 bytes; split half 128): a view at any other address is copied."""
     v = x.permute(0, 2, 3, 1)
-    if v.is_contiguous():
-        return v if x.dtype == dtype else native.cast(v, dtype)
-    return native.nchw_to_nhwc(x.contiguous(), dtype)
+    if not v.is_contiguous():
+        return native.nchw_to_nhwc(x.contiguous(), dtype)
+    v = v if x.dtype == dtype else native.cast(v, dtype)
+    return v if v.data_ptr() % 128 == 0 else v.clone()
 
 
 def as_logical(y):
@@ -145,6 +150,31 @@ def enable_training(module):
     return module
 
 
+class Step(collections.namedtuple('Step', 'kind projection downsample stride compact h1_in', defaults=(False, False, None, False, False))):
+    """How one Bottleneck of a stage closes (ResNet.stage_route).  kind: the native entry -- 'tail', 'tail_next' (`projection`: the shortcut
+    as a second K segment, else the identity form), 'tail_next_live', 'close_sampled' (at `stride` 2 from the full-resolution input) or 'conv'.
+    downsample: the projection shortcut is a conv of its own in front.  compact ('close_sampled' at stride 1, 'conv'): the dense close on the
+    compact map that a tail_next_live block left.  h1_in: the block's conv1 output arrived from the block before."""
+
+    def __str__(self):
+        form = {'tail_next': '(projection)' if self.projection else '(identity)', 'close_sampled': '/%s' % self.stride}.get(self.kind, '')
+        return ('downsample+' if self.downsample else '') + self.kind + form + ('@compact' if self.compact and self.kind == 'conv' else '')
+
+
+class Route(collections.namedtuple('Route', 'steps out_hw compact')):
+    """A stage's Steps (one per block), the (H, W) of the map it stores, and whether that is the compact map: the stage output at [:, ::2, ::2]."""
+
+    def __str__(self):
+        runs = [(k, len(list(g))) for k, g in itertools.groupby(str(s) for s in self.steps)]
+        return '%s -> %dx%d%s' % (', '.join(k if n == 1 else '%s x%d' % (k, n) for k, n in runs), self.out_hw[0], self.out_hw[1],
+                                  ' compact' if self.compact else '')
+
+
+def _w2d(wb):
+    """A packed 1x1 conv (w [Cout,1,1,Cin], bias) as the fused entries take it: (w [Cout,Cin], bias)."""
+    return wb[0].reshape(wb[0].shape[0], -1), wb[1]
+
+
 class Bottleneck(nn.Module, PackedMixin):
     expansion = 4
 
@@ -194,102 +224,85 @@ class Bottleneck(nn.Module, PackedMixin):
                          (p['c3'][1] + p['ds'][1]).contiguous())
         return p
 
-    def forward_nhwc(self, x, out=None, h1=None, nxt=None, compact_in=False, live_stride=None):
-        """out: where the block's output goes (a contiguous [B,OH,OW,4*planes] tensor), e.g. a frame group's slice of a map.
-        h1: this block's conv1 output, when the previous block's tail already computed it.  nxt: the block that consumes
-        this one's output; the return value is then (y, h1 of nxt or None) -- nxt's conv1 rides on this block's tail when
-        hvr_bottleneck_tail_next has a kernel for the shapes.  compact_in (a caffe-style stride-2 block only): x already holds
-        only the pixels this block's strided 1x1 convs read (forward_sampled_nhwc of the block before), so they run at stride 1.
-        live_stride (with nxt, an identity block): nothing but nxt's conv1 and a stride-`live_stride` consumer reads this block's output
-        (the block before the last of a stage that ends compact); where hvr_bottleneck_tail_next_live has a kernel the return value is
-        (y_live, h1 of nxt) with y_live [B,(H-1)//s+1,(W-1)//s+1,4*planes] = the output at [:, ::s, ::s], otherwise as without it."""
-        p = self.packed(x.device)
-        dst = out
-        stride, conv1_stride = (1, 1) if compact_in else (self.stride, self.conv1_stride)
-        out = h1 if h1 is not None else native.conv2d_nhwc(x, p['c1'][0], p['c1'][1], relu=True, stride=conv1_stride)
+    # ---- the steps of a block.  Which close runs is planned by shape (plan_close, ResNet.stage_route); a step runs its entry or raises.
+    def plan_close(self, B, H, W, dtype, nxt=None, compact_in=False):
+        """The Step this block closes through at full resolution on a [B,H,W] input map (pure: shape queries, nothing launched); the conv1 of
+        nxt, the block that reads the output, rides on the close where hvr_bottleneck_tail_next has a kernel."""
+        stride = 1 if compact_in else self.stride
+        OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+        P, C, proj = self.planes, 4 * self.planes, self.downsample is not None
+        # split half has no second-K-segment tail: the projection is its own conv and enters the fused closing 1x1 + next conv1 as the
+        # residual (the identity form of hvr_bottleneck_tail_next)
+        own_ds = proj and dtype == native.SPLIT
+        x_hwc = (H, W, self.inplanes) if proj and not own_ds else None
+        if nxt is not None and self.fuse_next and nxt.conv1_stride == 1 and (own_ds or self.fuse_tail or not proj) \
+                and native.tail_next_path(B, OH, OW, P, C, nxt.planes, x_hwc, stride, dtype):
+            return Step('tail_next', projection=x_hwc is not None, downsample=own_ds)
+        if x_hwc is not None and self.fuse_tail and native.tail_path(B, OH, OW, P, C, x_hwc, stride, dtype):
+            return Step('tail')
+        return Step('conv', downsample=proj)
+
+    def body(self, x, h1=None, compact_in=False, conv2_stride=None, out=None):
+        """conv1 (unless h1, its output, was handed in by the block before) and conv2 or the deformable pair -> the closing 1x1's input.
+        compact_in (a caffe-style stride-2 block): x holds only the pixels the strided 1x1 convs read, so they run at stride 1."""
+        p = self.packed(x.device if h1 is None else h1.device)
+        h = h1 if h1 is not None else native.conv2d_nhwc(x, p['c1'][0], p['c1'][1], relu=True, stride=1 if compact_in else self.conv1_stride)
+        s2 = self.conv2_stride if conv2_stride is None else conv2_stride
         if self.with_dcn:
-            om = native.conv2d_nhwc(out, p['off'][0], p['off'][1], relu=False, stride=self.conv2_stride, pad=self.dilation, dil=self.dilation,
-                                    out_f32=True)
-            out = native.deform_conv2d_nhwc(out, om, p['c2'][0], p['c2'][1], True, self.conv2_stride, self.dilation, self.dilation,
-                                            self.deformable_groups, self.with_modulated_dcn)
-        else:
-            out = native.conv2d_nhwc(out, p['c2'][0], p['c2'][1], relu=True, stride=self.conv2_stride, pad=self.dilation,
-                                     dil=self.dilation)
-        if nxt is not None and self.fuse_next and nxt.conv1_stride == 1:
-            pn = nxt.packed(x.device)
-            wn, bn = pn['c1'][0].reshape(pn['c1'][0].shape[0], -1), pn['c1'][1]
-            if self.downsample is not None:
-                args = (out, x, None, p['tail'][0], p['tail'][1], stride) if self.fuse_tail else None
-                if x.dtype == native.SPLIT:
-                    # split half has no second-K-segment tail: the projection is its own conv and enters the fused closing 1x1 +
-                    # next conv1 as the residual (the identity form of hvr_bottleneck_tail_next)
-                    ident = native.conv2d_nhwc(x, p['ds'][0], p['ds'][1], relu=False, stride=stride)
-                    w3, b3 = p['c3'][0].reshape(p['c3'][0].shape[0], -1), p['c3'][1]
-                    if native.bottleneck_tail_next_supported(out, None, ident, w3, b3, 1, wn, bn):
-                        return native.bottleneck_tail_next(out, None, ident, w3, b3, wn, bn, out=dst)
-                    y = native.conv2d_nhwc(out, p['c3'][0], p['c3'][1], resid=ident, relu=True, out=dst)
-                    return y, None
-            else:
-                args = (out, None, x, p['c3'][0].reshape(p['c3'][0].shape[0], -1), p['c3'][1], 1)
-                if live_stride is not None and dst is None and native.bottleneck_tail_next_live_supported(out, x, args[3], args[4], wn, bn, live_stride):
-                    return native.bottleneck_tail_next_live(out, x, args[3], args[4], wn, bn, live_stride=live_stride)
-            if args is not None and native.bottleneck_tail_next_supported(*args, wn, bn):
-                return native.bottleneck_tail_next(args[0], args[1], args[2], args[3], args[4], wn, bn, stride2=args[5], out=dst)
-        y = self._tail(x, out, p, dst, stride)
-        return y if nxt is None else (y, None)
+            om = native.conv2d_nhwc(h, p['off'][0], p['off'][1], relu=False, stride=s2, pad=self.dilation, dil=self.dilation, out_f32=True)
+            return native.deform_conv2d_nhwc(h, om, p['c2'][0], p['c2'][1], True, s2, self.dilation, self.dilation, self.deformable_groups,
+                                             self.with_modulated_dcn, out=out)
+        return native.conv2d_nhwc(h, p['c2'][0], p['c2'][1], relu=True, stride=s2, pad=self.dilation, dil=self.dilation, out=out)
 
-    def _tail(self, x, out, p, dst, stride):
-        identity = x
-        if self.downsample is not None:
-            if self.fuse_tail and native.bottleneck_tail_supported(out, x, p['tail'][0], p['tail'][1], stride):
-                # relu(conv3(out) + downsample(x)) in one pass: the identity map is never written (resnet.py:248-264)
-                return native.bottleneck_tail(out, x, p['tail'][0], p['tail'][1], stride2=stride, relu=True, out=dst)
-            identity = native.conv2d_nhwc(x, p['ds'][0], p['ds'][1], relu=False, stride=stride)
-        return native.conv2d_nhwc(out, p['c3'][0], p['c3'][1], resid=identity, relu=True, out=dst)
-
-    def forward_sampled_nhwc(self, x, h1=None, stride=2, resid_compact=None, plain_close=False):
-        """An identity block whose output only a stride-`stride` 1x1 consumer reads (the last block of a stage in front of a
-        caffe-style stage, resnet.py:127-132): conv1 everywhere (the 3x3 reads neighbours), conv2 as a stride-`stride` 3x3, and the
-        closing 1x1 on those pixels with the residual sampled from x (hvr_bottleneck_close_sampled).  -> (y, True) with
-        y [B,(H-1)//stride+1,(W-1)//stride+1,4*planes] = the full-resolution output at [:, ::stride, ::stride] bit for bit, or
-        (the full-resolution output, False) where the sampled close has no kernel for the dtype / shape.
-        resid_compact (with h1; x is not read and may be None): the block input at [:, ::stride, ::stride] only, as the block before
-        left it (forward_nhwc with live_stride) -- the close is then a dense conv on the compact map: hvr_bottleneck_close_sampled at
-        stride 1, or with plain_close hvr_conv2d_nhwc (the same row-panel kernel and sums either way).  The caller has asked
-        live_close_supported first: there is no full-resolution input to fall back on.  -> (y, True)"""
-        assert self.downsample is None and self.stride == 1 and not self.with_dcn
-        if resid_compact is not None:
-            assert h1 is not None and tuple(resid_compact.shape[1:3]) == ((h1.shape[1] - 1) // stride + 1, (h1.shape[2] - 1) // stride + 1)
-            p = self.packed(h1.device)
-            hs = native.conv2d_nhwc(h1, p['c2'][0], p['c2'][1], relu=True, stride=stride, pad=self.dilation, dil=self.dilation)
-            if plain_close:
-                return native.conv2d_nhwc(hs, p['c3'][0], p['c3'][1], resid=resid_compact, relu=True), True
-            w3, b3 = p['c3'][0].reshape(p['c3'][0].shape[0], -1), p['c3'][1]
-            return native.bottleneck_close_sampled(hs, w3, b3, resid_compact, stride=1, relu=True), True
+    def close(self, x, h, step, out=None, compact_in=False):
+        """The plain close ('tail' or 'conv') -> y.  out: where y goes (a contiguous [B,OH,OW,4*planes] tensor), e.g. a frame group's slice."""
         p = self.packed(x.device)
-        h = h1 if h1 is not None else native.conv2d_nhwc(x, p['c1'][0], p['c1'][1], relu=True, stride=1)
+        stride = 1 if compact_in else self.stride
+        if step.kind == 'tail':
+            # relu(conv3(h) + downsample(x)) in one pass: the identity map is never written (resnet.py:248-264)
+            return native.bottleneck_tail(h, x, p['tail'][0], p['tail'][1], stride2=stride, relu=True, out=out)
+        assert step.kind == 'conv' and not step.compact, step
+        identity = native.conv2d_nhwc(x, p['ds'][0], p['ds'][1], relu=False, stride=stride) if step.downsample else x
+        return native.conv2d_nhwc(h, p['c3'][0], p['c3'][1], resid=identity, relu=True, out=out)
+
+    def close_next(self, x, h, nxt, step, compact_in=False):
+        """'tail_next' -> (y, nxt's conv1 output)."""
+        p, (wn, bn) = self.packed(x.device), _w2d(nxt.packed(x.device)['c1'])
+        stride = 1 if compact_in else self.stride
+        if step.projection:
+            return native.bottleneck_tail_next(h, x, None, p['tail'][0], p['tail'][1], wn, bn, stride2=stride)
+        identity = native.conv2d_nhwc(x, p['ds'][0], p['ds'][1], relu=False, stride=stride) if step.downsample else x
+        return native.bottleneck_tail_next(h, None, identity, *_w2d(p['c3']), wn, bn, stride2=1)
+
+    def close_next_live(self, x, h, nxt, live_stride=2):
+        """'tail_next_live': an identity block whose output nothing reads but nxt's conv1 and a stride-s consumer (s = live_stride)
+        -> (y_live [B,(H-1)//s+1,(W-1)//s+1,4*planes] = the output at [:, ::s, ::s], nxt's conv1 output at full resolution)."""
+        (w3, b3), (wn, bn) = _w2d(self.packed(x.device)['c3']), _w2d(nxt.packed(x.device)['c1'])
+        return native.bottleneck_tail_next_live(h, x, w3, b3, wn, bn, live_stride=live_stride)
+
+    def close_sampled(self, x, h1=None, stride=2):
+        """'close_sampled' at stride 2, the whole of an identity block whose output only a stride-`stride` 1x1 consumer reads: conv1 everywhere (the
+        3x3 reads neighbours), conv2 at that stride, the close with the residual sampled from x -> the full output at [:, ::stride, ::stride]."""
+        assert self.downsample is None and self.stride == 1 and not self.with_dcn
         B, H, W, _ = x.shape
         hs = torch.empty((B, (H - 1) // stride + 1, (W - 1) // stride + 1, self.planes), dtype=x.dtype, device=x.device)
-        w3, b3 = p['c3'][0].reshape(p['c3'][0].shape[0], -1), p['c3'][1]
-        # (the sampled close is the row-panel kernel: the same sums as the full-resolution close only where that one takes it too)
-        full_path = native.conv2d_path(B, H, W, self.planes, 4 * self.planes, dtype=x.dtype, tile=native.TILE_HINT)
-        if full_path != 1 or not native.bottleneck_close_sampled_supported(hs, w3, b3, x, stride):
-            return self.forward_nhwc(x, h1=h), False
-        native.conv2d_nhwc(h, p['c2'][0], p['c2'][1], relu=True, stride=stride, pad=self.dilation, dil=self.dilation, out=hs)
-        return native.bottleneck_close_sampled(hs, w3, b3, x, stride=stride, relu=True), True
+        self.body(x, h1, conv2_stride=stride, out=hs)
+        return native.bottleneck_close_sampled(hs, *_w2d(self.packed(x.device)['c3']), x, stride=stride, relu=True)
 
-    def live_close_supported(self, B, H, W, dtype, stride=2, plain_close=False):
-        """Whether forward_sampled_nhwc(resid_compact=...) can close this block on the compact map of a [B,H,W] input and equal the
-        full-resolution block at [:, ::stride, ::stride] bit for bit: the row-panel kernel takes the close at both sizes (its K order
-        does not depend on the row count), and the compact map has the 128 pixels of one panel."""
-        if self.downsample is not None or self.stride != 1 or self.with_dcn:
-            return False
-        LH, LW = (H - 1) // stride + 1, (W - 1) // stride + 1
-        if B * LH * LW < 128 or native.conv2d_path(B, H, W, self.planes, 4 * self.planes, dtype=dtype, tile=native.TILE_HINT) != 1:
-            return False
-        if plain_close:
-            return native.conv2d_path(B, LH, LW, self.planes, 4 * self.planes, dtype=dtype, tile=native.TILE_HINT) == 1
-        return native.close_sampled_path(B, LH, LW, self.planes, 4 * self.planes, LH, LW, 1, dtype)
+    def close_compact(self, x_live, h1, stride=2, plain=False):
+        """The same block behind close_next_live: x_live is its input at [:, ::stride, ::stride] only, h1 its conv1 output at full resolution,
+        and the close is dense on the compact map: 'close_sampled' at stride 1, or with `plain` 'conv' (the same row-panel kernel and sums)."""
+        assert self.downsample is None and self.stride == 1 and not self.with_dcn
+        assert tuple(x_live.shape[1:3]) == ((h1.shape[1] - 1) // stride + 1, (h1.shape[2] - 1) // stride + 1)
+        w3, b3 = self.packed(h1.device)['c3']
+        hs = self.body(None, h1, conv2_stride=stride)
+        if plain:
+            return native.conv2d_nhwc(hs, w3, b3, resid=x_live, relu=True)
+        return native.bottleneck_close_sampled(hs, w3.reshape(w3.shape[0], -1), b3, x_live, stride=1, relu=True)
+
+    def forward_nhwc(self, x, out=None, h1=None):
+        """The block on its own, at full resolution: body + plain close -> y.  out as in close, h1 as in body."""
+        return self.close(x, self.body(x, h1), self.plan_close(x.shape[0], x.shape[1], x.shape[2], x.dtype), out=out)
 
     fuse_next = True   # class attributes (tests flip them to compare the fused kernels with the per-conv path); no environment switch
     fuse_tail = True
@@ -421,36 +434,63 @@ class ResNet(nn.Module, PackedMixin):
         return (B, h, w, 64 * 2 ** last * 4)
 
     skip_dead_pixels = True   # class attribute (tests flip it to compare with the full-resolution path); no environment switch
-    # Stages that end compact through hvr_bottleneck_close_sampled.  Layer 2 (index 1) qualifies too and is bit-identical as well
-    # (tests/test_dead_pixels_gpu.py), but its closing conv is then the last row-panel conv to leave hvr_conv2d_nhwc in a bf16 window, and
-    # the forward-kernel census (tests/test_forward_kernels_gpu.py) wants that route among the calls it checks against f64: layer 2 is
-    # not listed here and ends compact through live_store_stages instead, with a close that stays on hvr_conv2d_nhwc
+    # Stages that end compact through 'close_sampled' (stage_route).  Layer 2 (index 1) qualifies too and is bit-identical as well
+    # (tests/test_dead_pixels_gpu.py), but is not listed: in a bf16 window its 'conv' close on the compact map is the only closing conv that
+    # hvr_conv2d_nhwc runs on the row-panel kernel, the route the forward-kernel census (tests/test_forward_kernels_gpu.py) checks against
+    # f64, and as 'close_sampled' it would leave that entry (asserted on the route table: tests/test_stage_routes.py)
     compact_stages = (0,)
-    # Stages whose block before the last writes only the live quarter of its output (hvr_bottleneck_tail_next_live), so that the last block
-    # closes densely on the compact map.  A stage listed here and in compact_stages closes through hvr_bottleneck_close_sampled (stride 1);
-    # a stage listed here alone -- layer 2 -- ends compact only this way and closes through hvr_conv2d_nhwc, the route the census checks
+    # Stages whose block before the last writes only the live quarter of its output ('tail_next_live'), so that the last block closes
+    # densely on the compact map: through 'close_sampled' at stride 1 where the stage is in compact_stages too, else -- layer 2 -- through 'conv'
     live_store_stages = (0, 1)
+
+    def stage_route(self, i, B, H, W, dtype, compact_in=False):
+        """The Route of stage i on a stored [B,H,W] input map (compact_in: the compact map the stage before left).  Pure: module structure, the
+        class-attribute knobs, native.fewrow_enabled() and shape queries in; no tensors, nothing launched, nothing cached (str(route) prints it).
+        Precedence: the live-store form and the dense close behind it, else the sampled close, else full resolution."""
+        blocks = list(getattr(self, self.res_layers[i]))
+        steps = []
+        for j, blk in enumerate(blocks):
+            nxt = blocks[j + 1] if j + 1 < len(blocks) else None
+            first = compact_in and j == 0
+            if j >= 1 and j + 2 == len(blocks) and self._live_store(i, blk, nxt, B, H, W, dtype):
+                step = Step('tail_next_live')
+            elif steps and steps[-1].kind == 'tail_next_live':
+                step = Step('close_sampled', stride=1, compact=True) if i in self.compact_stages else Step('conv', compact=True)
+            elif nxt is None and self._ends_compact(i) and dtype in native.FUSED_DTYPES \
+                    and native.conv2d_path(B, H, W, blk.planes, 4 * blk.planes, dtype=dtype, tile=native.TILE_HINT) == 1 \
+                    and native.close_sampled_path(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, blk.planes, 4 * blk.planes, H, W, 2, dtype):
+                # (the sampled close is the row-panel kernel: the same sums as the full-resolution close only where that one takes it too)
+                step = Step('close_sampled', stride=2)
+            else:
+                step = blk.plan_close(B, H, W, dtype, nxt, first)
+            steps.append(step._replace(h1_in=bool(steps) and steps[-1].kind in ('tail_next', 'tail_next_live')))
+            if not first:
+                H, W = (H - 1) // blk.stride + 1, (W - 1) // blk.stride + 1
+        compact = steps[-1].kind == 'close_sampled' or steps[-1].compact
+        return Route(tuple(steps), ((H - 1) // 2 + 1, (W - 1) // 2 + 1) if compact else (H, W), compact)
 
     def _ends_compact(self, i):
         return i in self.compact_stages and self._dead_pixels(i)
 
-    def _live_store(self, i, blk, last, y):
-        """True when stage i ends compact through the live-store form: blk, the block before the last, is an identity block whose output
-        y-shaped map only `last` reads (conv1 from registers, the residual at the live pixels), both kernels exist for the shapes, and
-        the compact map has at least 128 pixels."""
-        if i not in self.live_store_stages or not self._dead_pixels(i) or not blk.fuse_next:
+    def _live_store(self, i, blk, last, B, H, W, dtype):
+        """True when stage i ends compact through the live-store form on a [B,H,W] map: blk, the block before the last, is an identity block
+        whose output only `last` reads (conv1 from registers, the residual at the live pixels), both kernels exist, the compact map has the
+        128 pixels of one panel, and the row-panel kernel takes the close at both sizes (its K order does not depend on the row count)."""
+        if i not in self.live_store_stages or not self._dead_pixels(i) or not blk.fuse_next or dtype not in native.FUSED_DTYPES \
+                or blk.downsample is not None or blk.stride != 1 or blk.with_dcn or last.conv1_stride != 1:
             return False
-        if blk.downsample is not None or blk.stride != 1 or blk.with_dcn or last.conv1_stride != 1 or y.dtype not in (torch.bfloat16, torch.float16, native.SPLIT):
+        P, C, LH, LW = blk.planes, 4 * blk.planes, (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        if not native.tail_next_live_path(B, H, W, P, C, last.planes, 2, dtype) or B * LH * LW < 128 \
+                or native.conv2d_path(B, H, W, P, C, dtype=dtype, tile=native.TILE_HINT) != 1:
             return False
-        B, H, W, _ = y.shape
-        if not native.tail_next_live_path(B, H, W, blk.planes, 4 * blk.planes, last.planes, 2, y.dtype):
-            return False
-        return last.live_close_supported(B, H, W, y.dtype, 2, plain_close=i not in self.compact_stages)
+        if i in self.compact_stages:
+            return native.close_sampled_path(B, LH, LW, P, C, LH, LW, 1, dtype)
+        return native.conv2d_path(B, LH, LW, P, C, dtype=dtype, tile=native.TILE_HINT) == 1
 
     def _dead_pixels(self, i):
         """True when nothing reads stage i's output but the stride-2 1x1 convs (conv1 and downsample) of a caffe-style stage i + 1
         (resnet.py:127-132,283-296): three quarters of its pixels are dead, and its last block computes the live quarter only
-        (Bottleneck.forward_sampled_nhwc).  Few-row split-K (native.fewrow_split) picks its K slices by the row count, so the
+        (Bottleneck.close_sampled).  Few-row split-K (native.fewrow_split) picks its K slices by the row count, so the
         compact 3x3 would sum in another order than the full one: full resolution there."""
         if not self.skip_dead_pixels or i + 1 >= len(self.res_layers) or i in self.out_indices or native.fewrow_enabled():
             return False
@@ -461,46 +501,45 @@ class ResNet(nn.Module, PackedMixin):
         return (nxt.style == 'caffe' and nxt.conv1_stride == 2 and nxt.conv2_stride == 1 and nxt.conv1.kernel_size == (1, 1)
                 and ds is not None and ds[0].kernel_size == (1, 1) and ds[0].stride == (2, 2))
 
+    def _stem(self, x, p):
+        """conv1 7x7/2 + bn1 + relu + maxpool 3x3/2 of x [B,3,H,W] -> physical NHWC in the compute dtype.  forward_train_nhwc never reaches
+        the split-half branch of the generic route (training runs f32 or bf16)."""
+        dt = self.compute_dtype
+        if dt in native.FUSED_DTYPES and self.fused_stem:
+            return native.stem_fused(x.contiguous().float(), p['fused'], p['fused_bias'])
+        # generic route (f32 / split-half modes): patch matrix + GEMM + pooling
+        cols, OH, OW = native.im2col_stem(x.contiguous().float(), dt, STEM_KP)
+        # split half is pooled in f32 (max does not act per half plane): the GEMM hands its f32 tile over directly; the cast is a no-op otherwise
+        y = native.gemm(cols, p['stem'][0], p['stem'][1], relu=True, out_f32=dt == native.SPLIT).view(x.shape[0], OH, OW, 64)
+        return native.cast(native.maxpool3x3s2_nhwc(y), dt)
+
     def forward(self, x, out=None):
         """x [B,3,H,W] f32 -> tuple of logical-NCHW feature maps (resnet.py:522-533).  out: a contiguous NHWC tensor of
         out_shape_nhwc(...) in the compute dtype that receives the (single) returned map, e.g. a slice of a larger batch."""
         if not x.is_cuda:
             raise NotImplementedError('ResNet runs on the GPU only (no CPU fallback)')
-        p = self.packed(x.device)
-        dt = self.compute_dtype
-        if dt in (torch.bfloat16, torch.float16, native.SPLIT) and self.fused_stem:
-            y = native.stem_fused(x.contiguous().float(), p['fused'], p['fused_bias'])
-        else:  # generic route (f32 / split-half modes): patch matrix + GEMM + pooling
-            cols, OH, OW = native.im2col_stem(x.contiguous().float(), dt, STEM_KP)
-            if dt == native.SPLIT:   # pooled in f32 (max does not act per half plane): the GEMM hands its f32 tile over directly
-                y = native.gemm(cols, p['stem'][0], p['stem'][1], relu=True, out_f32=True).view(x.shape[0], OH, OW, 64)
-                y = native.cast(native.maxpool3x3s2_nhwc(y), dt)
-            else:
-                y = native.gemm(cols, p['stem'][0], p['stem'][1], relu=True).view(x.shape[0], OH, OW, 64)
-                y = native.maxpool3x3s2_nhwc(y)
-        outs = []
-        compact = False
-        if out is not None:
-            assert len(self.out_indices) == 1, 'out= needs a single returned map'
+        y = self._stem(x, self.packed(x.device))
+        outs, compact = [], False   # compact: y holds every second pixel of every second row of the previous stage's output
+        assert out is None or len(self.out_indices) == 1, 'out= needs a single returned map'
         for i, name in enumerate(self.res_layers):
             blocks = list(getattr(self, name))
+            route = self.stage_route(i, y.shape[0], y.shape[1], y.shape[2], self.compute_dtype, compact)
             h1 = None
-            compact_in, compact = compact, False   # y holds every second pixel of every second row of the previous stage's output
-            live = False   # y holds the live quarter of the block input only (the block before the last stored nothing else)
-            for j, blk in enumerate(blocks):
-                last = out is not None and i == self.out_indices[0] and j == len(blocks) - 1
-                if j >= 1 and j + 2 == len(blocks) and self._live_store(i, blk, blocks[j + 1], y):
-                    full_hw = tuple(y.shape[1:3])
-                    y, h1 = blk.forward_nhwc(y, h1=h1, nxt=blocks[j + 1], live_stride=2)
-                    live = tuple(y.shape[1:3]) != full_hw
-                elif j + 1 < len(blocks):  # the next block's conv1 rides on this block's tail where a kernel exists
-                    y, h1 = blk.forward_nhwc(y, h1=h1, nxt=blocks[j + 1], compact_in=compact_in and j == 0)
-                elif live:
-                    y, compact = blk.forward_sampled_nhwc(None, h1=h1, resid_compact=y, plain_close=i not in self.compact_stages)
-                elif self._ends_compact(i):
-                    y, compact = blk.forward_sampled_nhwc(y, h1=h1)
+            for j, (blk, step) in enumerate(zip(blocks, route.steps)):
+                assert step.h1_in == (h1 is not None), (i, j, step)
+                first = compact and j == 0
+                if step.compact:
+                    y, h1 = blk.close_compact(y, h1, plain=step.kind == 'conv'), None
+                elif step.kind == 'close_sampled':
+                    y, h1 = blk.close_sampled(y, h1, step.stride), None
+                elif step.kind == 'tail_next_live':
+                    y, h1 = blk.close_next_live(y, blk.body(y, h1), blocks[j + 1])
+                elif step.kind == 'tail_next':   # the next block's conv1 rides on this block's close
+                    y, h1 = blk.close_next(y, blk.body(y, h1, first), blocks[j + 1], step, first)
                 else:
-                    y = blk.forward_nhwc(y, out=out if last else None, h1=h1, compact_in=compact_in and j == 0)
+                    dst = out if out is not None and i == self.out_indices[0] and j + 1 == len(blocks) else None
+                    y, h1 = blk.close(y, blk.body(y, h1, first), step, dst, first), None
+            compact = route.compact
             if i in self.out_indices:
                 outs.append(as_logical(y))
             if out is not None and i == self.out_indices[0]:
@@ -511,15 +550,8 @@ class ResNet(nn.Module, PackedMixin):
         """Training forward in the compute dtype (f32 = parity mode, bf16 = throughput mode with f32 master weights): the
         frozen stem and stages (`frozen_stages`, BatchNorm everywhere) run the inference kernels without a graph, the remaining stages are autograd graphs of HIP convs (Bottleneck.forward_train_nhwc).
         -> the last out_indices map, physical NHWC."""
-        p = self.packed(x.device)
-        dt = self.compute_dtype
         with torch.no_grad():
-            if dt in (torch.bfloat16, torch.float16, native.SPLIT) and self.fused_stem:
-                y = native.stem_fused(x.contiguous().float(), p['fused'], p['fused_bias'])
-            else:
-                cols, OH, OW = native.im2col_stem(x.contiguous().float(), dt, STEM_KP)
-                y = native.gemm(cols, p['stem'][0], p['stem'][1], relu=True).view(x.shape[0], OH, OW, 64)
-                y = native.maxpool3x3s2_nhwc(y)
+            y = self._stem(x, self.packed(x.device))
             for i, name in enumerate(self.res_layers):
                 if i + 1 <= self.frozen_stages:
                     for blk in getattr(self, name):

@@ -26,6 +26,7 @@ ABI_VERSION = 7
 # (`set_compute_dtype(model, native.SPLIT)`).
 SPLIT = torch.int32
 COMPUTE_DTYPES = (torch.bfloat16, torch.float16, SPLIT, torch.float32)
+FUSED_DTYPES = COMPUTE_DTYPES[:3]   # the formats the fused stem and the fused Bottleneck entries have kernels for
 DTYPE_NAMES = {torch.bfloat16: 'bf16', torch.float16: 'f16', SPLIT: 'f16x2', torch.float32: 'f32'}
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 
@@ -239,16 +240,13 @@ def _stream():
     return ctypes.c_void_p(_raw_stream())
 
 
+DTYPE_CODES = {torch.float32: HVR_F32, torch.bfloat16: HVR_BF16, torch.float16: HVR_F16, SPLIT: HVR_F16S}
+
+
 def _dt(t):
-    if t.dtype == torch.float32:
-        return HVR_F32
-    if t.dtype == torch.bfloat16:
-        return HVR_BF16
-    if t.dtype == torch.float16:
-        return HVR_F16
-    if t.dtype == SPLIT:
-        return HVR_F16S
-    raise HvrError('unsupported tensor dtype %s (float32 / bfloat16 / float16 / the split-half container int32)' % t.dtype)
+    if t.dtype not in DTYPE_CODES:
+        raise HvrError('unsupported tensor dtype %s (float32 / bfloat16 / float16 / the split-half container int32)' % t.dtype)
+    return DTYPE_CODES[t.dtype]
 
 
 def _need_cuda(*ts):
@@ -259,6 +257,16 @@ def _need_cuda(*ts):
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _out(out, shape, dtype, device):
+    """The `out=` contract of the wrappers (the caller-allocates contract of the C ABI): `out` when given -- a contiguous tensor of exactly
+    this shape, dtype and device, e.g. a slice of a larger batch -- else a fresh one."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    assert tuple(out.shape) == tuple(shape) and out.dtype == dtype and out.is_contiguous() and out.device == device, \
+        (tuple(out.shape), tuple(shape), out.dtype, dtype)
+    return out
 
 
 # ---- optional per-call timing with HIP events on the launch stream (used by bench.py) ----
@@ -404,10 +412,7 @@ def gemm_splitk(a, w, staging=None, tile=None, out=None):
     assert a.stride(1) == 1 and w.stride(1) == 1
     M, K = a.shape
     N = w.shape[0]
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    else:
-        assert out.dtype == torch.float32 and tuple(out.shape) == (M, N) and out.is_contiguous() and out.device == a.device
+    out = _out(out, (M, N), torch.float32, a.device)
     d = GemmDesc(A=a.data_ptr(), B=w.data_ptr(), C=out.data_ptr(), M=M, N=N, K=K, lda=a.stride(0), ldb=w.stride(0), ldc=N,
                  bias=None, resid=None, ldr=0, relu=0, out_f32=int(a.dtype != torch.float32), dtype=_dt(a),
                  staging=STAGING if staging is None else staging, tile_hint=TILE_HINT if tile is None else tile)
@@ -426,8 +431,7 @@ def gemm_splitk_batched(a, w, out=None):
     assert a.stride(2) == 1 and w.stride(2) == 1 and a.stride(1) == a.shape[2] and w.stride(1) == w.shape[2]
     G, M, K = a.shape
     N = w.shape[1]
-    if out is None:
-        out = torch.empty((G, M, N), dtype=torch.float32, device=a.device)
+    out = _out(out, (G, M, N), torch.float32, a.device)
     d = GemmDesc(A=a.data_ptr(), B=w.data_ptr(), C=out.data_ptr(), M=M, N=N, K=K, lda=K, ldb=K, ldc=N, bias=None, resid=None, ldr=0, relu=0,
                  out_f32=int(a.dtype != torch.float32), dtype=_dt(a), staging=STAGING, tile_hint=TILE_HINT)
     nbytes = lib().hvr_gemm_splitk_batched_workspace_bytes(M, N, K, _dt(a), G)
@@ -445,13 +449,7 @@ def conv2d_nhwc(x, w, bias=None, resid=None, relu=False, stride=1, pad=0, dil=1,
     Cout, KH, KW, _ = w.shape
     OH = (H + 2 * pad - dil * (KH - 1) - 1) // stride + 1
     OW = (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1
-    odt = torch.float32 if out_f32 else x.dtype
-    if out is not None:
-        assert tuple(out.shape) == (B, OH, OW, Cout) and out.dtype == odt and out.is_contiguous() and out.device == x.device, \
-            (tuple(out.shape), (B, OH, OW, Cout), out.dtype)
-        y = out
-    else:
-        y = torch.empty((B, OH, OW, Cout), dtype=odt, device=x.device)
+    y = _out(out, (B, OH, OW, Cout), torch.float32 if out_f32 else x.dtype, x.device)
     d = ConvDesc(x=x.data_ptr(), w=w.data_ptr(), y=y.data_ptr(), B=B, H=H, W=W, Cin=Cin, Cout=Cout, KH=KH, KW=KW,
                  stride=stride, pad=pad, dil=dil,
                  bias=bias.data_ptr() if bias is not None else None,
@@ -481,18 +479,48 @@ def conv2d_nhwc(x, w, bias=None, resid=None, relu=False, stride=1, pad=0, dil=1,
     return y
 
 
+# ---- the fused Bottleneck entries.  Each descriptor is built once, by shape, with placeholder addresses: a query by shape (*_path) hands
+# it to the library as it is -- nothing is launched, no memory is touched -- and the launch points it at its tensors first.
+_PH = 1 << 20   # the placeholder address: 128-byte aligned, as every map the torch allocator or backbone.as_nhwc hands out
+
+
+def _launch_fused(entry, d, nbytes, detail, args):
+    """Launches `entry` on descriptor d inside a 'conv_expand' span (the HBM-bound row-panel family, accounted in the bytes it moves)."""
+    tag = 'conv_expand ' + detail % args if _prof is not None and _prof['detail'] else 'conv_expand'
+    with _span(tag, float(nbytes)):
+        _check(getattr(lib(), entry)(ctypes.byref(d), _stream()), entry)
+
+
+def _point(d, **tensors):
+    """Descriptor d with the address of every tensor given (None: the field stays as the shape form left it)."""
+    for field, t in tensors.items():
+        if t is not None:
+            setattr(d, field, t.data_ptr())
+    return d
+
+
+def _tail_form(code, B, OH, OW, C1, Cout, x_hwc=None, stride2=1, relu=True):
+    """x_hwc: (H2, W2, C2) of the input map a projection block samples at stride2 as its second K segment; None: no second segment."""
+    H2, W2, C2 = x_hwc if x_hwc is not None else (OH, OW, 0)
+    return TailDesc(h=_PH, x=_PH if x_hwc is not None else None, w=_PH, y=_PH, B=B, OH=OH, OW=OW, C1=C1, H2=H2, W2=W2, C2=C2,
+                    stride2=int(stride2) if x_hwc is not None else 1, Cout=Cout, bias=_PH, relu=int(relu), dtype=code)
+
+
 def _tail_desc(h, x, w, bias, stride2, relu, y):
     B, OH, OW, C1 = h.shape
-    _, H2, W2, C2 = x.shape
-    return TailDesc(h=h.data_ptr(), x=x.data_ptr(), w=w.data_ptr(), y=y.data_ptr() if y is not None else 1 << 20, B=B, OH=OH, OW=OW, C1=C1,
-                    H2=H2, W2=W2, C2=C2, stride2=int(stride2), Cout=w.shape[0], bias=bias.data_ptr(), relu=int(relu), dtype=_dt(h))
+    return _point(_tail_form(_dt(h), B, OH, OW, C1, w.shape[0], tuple(x.shape[1:]), stride2, relu), h=h, x=x, w=w, bias=bias, y=y)
+
+
+def tail_path(B, OH, OW, C1, Cout, x_hwc, stride2=1, dtype=torch.bfloat16):
+    """Whether hvr_bottleneck_tail has a fused kernel for a projection block of these shapes (bf16 / half, C1 + C2 in {128, 384}, ...)."""
+    return bool(lib().hvr_bottleneck_tail_supported(ctypes.byref(_tail_form(DTYPE_CODES.get(dtype, HVR_F32), B, OH, OW, C1, Cout, x_hwc, stride2))))
 
 
 def bottleneck_tail_supported(h, x, w, bias, stride2):
-    """True when hvr_bottleneck_tail has a fused kernel for these shapes (bf16, C1 + C2 in {128, 384}, ...)."""
+    """tail_path for these tensors (on the device, bf16 / half, one dtype, contiguous)."""
     if not (h.is_cuda and h.dtype in (torch.bfloat16, torch.float16) and x.dtype == h.dtype and h.is_contiguous() and x.is_contiguous()):
         return False
-    return bool(lib().hvr_bottleneck_tail_supported(ctypes.byref(_tail_desc(h, x, w, bias, stride2, True, None))))
+    return tail_path(h.shape[0], h.shape[1], h.shape[2], h.shape[3], w.shape[0], tuple(x.shape[1:]), stride2, h.dtype)
 
 
 def bottleneck_tail(h, x, w, bias, stride2=1, relu=True, out=None):
@@ -501,46 +529,48 @@ def bottleneck_tail(h, x, w, bias, stride2=1, relu=True, out=None):
     _need_cuda(h, x, w, bias)
     B, OH, OW, C1 = h.shape
     Cout = w.shape[0]
-    if out is not None:
-        assert tuple(out.shape) == (B, OH, OW, Cout) and out.dtype == h.dtype and out.is_contiguous()
-        y = out
-    else:
-        y = torch.empty((B, OH, OW, Cout), dtype=h.dtype, device=h.device)
+    y = _out(out, (B, OH, OW, Cout), h.dtype, h.device)
     d = _tail_desc(h, x, w, bias, stride2, relu, y)
-    tag, work = 'conv_expand', float((h.numel() + B * OH * OW * x.shape[3] + y.numel() + w.numel()) * h.element_size())
-    if _prof is not None and _prof['detail']:
-        tag = 'conv_expand tail %dx%d %d+%d->%d s%d' % (OH, OW, C1, x.shape[3], Cout, stride2)
-    with _span(tag, work):
-        _check(lib().hvr_bottleneck_tail(ctypes.byref(d), _stream()), 'hvr_bottleneck_tail')
+    _launch_fused('hvr_bottleneck_tail', d, (h.numel() + B * OH * OW * x.shape[3] + y.numel() + w.numel()) * h.element_size(),
+                  'tail %dx%d %d+%d->%d s%d', (OH, OW, C1, x.shape[3], Cout, stride2))
     return y
 
 
-def _tail_next_desc(h, x, resid, w, bias, stride2, wn, bias_n, y, hn):
-    B, OH, OW, C1 = h.shape
-    ph = 1 << 20  # placeholder address for the support query
-    if x is not None:
-        t = _tail_desc(h, x, w, bias, stride2, True, y)
-    else:
-        t = TailDesc(h=h.data_ptr(), x=None, w=w.data_ptr(), y=y.data_ptr() if y is not None else ph, B=B, OH=OH, OW=OW, C1=C1,
-                     H2=OH, W2=OW, C2=0, stride2=1, Cout=w.shape[0], bias=bias.data_ptr(), relu=1, dtype=_dt(h))
-    d = TailNextDesc(tail=t, resid=resid.data_ptr() if resid is not None else None, wn=wn.data_ptr(), bias_n=bias_n.data_ptr(),
-                     hn=hn.data_ptr() if hn is not None else ph, Cn=wn.shape[0])
-    if h.dtype == SPLIT:   # both products: scaled split activations x scaled split weights -> a scaled split activation
+def _tail_next_form(code, B, OH, OW, C1, Cout, Cn, x_hwc=None, stride2=1):
+    """x_hwc as _tail_form: given for a projection block (its input map is the second K segment), None for an identity block (a residual map)."""
+    d = TailNextDesc(tail=_tail_form(code, B, OH, OW, C1, Cout, x_hwc, stride2), resid=_PH if x_hwc is None else None, wn=_PH, bias_n=_PH,
+                     hn=_PH, Cn=Cn)
+    if code == HVR_F16S:   # both products: scaled split activations x scaled split weights -> a scaled split activation
         d.alpha, d.beta = _split_factors(False, None)
     return d
 
 
+def _tail_next_desc(h, x, resid, w, bias, stride2, wn, bias_n, y, hn):
+    B, OH, OW, C1 = h.shape
+    d = _tail_next_form(_dt(h), B, OH, OW, C1, w.shape[0], wn.shape[0], tuple(x.shape[1:]) if x is not None else None, stride2)
+    _point(d.tail, h=h, x=x, w=w, bias=bias, y=y)
+    d.resid = resid.data_ptr() if resid is not None else None
+    return _point(d, wn=wn, bias_n=bias_n, hn=hn)
+
+
+def tail_next_path(B, OH, OW, C1, Cout, Cn, x_hwc=None, stride2=1, dtype=torch.bfloat16):
+    """Whether hvr_bottleneck_tail_next runs these shapes: (Cout, Cn) = (256, 64) / (512, 128) in bf16 / half, the projection form (x_hwc) or the
+    identity form; split half: the identity form with (Cout, Cn) = (256, 64)."""
+    return bool(lib().hvr_bottleneck_tail_next_supported(ctypes.byref(
+        _tail_next_form(DTYPE_CODES.get(dtype, HVR_F32), B, OH, OW, C1, Cout, Cn, x_hwc, stride2))))
+
+
 def bottleneck_tail_next_supported(h, x, resid, w, bias, stride2, wn, bias_n):
-    """True when hvr_bottleneck_tail_next runs these shapes: (Cout, Cn) = (256, 64) / (512, 128), bf16 / half, contiguous maps;
-    split half: the identity form (resid given, x None) with (Cout, Cn) = (256, 64)."""
+    """tail_next_path for these tensors (on the device, bf16 / half / split half, one dtype, contiguous, exactly one of x and resid)."""
     ts = [t for t in (h, x, resid) if t is not None]
-    if not all(t.is_cuda and t.dtype in (torch.bfloat16, torch.float16, SPLIT) and t.dtype == h.dtype and t.is_contiguous() for t in ts):
+    if not all(t.is_cuda and t.dtype in FUSED_DTYPES and t.dtype == h.dtype and t.is_contiguous() for t in ts):
         return False
     if h.dtype == SPLIT and (x is not None or wn.dtype != SPLIT or w.dtype != SPLIT):
         return False
     if (x is None) == (resid is None) or wn.dim() != 2 or wn.shape[1] != w.shape[0] or not wn.is_contiguous():
         return False
-    return bool(lib().hvr_bottleneck_tail_next_supported(ctypes.byref(_tail_next_desc(h, x, resid, w, bias, stride2, wn, bias_n, None, None))))
+    return tail_next_path(h.shape[0], h.shape[1], h.shape[2], h.shape[3], w.shape[0], wn.shape[0], tuple(x.shape[1:]) if x is not None else None,
+                          stride2, h.dtype)
 
 
 def bottleneck_tail_next(h, x, resid, w, bias, wn, bias_n, stride2=1, out=None):
@@ -549,20 +579,13 @@ def bottleneck_tail_next(h, x, resid, w, bias, wn, bias_n, stride2=1, out=None):
     _need_cuda(h, w, bias, wn, bias_n)
     B, OH, OW, C1 = h.shape
     Cout, Cn = w.shape[0], wn.shape[0]
-    if out is not None:
-        assert tuple(out.shape) == (B, OH, OW, Cout) and out.dtype == h.dtype and out.is_contiguous()
-        y = out
-    else:
-        y = torch.empty((B, OH, OW, Cout), dtype=h.dtype, device=h.device)
+    y = _out(out, (B, OH, OW, Cout), h.dtype, h.device)
     hn = torch.empty((B, OH, OW, Cn), dtype=h.dtype, device=h.device)
     d = _tail_next_desc(h, x, resid, w, bias, stride2, wn, bias_n, y, hn)
     side = x if x is not None else resid
-    tag = 'conv_expand'
-    work = float((h.numel() + B * OH * OW * side.shape[3] + y.numel() + hn.numel() + w.numel() + wn.numel()) * h.element_size())
-    if _prof is not None and _prof['detail']:
-        tag = 'conv_expand tail+next %dx%d %d+%d->%d->%d' % (OH, OW, C1, x.shape[3] if x is not None else 0, Cout, Cn)
-    with _span(tag, work):
-        _check(lib().hvr_bottleneck_tail_next(ctypes.byref(d), _stream()), 'hvr_bottleneck_tail_next')
+    _launch_fused('hvr_bottleneck_tail_next', d,
+                  (h.numel() + B * OH * OW * side.shape[3] + y.numel() + hn.numel() + w.numel() + wn.numel()) * h.element_size(),
+                  'tail+next %dx%d %d+%d->%d->%d', (OH, OW, C1, x.shape[3] if x is not None else 0, Cout, Cn))
     return y, hn
 
 
@@ -573,7 +596,7 @@ def _tail_next_live_desc(h, resid, w, bias, wn, bias_n, live_stride, y, hn):
 def bottleneck_tail_next_live_supported(h, resid, w, bias, wn, bias_n, live_stride=2):
     """True when hvr_bottleneck_tail_next_live runs these shapes: an identity block, (Cout, Cn, C1) = (256, 64, 64) / (512, 128, 128) in
     bf16 / half, (256, 64, 64) in split half, contiguous maps, at least 128 pixels."""
-    if not all(t.is_cuda and t.dtype in (torch.bfloat16, torch.float16, SPLIT) and t.dtype == h.dtype and t.is_contiguous() for t in (h, resid, w, wn)):
+    if not all(t.is_cuda and t.dtype in FUSED_DTYPES and t.dtype == h.dtype and t.is_contiguous() for t in (h, resid, w, wn)):
         return False
     if h.dim() != 4 or resid.dim() != 4 or wn.dim() != 2 or w.dim() != 2 or wn.shape[1] != w.shape[0] or int(live_stride) < 1:
         return False
@@ -583,15 +606,8 @@ def bottleneck_tail_next_live_supported(h, resid, w, bias, wn, bias_n, live_stri
 
 
 def tail_next_live_path(B, OH, OW, C1, Cout, Cn, live_stride=2, dtype=torch.bfloat16):
-    """Whether hvr_bottleneck_tail_next_live has a kernel for an identity block of these shapes (the query by shape, as conv2d_path: nothing
-    is launched and no memory is touched, the descriptor carries placeholder addresses)."""
-    fake = 1 << 20
-    code = {torch.bfloat16: HVR_BF16, torch.float16: HVR_F16, SPLIT: HVR_F16S}.get(dtype, HVR_F32)
-    t = TailDesc(h=fake, x=None, w=fake, y=fake, B=B, OH=OH, OW=OW, C1=C1, H2=OH, W2=OW, C2=0, stride2=1, Cout=Cout, bias=fake, relu=1, dtype=code)
-    nd = TailNextDesc(tail=t, resid=fake, wn=fake, bias_n=fake, hn=fake, Cn=Cn)
-    if dtype == SPLIT:
-        nd.alpha, nd.beta = _split_factors(False, None)
-    d = TailNextLiveDesc(next=nd, live_stride=int(live_stride))
+    """Whether hvr_bottleneck_tail_next_live has a kernel for an identity block of these shapes (the query by shape: nothing is launched)."""
+    d = TailNextLiveDesc(next=_tail_next_form(DTYPE_CODES.get(dtype, HVR_F32), B, OH, OW, C1, Cout, Cn), live_stride=int(live_stride))
     return bool(lib().hvr_bottleneck_tail_next_live_supported(ctypes.byref(d)))
 
 
@@ -606,57 +622,43 @@ def bottleneck_tail_next_live(h, resid, w3, b3, wn, bn, live_stride=2, out=None,
     Cout, Cn, s = w3.shape[0], wn.shape[0], int(live_stride)
     LH, LW = (OH - 1) // s + 1, (OW - 1) // s + 1
     assert h.is_contiguous() and resid.is_contiguous() and tuple(resid.shape) == (B, OH, OW, Cout) and resid.dtype == h.dtype
-    if out is not None:
-        assert tuple(out.shape) == (B, LH, LW, Cout) and out.dtype == h.dtype and out.is_contiguous()
-        y = out
-    else:
-        y = torch.empty((B, LH, LW, Cout), dtype=h.dtype, device=h.device)
-    if out_hn is not None:
-        assert tuple(out_hn.shape) == (B, OH, OW, Cn) and out_hn.dtype == h.dtype and out_hn.is_contiguous()
-        hn = out_hn
-    else:
-        hn = torch.empty((B, OH, OW, Cn), dtype=h.dtype, device=h.device)
+    y, hn = _out(out, (B, LH, LW, Cout), h.dtype, h.device), _out(out_hn, (B, OH, OW, Cn), h.dtype, h.device)
     d = _tail_next_live_desc(h, resid, w3, b3, wn, bn, s, y, hn)
-    tag = 'conv_expand'
     # bytes it moves: h, the residual and hn at every pixel, y at the live ones, W3 and Wn once
-    work = float((h.numel() + resid.numel() + y.numel() + hn.numel() + w3.numel() + wn.numel()) * h.element_size())
-    if _prof is not None and _prof['detail']:
-        tag = 'conv_expand tail+next live/%d %dx%d %d+0->%d->%d' % (s, OH, OW, C1, Cout, Cn)
-    with _span(tag, work):
-        _check(lib().hvr_bottleneck_tail_next_live(ctypes.byref(d), _stream()), 'hvr_bottleneck_tail_next_live')
+    _launch_fused('hvr_bottleneck_tail_next_live', d, (h.numel() + resid.numel() + y.numel() + hn.numel() + w3.numel() + wn.numel()) * h.element_size(),
+                  'tail+next live/%d %dx%d %d+0->%d->%d', (s, OH, OW, C1, Cout, Cn))
     return y, hn
+
+
+def _close_sampled_form(code, B, OH, OW, C1, Cout, RH, RW, stride, relu=True):
+    d = CloseSampledDesc(h=_PH, w=_PH, resid=_PH, y=_PH, B=B, OH=OH, OW=OW, C1=C1, Cout=Cout, RH=RH, RW=RW, rstride=int(stride), bias=_PH,
+                         relu=int(relu), dtype=code)
+    if code == HVR_F16S:
+        d.alpha, d.beta = _split_factors(False, None)
+    return d
 
 
 def _close_sampled_desc(h, w, bias, resid, stride, relu, y):
     B, OH, OW, C1 = h.shape
     _, RH, RW, Cout = resid.shape
-    d = CloseSampledDesc(h=h.data_ptr(), w=w.data_ptr(), resid=resid.data_ptr(), y=y.data_ptr() if y is not None else 1 << 20, B=B, OH=OH, OW=OW,
-                         C1=C1, Cout=Cout, RH=RH, RW=RW, rstride=int(stride), bias=bias.data_ptr(), relu=int(relu), dtype=_dt(h))
-    if h.dtype == SPLIT:
-        d.alpha, d.beta = _split_factors(False, None)
-    return d
+    return _point(_close_sampled_form(_dt(h), B, OH, OW, C1, Cout, RH, RW, stride, relu), h=h, w=w, bias=bias, resid=resid, y=y)
 
 
 def bottleneck_close_sampled_supported(h, w, bias, resid, stride):
     """True when hvr_bottleneck_close_sampled runs these shapes: bf16 / half / split half on the row-panel kernels, contiguous maps,
     h [B,OH,OW,C1] compact, resid [B,RH,RW,Cout] at full resolution with (OH - 1) stride < RH and (OW - 1) stride < RW."""
-    if not (h.is_cuda and h.dtype in (torch.bfloat16, torch.float16, SPLIT) and resid.dtype == h.dtype and w.dtype == h.dtype
+    if not (h.is_cuda and h.dtype in FUSED_DTYPES and resid.dtype == h.dtype and w.dtype == h.dtype
             and h.is_contiguous() and resid.is_contiguous() and w.is_contiguous() and h.dim() == 4 and resid.dim() == 4):
         return False
     if h.shape[0] != resid.shape[0] or w.numel() != resid.shape[3] * h.shape[3] or w.shape[0] != resid.shape[3]:
         return False
-    return bool(lib().hvr_bottleneck_close_sampled_supported(ctypes.byref(_close_sampled_desc(h, w, bias, resid, stride, True, None))))
+    return close_sampled_path(h.shape[0], h.shape[1], h.shape[2], h.shape[3], resid.shape[3], resid.shape[1], resid.shape[2], stride, h.dtype)
 
 
 def close_sampled_path(B, OH, OW, C1, Cout, RH, RW, stride=2, dtype=torch.bfloat16):
     """Whether hvr_bottleneck_close_sampled has a kernel for these shapes (the query by shape: placeholder addresses, nothing is launched)."""
-    fake = 1 << 20
-    code = {torch.bfloat16: HVR_BF16, torch.float16: HVR_F16, SPLIT: HVR_F16S}.get(dtype, HVR_F32)
-    d = CloseSampledDesc(h=fake, w=fake, resid=fake, y=fake, B=B, OH=OH, OW=OW, C1=C1, Cout=Cout, RH=RH, RW=RW, rstride=int(stride), bias=fake,
-                         relu=1, dtype=code)
-    if dtype == SPLIT:
-        d.alpha, d.beta = _split_factors(False, None)
-    return bool(lib().hvr_bottleneck_close_sampled_supported(ctypes.byref(d)))
+    return bool(lib().hvr_bottleneck_close_sampled_supported(ctypes.byref(
+        _close_sampled_form(DTYPE_CODES.get(dtype, HVR_F32), B, OH, OW, C1, Cout, RH, RW, stride))))
 
 
 def bottleneck_close_sampled(h, w, bias, resid, stride=2, relu=True, out=None):
@@ -669,29 +671,20 @@ def bottleneck_close_sampled(h, w, bias, resid, stride=2, relu=True, out=None):
     _, RH, RW, Cout = resid.shape
     assert h.is_contiguous() and resid.is_contiguous() and w.is_contiguous() and resid.dtype == h.dtype and w.dtype == h.dtype
     assert w.shape[0] == Cout and w.numel() == Cout * C1 and resid.shape[0] == B, (tuple(w.shape), tuple(resid.shape))
-    if out is not None:
-        assert tuple(out.shape) == (B, OH, OW, Cout) and out.dtype == h.dtype and out.is_contiguous()
-        y = out
-    else:
-        y = torch.empty((B, OH, OW, Cout), dtype=h.dtype, device=h.device)
+    y = _out(out, (B, OH, OW, Cout), h.dtype, h.device)
     d = _close_sampled_desc(h, w, bias, resid, stride, relu, y)
     # bytes it moves: h, the sampled residual rows and y once, W once
-    tag, work = 'conv_expand', float((B * OH * OW * (C1 + 2 * Cout) + Cout * C1) * h.element_size())
-    if _prof is not None and _prof['detail']:
-        tag = 'conv_expand sampled %dx%d<-%dx%d %d->%d k1+res s%d' % (OH, OW, RH, RW, C1, Cout, stride)
-    with _span(tag, work):
-        _check(lib().hvr_bottleneck_close_sampled(ctypes.byref(d), _stream()), 'hvr_bottleneck_close_sampled')
+    _launch_fused('hvr_bottleneck_close_sampled', d, (B * OH * OW * (C1 + 2 * Cout) + Cout * C1) * h.element_size(),
+                  'sampled %dx%d<-%dx%d %d->%d k1+res s%d', (OH, OW, RH, RW, C1, Cout, stride))
     return y
 
 
 def conv2d_path(B, H, W, Cin, Cout, k=1, stride=1, pad=0, dil=1, dtype=torch.bfloat16, resid=True, bias=True, out_f32=False, tile=0):
     """Which kernel hvr_conv2d_nhwc would run for a conv of this shape (0 tile engine, 1 expand.hip panel kernel, < 0 rejected).
     Nothing is launched and no memory is touched: the descriptor carries placeholder (16-byte aligned) addresses."""
-    fake = 1 << 20
-    d = ConvDesc(x=fake, w=fake, y=fake, B=B, H=H, W=W, Cin=Cin, Cout=Cout, KH=k, KW=k, stride=stride, pad=pad, dil=dil,
-                 bias=fake if bias else None, resid=fake if resid else None, relu=1, out_f32=int(out_f32),
-                 dtype={torch.bfloat16: HVR_BF16, torch.float16: HVR_F16, SPLIT: HVR_F16S}.get(dtype, HVR_F32), staging=STAGING,
-                 tile_hint=tile, zero=fake)
+    d = ConvDesc(x=_PH, w=_PH, y=_PH, B=B, H=H, W=W, Cin=Cin, Cout=Cout, KH=k, KW=k, stride=stride, pad=pad, dil=dil,
+                 bias=_PH if bias else None, resid=_PH if resid else None, relu=1, out_f32=int(out_f32),
+                 dtype=DTYPE_CODES.get(dtype, HVR_F32), staging=STAGING, tile_hint=tile, zero=_PH)
     return int(lib().hvr_conv2d_path(ctypes.byref(d)))
 
 
@@ -903,11 +896,7 @@ def relation_probs(q, k, scale, staging=None, out=None):
     Mq, D = q.shape
     Mk = k.shape[0]
     ldp = relation_ldp(Mk)
-    if out is None:
-        P = torch.empty((Mq, ldp), dtype=q.dtype, device=q.device)
-    else:
-        assert out.shape == (Mq, ldp) and out.dtype == q.dtype and out.device == q.device and out.is_contiguous()
-        P = out
+    P = _out(out, (Mq, ldp), q.dtype, q.device)
     ws = _workspace(lib().hvr_relation_probs_workspace_bytes(Mq, Mk), q.device, 'relation_probs')
     _check(lib().hvr_relation_probs(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(P), ldp, Mq, Mk, D, float(scale), _dt(q),
                                     STAGING if staging is None else staging, _ptr(ws), ws.numel(), _stream()), 'hvr_relation_probs')
@@ -975,11 +964,7 @@ def relu_bwd_t(dy, y, ldt, dzt_out=None):
     assert dy.dim() == 2 and dy.shape == y.shape and dy.dtype == y.dtype
     R, C = dy.shape
     dz = torch.empty_like(dy)
-    if dzt_out is None:
-        dzt = torch.empty((C, ldt), dtype=dy.dtype, device=dy.device)
-    else:
-        assert tuple(dzt_out.shape) == (C, ldt) and dzt_out.dtype == dy.dtype and dzt_out.is_contiguous()
-        dzt = dzt_out
+    dzt = _out(dzt_out, (C, ldt), dy.dtype, dy.device)
     _check(lib().hvr_relu_bwd_t(_ptr(dy), _ptr(y), _ptr(dz), _ptr(dzt), ldt, R, C, _dt(dy), _stream()), 'hvr_relu_bwd_t')
     return dz, dzt
 
@@ -989,10 +974,7 @@ def im2col_t(x, KH, KW, pad, dil, ldt, out=None):
     _need_cuda(x)
     x = x.contiguous()
     B, H, W, Cin = x.shape
-    if out is None:
-        out = torch.empty((KH * KW * Cin, ldt), dtype=x.dtype, device=x.device)
-    else:
-        assert tuple(out.shape) == (KH * KW * Cin, ldt) and out.dtype == x.dtype and out.is_contiguous()
+    out = _out(out, (KH * KW * Cin, ldt), x.dtype, x.device)
     _check(lib().hvr_im2col_t(_ptr(x), _ptr(out), ldt, B, H, W, Cin, KH, KW, pad, dil, _dt(x), _stream()), 'hvr_im2col_t')
     return out
 
@@ -1001,11 +983,7 @@ def colsum(dy, out=None):
     """[M, N] -> f32 [N] column sums (bias gradient); out: a contiguous f32 [N] tensor to write into."""
     _need_cuda(dy)
     assert dy.dim() == 2 and dy.stride(1) == 1
-    if out is None:
-        db = torch.empty(dy.shape[1], dtype=torch.float32, device=dy.device)
-    else:
-        assert out.dtype == torch.float32 and tuple(out.shape) == (dy.shape[1],) and out.is_contiguous() and out.device == dy.device
-        db = out
+    db = _out(out, (dy.shape[1],), torch.float32, dy.device)
     nbytes = lib().hvr_colsum_workspace_bytes(dy.shape[0], dy.shape[1])
     ws = _workspace(nbytes, dy.device, 'colsum') if nbytes else None
     _check(lib().hvr_colsum(_ptr(dy), _ptr(db), dy.shape[0], dy.shape[1], dy.stride(0), _dt(dy), _ptr(ws), nbytes, _stream()), 'hvr_colsum')
@@ -1315,9 +1293,7 @@ def roi_align_fwd(feat, rois, out_h, out_w, spatial_scale, sample_num, layout, o
     else:
         B, H, W, C = feat.shape
         shape = (K, out_h, out_w, C)
-    if out is None:
-        out = torch.empty(shape, dtype=feat.dtype, device=feat.device)
-    assert tuple(out.shape) == shape and out.dtype == feat.dtype and out.device == feat.device and out.is_contiguous()
+    out = _out(out, shape, feat.dtype, feat.device)
     assert feat.is_contiguous()
     with _span('roi_align', float((feat.numel() + out.numel()) * feat.element_size() + rois.numel() * 4)):
         _check(lib().hvr_roi_align_fwd(_ptr(feat), _ptr(rois), _ptr(out), B, C, H, W, K, out_h, out_w, float(spatial_scale),
@@ -1356,10 +1332,7 @@ def deform_im2col(x, om, KH, KW, stride, pad, dil, deformable_groups, modulated,
     assert x.is_contiguous() and om.dtype == torch.float32 and om.is_contiguous() and tuple(om.shape[:3]) == (B, OH, OW), \
         (tuple(x.shape), tuple(om.shape), (B, OH, OW))
     M, K = B * OH * OW, KH * KW * Cin
-    if out is None:
-        out = torch.empty((M, K), dtype=x.dtype, device=x.device)
-    else:
-        assert tuple(out.shape) == (M, K) and out.dtype == x.dtype and out.is_contiguous() and out.device == x.device, (tuple(out.shape), (M, K))
+    out = _out(out, (M, K), x.dtype, x.device)
     # bytes: four corner vectors read and one written per (pixel, tap), the offsets once per pixel
     with _span('deform_im2col', float(5 * M * K * x.element_size() + M * om.shape[3] * 4)):
         _check(lib().hvr_deform_im2col(_ptr(x), _ptr(om), _ptr(out), B, H, W, Cin, KH, KW, int(stride), int(pad), int(dil),
@@ -1384,10 +1357,7 @@ def deform_conv2d_nhwc(x, om, w, bias, relu, stride, pad, dil, deformable_groups
     B, H, W, Cin = x.shape
     Cout, KH, KW, _ = w.shape
     OH, OW = _deform_out_hw(H, W, KH, KW, stride, pad, dil)
-    if out is None:
-        out = torch.empty((B, OH, OW, Cout), dtype=x.dtype, device=x.device)
-    else:
-        assert tuple(out.shape) == (B, OH, OW, Cout) and out.dtype == x.dtype and out.is_contiguous() and out.device == x.device
+    out = _out(out, (B, OH, OW, Cout), x.dtype, x.device)
     rows = DEFORM_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)
     K = KH * KW * Cin
     fpc = B if rows <= 0 else max(1, min(B, rows // (OH * OW)))   # frames per chunk
@@ -1678,10 +1648,7 @@ def transpose_pad(x, ldt, out=None):
     _need_cuda(x)
     x = x.contiguous()
     R, C = x.shape
-    if out is None:
-        out = torch.empty((C, ldt), dtype=x.dtype, device=x.device)
-    else:
-        assert tuple(out.shape) == (C, ldt) and out.dtype == x.dtype and out.is_contiguous()
+    out = _out(out, (C, ldt), x.dtype, x.device)
     _check(lib().hvr_transpose_pad(_ptr(x), _ptr(out), R, C, C, ldt, _dt(x), _stream()), 'hvr_transpose_pad')
     return out
 

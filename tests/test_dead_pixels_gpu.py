@@ -230,14 +230,19 @@ def test_backbone_keeps_full_resolution_where_the_pixels_are_read(style, out_ind
 
 @pytest.mark.parametrize('dt', MODES, ids=MODE_IDS)
 @pytest.mark.parametrize('B,H,W', SIZES)
-def test_last_block_of_a_stage_on_the_live_pixels(B, H, W, dt):
-    """Bottleneck.forward_sampled_nhwc = forward_nhwc at [:, ::2, ::2]; below one 128-row panel it returns the full map and says so."""
-    from hvrnet_amd.backbone import set_compute_dtype
-    blk = set_compute_dtype(_net().layer1[2], dt)
+def test_last_block_of_a_stage_on_the_live_pixels(B, H, W, dt, monkeypatch):
+    """Bottleneck.close_sampled = forward_nhwc at [:, ::2, ::2]; below one 128-row panel the route (ResNet.stage_route, without the
+    live-store form in front) says the full-resolution close, which returns the full map."""
+    from hvrnet_amd.backbone import ResNet, set_compute_dtype
+    net = _net()
+    blk = set_compute_dtype(net.layer1[2], dt)
+    monkeypatch.setattr(ResNet, 'live_store_stages', ())
+    step = net.stage_route(0, B, H, W, dt).steps[-1]
+    compact = (step.kind, step.stride) == ('close_sampled', 2)
     x = _to(_rand((B, H, W, 256), 21).abs(), dt)
     with torch.no_grad():
         full = blk.forward_nhwc(x)
-        y, compact = blk.forward_sampled_nhwc(x)
+        y = blk.close_sampled(x) if compact else blk.close(x, blk.body(x), step)
     assert compact == (B * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1) >= 128)
     assert torch.equal(y, full[:, ::2, ::2] if compact else full)
 
