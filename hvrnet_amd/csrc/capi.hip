@@ -68,6 +68,8 @@ hipError_t run_roi_align_fwd(const void*, const float*, void*, int, int, int, in
 hipError_t run_roi_align_bwd(const float*, const float*, float*, int, int, int, int, int, int, float, int, int, hipStream_t);
 hipError_t run_deform_im2col(const void*, const float*, void*, int, int, int, int, int, int, int, int, int, int, int, int, long, int, int,
                              hipStream_t);
+hipError_t run_deform_roi_pool(const void*, const float*, const float*, const float*, void*, int, int, int, int, int, int, int, int, int, int, int,
+                               float, float, long, long, int, hipStream_t);
 size_t nms_workspace_bytes(int P, int n);
 hipError_t run_nms_batched(const float*, int, int, float, int, int, int, long long*, int*, void*, hipStream_t, int band = 0,
                            int* band_done = nullptr);
@@ -1339,6 +1341,39 @@ int hvr_deform_im2col(const void* x, const float* om, void* col, int B, int H, i
   return check_launch(run_deform_im2col(x, om, col, B, H, W, Cin, (int)OH, (int)OW, KH, KW, stride, pad, dil, deformable_groups, (long)ldo,
                                         modulated != 0, dtype, (hipStream_t)stream),
                       "hvr_deform_im2col");
+}
+
+// ---- deformable RoI pooling (dpool.hip) ----
+int hvr_deform_roi_pool_fwd(const void* feat, const float* rois, const float* trans, const float* mask_logit, void* out, int B, int H, int W, int C,
+                            int K, int PH, int PW, int out_channels, int group_size, int part_size, int num_classes, int sample_per_part,
+                            float spatial_scale, float trans_std, int64_t ldt, int64_t ldm, int dtype, void* stream) {
+  if (!valid_dtype(dtype)) return fail(HVR_EINVAL, "hvr_deform_roi_pool_fwd: bad dtype %d", dtype);
+  if (dtype == HVR_F16S) return fail(HVR_EINVAL, "hvr_deform_roi_pool_fwd: no split-half instance (pool in f32 and convert)");
+  if (PH != PW) return fail(HVR_EINVAL, "hvr_deform_roi_pool_fwd: out_size %d x %d is not square", PH, PW);
+  if (K < 0 || B <= 0 || H <= 0 || W <= 0 || C <= 0 || PH <= 0 || out_channels <= 0 || group_size <= 0 || part_size <= 0 || num_classes <= 0 ||
+      sample_per_part <= 0)
+    return fail(HVR_EINVAL, "hvr_deform_roi_pool_fwd: bad shape K=%d B=%d H=%d W=%d C=%d out_size=%d out_channels=%d group_size=%d part_size=%d classes=%d "
+                "sample_per_part=%d", K, B, H, W, C, PH, out_channels, group_size, part_size, num_classes, sample_per_part);
+  if ((long)C != (long)out_channels * group_size * group_size)
+    return fail(HVR_EINVAL, "hvr_deform_roi_pool_fwd: C=%d is not out_channels * group_size^2 = %d * %d^2", C, out_channels, group_size);
+  if (out_channels % num_classes)
+    return fail(HVR_EINVAL, "hvr_deform_roi_pool_fwd: out_channels=%d is not a multiple of the %d offset classes", out_channels, num_classes);
+  if (!(trans_std >= 0.f && trans_std <= 1.f)) return fail(HVR_EINVAL, "hvr_deform_roi_pool_fwd: trans_std=%g is outside [0, 1]", (double)trans_std);
+  if (PH > 1024 || part_size > 1024 || sample_per_part > 1024 || (long)H * W >= (1L << 31))
+    return fail(HVR_EUNSUPPORTED, "hvr_deform_roi_pool_fwd: out_size, part_size, sample_per_part above 1024 or a map of 2^31 pixels");
+  if (K == 0) return HVR_OK;
+  if (!feat || !rois || !out) return fail(HVR_EINVAL, "hvr_deform_roi_pool_fwd: null pointer");
+  if (trans && ldt < (long)num_classes * 2 * part_size * part_size)
+    return fail(HVR_EINVAL, "hvr_deform_roi_pool_fwd: ldt=%ld is below the %ld offsets of a RoI", (long)ldt, (long)num_classes * 2 * part_size * part_size);
+  if (!trans && num_classes != 1) return fail(HVR_EINVAL, "hvr_deform_roi_pool_fwd: %d offset classes without offsets", num_classes);
+  if (mask_logit && ldm < (long)PH * PW) return fail(HVR_EINVAL, "hvr_deform_roi_pool_fwd: ldm=%ld is below the %d mask logits of a RoI", (long)ldm, PH * PW);
+  const uintptr_t es = (uintptr_t)elem_size(dtype) - 1;
+  if ((reinterpret_cast<uintptr_t>(feat) & es) || (reinterpret_cast<uintptr_t>(out) & es) || (reinterpret_cast<uintptr_t>(rois) & 3) ||
+      (reinterpret_cast<uintptr_t>(trans) & 3) || (reinterpret_cast<uintptr_t>(mask_logit) & 3))
+    return fail(HVR_EINVAL, "hvr_deform_roi_pool_fwd: misaligned pointer");
+  return check_launch(run_deform_roi_pool(feat, rois, trans, mask_logit, out, B, H, W, C, K, PH, out_channels, group_size, part_size, num_classes,
+                                          sample_per_part, spatial_scale, trans_std, (long)ldt, (long)ldm, dtype, (hipStream_t)stream),
+                      "hvr_deform_roi_pool_fwd");
 }
 
 // ---- NMS ----

@@ -222,6 +222,16 @@ class _WindowDetector(TwoStageDetector):
             raise NotImplementedError('per-RoI shared head (feat_from_shared_head=False) is outside the hot path')
         return self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
 
+    def _train_roi_layer(self):
+        """The RoI layer of the training paths: they differentiate through RoIAlign; every other roi_layer (the deformable
+        pooling packs of ops.py) is inference only."""
+        from . import ops
+        layer = self.bbox_roi_extractor.roi_layers[0]
+        if not isinstance(layer, ops.RoIAlign):
+            raise NotImplementedError('training runs through RoIAlign only: roi_layer %s is inference only (it has no backward)'
+                                      % type(layer).__name__)
+        return layer
+
     rpn_side_stream = os.environ.get('HVR_RPN_SIDE', '1') != '0'
 
     def _side_stream(self, device):
@@ -707,10 +717,10 @@ class SelsaRCNN(_WindowDetector):
         HIP (f32; enable_training + set_compute_dtype(float32) first).  The assigner / sampler / RPN-loss steps that
         produce rois and targets in the reference are not part of this build yet.  -> dict(loss_cls, loss_bbox, acc, total)."""
         from . import ops
+        layer = self._train_roi_layer()
         c4 = self.backbone.forward_train_nhwc(img)
         c5 = self.shared_head.forward_train_nhwc(c4)
-        feats = ops.roi_align(c5.permute(0, 3, 1, 2), rois, self.bbox_roi_extractor.roi_layers[0].out_size,
-                              self.bbox_roi_extractor.roi_layers[0].spatial_scale, self.bbox_roi_extractor.roi_layers[0].sample_num)
+        feats = ops.roi_align(c5.permute(0, 3, 1, 2), rois, layer.out_size, layer.spatial_scale, layer.sample_num)
         logits = self.bbox_head.forward_train(feats, cur_range)
         return self.bbox_head.loss_train(logits, labels, label_weights, bbox_targets, bbox_weights)
 
@@ -726,6 +736,7 @@ class SelsaRCNN(_WindowDetector):
         draws.  -> dict(loss_rpn_cls [1-list], loss_rpn_bbox [1-list], loss_cls, loss_bbox, acc); summing the 'loss' entries
         and calling backward() trains (the reference's parse_losses does the same sum)."""
         from . import native, ops, targets as T, train_ops as TO
+        layer = self._train_roi_layer()
         if self.train_cfg is None:
             raise ValueError('this detector was built without train_cfg (hvrnet_amd.config.selsa_train_config, or the reference config file)')
         key = self.key_dim
@@ -769,7 +780,6 @@ class SelsaRCNN(_WindowDetector):
         n_key = sampling_results[key].bboxes.shape[0]
         cur_range = dict(start=key * n_key, length=n_key)
         c5 = self.shared_head.forward_train_nhwc(c4)
-        layer = self.bbox_roi_extractor.roi_layers[0]
         feats = ops.roi_align(c5.permute(0, 3, 1, 2), rois, layer.out_size, layer.spatial_scale, layer.sample_num)
         logits = self.bbox_head.forward_train(feats, cur_range)
         labels, label_w, bbox_t, bbox_w = T.bbox_target([sampling_results[key]], [gt_b], [gt_l], rcnn_cfg,
@@ -880,6 +890,7 @@ class HNMBRCNN(_WindowDetector):
         keys: optional {'rcnn': [[f32 [num_gt + nms_post] per frame] per chosen video]} replacing the sampler's draws.
         -> dict(loss_cls_1, acc_1, loss_bbox_1, loss_cls_2, acc_2, loss_bbox_2, loss_trip)."""
         from . import ops, targets as T
+        layer = self._train_roi_layer()
         if self.train_cfg is None:
             raise ValueError('this detector was built without train_cfg (hvrnet_amd.config.hvr_train_config, or the reference config file)')
         if self.key_dim != 0:
@@ -903,7 +914,6 @@ class HNMBRCNN(_WindowDetector):
         bbox_assigner = T.build_assigner(rcnn_cfg.assigner)
         bbox_sampler = T.build_sampler(rcnn_cfg.sampler, context=self)
         proposal_cfg = self.train_cfg.get('rpn_proposal', self.test_cfg.rpn)
-        layer = self.bbox_roi_extractor.roi_layers[0]
         c4k = torch.cat([c4.permute(0, 2, 3, 1)[v * F_:(v + 1) * F_] for v in chosen], 0)          # the chosen videos' frames
         metas_k = [m for v in chosen for m in img_meta[v * F_:(v + 1) * F_]]
         with torch.no_grad():

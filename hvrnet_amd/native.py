@@ -167,6 +167,7 @@ SYMBOLS = {
     'hvr_roi_align_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
     'hvr_deform_im2col_supported': (_i, [_i, _i, _i]),
     'hvr_deform_im2col': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i, _vp]),
+    'hvr_deform_roi_pool_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i64, _i64, _i, _vp]),
     'hvr_nms_workspace_bytes': (_sz, [_i]),
     'hvr_nms_first': (_i, [_vp, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'hvr_nms': (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -1372,6 +1373,59 @@ def deform_conv2d_nhwc(x, om, w, bias, relu, stride, pad, dil, deformable_groups
             col = ws[:m * K * x.element_size()].view(x.dtype).view(m, K)
             deform_im2col(x[b0:b0 + nb], om[b0:b0 + nb], KH, KW, stride, pad, dil, deformable_groups, modulated, out=col)
             gemm(col, w2, bias, relu=relu, out=y2[b0 * OH * OW:b0 * OH * OW + m])
+    return out
+
+
+def _dpool_rows(t, K, what):
+    """A per-RoI f32 operand of deform_roi_pool as [K, n] rows with unit column stride (a column slice of a wider GEMM output
+    keeps its row stride) -> (tensor, n, row stride)."""
+    assert t.dtype == torch.float32 and t.shape[0] == K, (what, t.dtype, tuple(t.shape), K)
+    if t.dim() != 2:
+        assert t.is_contiguous(), what
+        t = t.view(K, -1)
+    assert t.shape[1] > 0 and (K <= 1 or (t.stride(1) == 1 and t.stride(0) >= t.shape[1])), (what, tuple(t.shape), t.stride())
+    return t, t.shape[1], (t.stride(0) if K > 1 else max(t.stride(0), t.shape[1]))
+
+
+def deform_roi_pool(feat_nhwc, rois, trans, mask_logit, out_size, out_channels, group_size, part_size, sample_per_part, spatial_scale,
+                    trans_std, out=None):
+    """Deformable position-sensitive RoI pooling (hvr_deform_roi_pool_fwd; the rule is stated in include/hvr_hip.h): feat_nhwc
+    [B,H,W,C] physical NHWC with C = out_channels * group_size^2, rois [K,5] -> [K, P, P, out_channels] of the map's dtype.
+    trans: None (no_trans) or f32 [K, ncls*2*ps*ps] / [K, ncls*2, ps, ps] (x offsets then y offsets per class); mask_logit: None or
+    f32 [K, P*P] / [K, 1, P, P], the logits whose sigmoid multiplies the result.  Both may be column slices of wider f32 GEMM
+    outputs: the row strides are passed on.  out_size: an int or a square pair.  A split-half map is pooled in f32 and handed
+    back in the split format, as roi_align_fwd does.  out: a contiguous tensor of the result's shape and dtype to write into.
+    Byte model of the span: per output bin up to 4 * sample_per_part^2 corner vectors of out_channels read (fewer where samples share
+    cells or are skipped; they hit L2) and one written, plus the rois, offsets and logits once."""
+    _need_cuda(feat_nhwc, rois, trans, mask_logit)
+    ph, pw = (out_size, out_size) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
+    if feat_nhwc.dtype == SPLIT:
+        assert out is None
+        return cast(deform_roi_pool(cast(feat_nhwc, torch.float32), rois, trans, mask_logit, (ph, pw), out_channels, group_size, part_size,
+                                    sample_per_part, spatial_scale, trans_std), SPLIT)
+    rois = rois.contiguous().float()
+    assert feat_nhwc.dim() == 4 and feat_nhwc.is_contiguous() and rois.dim() == 2 and rois.shape[1] == 5, (tuple(feat_nhwc.shape), tuple(rois.shape))
+    B, H, W, C = feat_nhwc.shape
+    K = rois.shape[0]
+    part_size = ph if part_size is None else int(part_size[0] if isinstance(part_size, (tuple, list)) else part_size)
+    ncls, ldt, ldm = 1, 0, 0
+    if trans is not None:
+        trans, n, ldt = _dpool_rows(trans, K, 'trans')
+        if part_size <= 0 or n % (2 * part_size * part_size):
+            raise HvrError('deform_roi_pool: %d offsets per RoI are no multiple of 2 * part_size^2 = %d' % (n, 2 * part_size * part_size))
+        ncls = n // (2 * part_size * part_size)
+    if mask_logit is not None:
+        mask_logit, n, ldm = _dpool_rows(mask_logit, K, 'mask_logit')
+        if n != ph * pw:
+            raise HvrError('deform_roi_pool: %d mask logits per RoI, out_size is %d x %d' % (n, ph, pw))
+    out = _out(out, (K, ph, pw, int(out_channels)), feat_nhwc.dtype, feat_nhwc.device)
+    es = feat_nhwc.element_size()
+    work = float(K * ph * pw * out_channels * es * (4 * sample_per_part * sample_per_part + 1) + rois.numel() * 4
+                 + (0 if trans is None else K * ncls * 2 * part_size * part_size * 4) + (0 if mask_logit is None else K * ph * pw * 4))
+    with _span('deform_roi_pool', work):
+        _check(lib().hvr_deform_roi_pool_fwd(_ptr(feat_nhwc), _ptr(rois), _ptr(trans), _ptr(mask_logit), _ptr(out), B, H, W, C, K, ph, pw,
+                                             int(out_channels), int(group_size), part_size, ncls, int(sample_per_part), float(spatial_scale),
+                                             float(trans_std), ldt, ldm, _dt(feat_nhwc), _stream()), 'hvr_deform_roi_pool_fwd')
     return out
 
 

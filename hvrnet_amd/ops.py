@@ -10,6 +10,9 @@ signatures and error behaviour:
   soft_nms(dets, iou_thr, method='linear', sigma=0.5, min_score=1e-3)      nms/nms_wrapper.py:64-102
   seq_nms(boxes, scores, score_thr, link_iou_thr=0.5, nms_iou_thr=0.3, max_num=300, rescore='avg', *, frame_counts=None, tubes=False)   (no reference counterpart:
                                                                            Seq-NMS over one video, specified in DESIGN.md)
+  deform_roi_pooling(data, rois, offset, spatial_scale, out_size, out_channels, no_trans, group_size=1, part_size=None,
+                     sample_per_part=4, trans_std=.0)                      dcn/deform_pool.py:10-79 (inference only)
+  DeformRoIPooling / DeformRoIPoolingPack / ModulatedDeformRoIPoolingPack   dcn/deform_pool.py:82-252 (inference only)
 plus `relation(q, k, v, scale)`: the relation core as an autograd Function with a HIP backward (training path).
 CPU tensors raise NotImplementedError exactly like the reference's RoIAlign (roi_align.py:27-28);
 NMS follows the reference's CPU semantics (`IoU >= thr` suppresses, nms_cpu.cpp:55).
@@ -22,6 +25,19 @@ from torch.autograd.function import once_differentiable
 from torch.nn.modules.utils import _pair
 
 from . import native
+from .backbone import PackedMixin
+
+
+def _pad_rows(w, b, mult=4):
+    """Weight rows and bias padded with zeros to a multiple of `mult` outputs (the tile engine's N % 4 == 0)."""
+    n = w.shape[0]
+    npad = (n + mult - 1) // mult * mult
+    if npad == n:
+        return w.contiguous(), b.contiguous()
+    wp = torch.zeros((npad, w.shape[1]), dtype=w.dtype, device=w.device)
+    bp = torch.zeros(npad, dtype=b.dtype, device=b.device)
+    wp[:n], bp[:n] = w, b
+    return wp, bp
 
 
 def _channels_last(t):
@@ -87,6 +103,193 @@ class RoIAlign(nn.Module):
     def __repr__(self):
         return '%s(out_size=%s, spatial_scale=%s, sample_num=%s, use_torchvision=%s)' % (
             self.__class__.__name__, self.out_size, self.spatial_scale, self.sample_num, self.use_torchvision)
+
+
+def _pooling_map(data, dtype=None):
+    """The physical NHWC map behind `data` [B,C,H,W] (optionally in `dtype`): a channels_last tensor -- logical NCHW over physical
+    NHWC, what the window hands over -- is used in place; an NCHW-contiguous one is converted ONCE here (one permute launch, a
+    copy of the whole map: callers that pool repeatedly from one map should hand it over channels_last)."""
+    if _channels_last(data):
+        v = data.permute(0, 2, 3, 1)
+        return v if dtype is None or v.dtype == dtype else native.cast(v, dtype)
+    return native.nchw_to_nhwc(data.contiguous(), dtype)
+
+
+class DeformRoIPoolingFunction(Function):
+    """deform_pool.py:10-79, forward only.  data [B,C,H,W] (channels_last: in place), rois [K,5], offset [K, 2*ncls, ps, ps] (any
+    tensor when no_trans) -> the logical [K, out_channels, P, P] view of the physical [K, P, P, out_channels] result."""
+
+    @staticmethod
+    def forward(ctx, data, rois, offset, spatial_scale, out_size, out_channels, no_trans, group_size=1, part_size=None,
+                sample_per_part=4, trans_std=.0):
+        out_h, out_w = _pair(out_size)
+        assert isinstance(out_h, int) and isinstance(out_w, int)
+        assert out_h == out_w
+        part_size = out_h if part_size is None else part_size
+        assert 0.0 <= trans_std <= 1.0
+        if not data.is_cuda:
+            raise NotImplementedError
+        if rois.dim() != 2 or rois.size(1) != 5:
+            raise ValueError('wrong roi size: expected [K, 5], got %s' % (tuple(rois.shape),))
+        trans = None
+        if not no_trans:
+            trans = offset if offset.dtype == torch.float32 else native.cast(offset.contiguous(), torch.float32)
+        out = native.deform_roi_pool(_pooling_map(data), rois, trans, None, out_h, out_channels, group_size, part_size,
+                                     sample_per_part, spatial_scale, trans_std)
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        raise NotImplementedError('inference only')
+
+
+deform_roi_pooling = DeformRoIPoolingFunction.apply
+
+
+class DeformRoIPooling(nn.Module):
+
+    def __init__(self, spatial_scale, out_size, out_channels, no_trans, group_size=1, part_size=None, sample_per_part=4, trans_std=.0):
+        super(DeformRoIPooling, self).__init__()
+        self.spatial_scale = spatial_scale
+        self.out_size = _pair(out_size)
+        self.out_channels = out_channels
+        self.no_trans = no_trans
+        self.group_size = group_size
+        self.part_size = out_size if part_size is None else part_size
+        self.sample_per_part = sample_per_part
+        self.trans_std = trans_std
+
+    def forward(self, data, rois, offset):
+        if self.no_trans:
+            offset = data.new_empty(0)
+        return deform_roi_pooling(data, rois, offset, self.spatial_scale, self.out_size, self.out_channels, self.no_trans,
+                                  self.group_size, self.part_size, self.sample_per_part, self.trans_std)
+
+
+def _fc_chain(num_fcs, in_features, hidden, out_features, sigmoid):
+    """deform_pool.py:134-147 / :197-227: Linear (+ ReLU) ... Linear (+ Sigmoid), the last Linear zero-initialised."""
+    seq, ic = [], in_features
+    for i in range(num_fcs):
+        oc = hidden if i < num_fcs - 1 else out_features
+        seq.append(nn.Linear(ic, oc))
+        ic = oc
+        if i < num_fcs - 1:
+            seq.append(nn.ReLU(inplace=True))
+        elif sigmoid:
+            seq.append(nn.Sigmoid())
+    fc = nn.Sequential(*seq)
+    last = fc[-2] if sigmoid else fc[-1]
+    last.weight.data.zero_()
+    last.bias.data.zero_()
+    return fc
+
+
+class _DeformRoIPoolingPackBase(DeformRoIPooling, PackedMixin):
+    """What the two packs share: the device chain
+        pass 1   native.deform_roi_pool without offsets                       -> x [K, P, P, C] (physical)
+        layer 0  of offset_fc and mask_fc as ONE native.gemm (weight rows concatenated, ReLU in the epilogue), whenever both
+                 chains have a hidden layer; columns permuted at pack time to the (ph, pw, c) order of x's rows
+        layers   1 .. on column slices of that result; the last layer of a chain with an f32 output, its rows padded to a
+                 multiple of 4 (98 -> 100 offsets, 49 -> 52 logits: the row strides travel to the kernel)
+        pass 2   native.deform_roi_pool with the offsets and, modulated, the mask LOGITS: the sigmoid and the product happen
+                 inside the kernel
+    with no torch elementwise kernel and no host read.  The modules keep the reference's parameters (offset_fc.N.weight ...), so
+    its checkpoints load strictly.  A split-half map is pooled in f32 (converted once for both passes)."""
+
+    def _linears(self, name):
+        return [m for m in getattr(self, name, ()) if isinstance(m, nn.Linear)]
+
+    def _pack(self, dtype):
+        P, C = self.out_size[0], self.out_channels
+        p = {}
+        chains = {'off': self._linears('offset_fc'), 'mask': self._linears('mask_fc')}
+
+        def hwc(w):   # columns (c, ph, pw) -> (ph, pw, c)
+            return w.view(-1, C, P, P).permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+
+        def layer(fc, first, last):
+            w, b = fc.weight.detach().float(), fc.bias.detach().float()
+            w = hwc(w) if first else w
+            w, b = _pad_rows(w, b) if last else (w.contiguous(), b.contiguous())
+            return native.as_operand(w, dtype), b
+
+        fused = all(len(c) > 1 for c in chains.values())
+        if fused:
+            o0, m0 = chains['off'][0], chains['mask'][0]
+            p['fused0'] = (native.as_operand(hwc(torch.cat([o0.weight.detach().float(), m0.weight.detach().float()], 0)), dtype),
+                           torch.cat([o0.bias.detach().float(), m0.bias.detach().float()], 0).contiguous())
+            p['fused_split'] = o0.weight.shape[0]
+        for tag, fcs in chains.items():
+            p[tag] = [None if fused and i == 0 else layer(fc, i == 0, i == len(fcs) - 1) for i, fc in enumerate(fcs)]
+        return p
+
+    @staticmethod
+    def _chain(layers, h, start):
+        for i in range(start, len(layers)):
+            w, b = layers[i]
+            last = i == len(layers) - 1
+            h = native.gemm(h, w, b, relu=not last, out_f32=last)
+        return h
+
+    def _pool(self, fmap, rois, trans, mask_logit):
+        ps = self.part_size[0] if isinstance(self.part_size, (tuple, list)) else self.part_size   # (the reference keeps out_size as given)
+        return native.deform_roi_pool(fmap, rois, trans, mask_logit, self.out_size, self.out_channels, self.group_size, ps,
+                                      self.sample_per_part, self.spatial_scale, self.trans_std)
+
+    def forward(self, data, rois):
+        assert data.size(1) == self.out_channels
+        if not data.is_cuda:
+            raise NotImplementedError
+        dt = self.compute_dtype
+        fmap = _pooling_map(data, torch.float32 if dt == native.SPLIT else dt)
+        x = self._pool(fmap, rois, None, None)
+        K, n = rois.shape[0], self.out_size[0] * self.out_size[1]
+        if not self.no_trans and K > 0:
+            p = self.packed(data.device)
+            rows = x.view(K, -1)
+            rows = native.cast(rows, dt) if dt == native.SPLIT else rows
+            if 'fused0' in p:
+                h = native.gemm(rows, p['fused0'][0], p['fused0'][1], relu=True)
+                ho, hm = h[:, :p['fused_split']], h[:, p['fused_split']:]
+            else:
+                ho = hm = rows
+            start = 1 if 'fused0' in p else 0
+            trans = self._chain(p['off'], ho, start)[:, :2 * n]
+            mask_logit = self._chain(p['mask'], hm, start)[:, :n] if p['mask'] else None
+            x = self._pool(fmap, rois, trans, mask_logit)
+        x = native.cast(x, dt) if dt == native.SPLIT else x
+        return x.permute(0, 3, 1, 2)
+
+
+class DeformRoIPoolingPack(_DeformRoIPoolingPackBase):
+
+    def __init__(self, spatial_scale, out_size, out_channels, no_trans, group_size=1, part_size=None, sample_per_part=4, trans_std=.0,
+                 num_offset_fcs=3, deform_fc_channels=1024):
+        super(DeformRoIPoolingPack, self).__init__(spatial_scale, out_size, out_channels, no_trans, group_size, part_size,
+                                                   sample_per_part, trans_std)
+        self.num_offset_fcs = num_offset_fcs
+        self.deform_fc_channels = deform_fc_channels
+        if not no_trans:
+            n = self.out_size[0] * self.out_size[1]
+            self.offset_fc = _fc_chain(num_offset_fcs, n * out_channels, deform_fc_channels, n * 2, sigmoid=False)
+        self._init_packed()
+
+
+class ModulatedDeformRoIPoolingPack(_DeformRoIPoolingPackBase):
+
+    def __init__(self, spatial_scale, out_size, out_channels, no_trans, group_size=1, part_size=None, sample_per_part=4, trans_std=.0,
+                 num_offset_fcs=3, num_mask_fcs=2, deform_fc_channels=1024):
+        super(ModulatedDeformRoIPoolingPack, self).__init__(spatial_scale, out_size, out_channels, no_trans, group_size, part_size,
+                                                            sample_per_part, trans_std)
+        self.num_offset_fcs = num_offset_fcs
+        self.num_mask_fcs = num_mask_fcs
+        self.deform_fc_channels = deform_fc_channels
+        if not no_trans:
+            n = self.out_size[0] * self.out_size[1]
+            self.offset_fc = _fc_chain(num_offset_fcs, n * out_channels, deform_fc_channels, n * 2, sigmoid=False)
+            self.mask_fc = _fc_chain(num_mask_fcs, n * out_channels, deform_fc_channels, n, sigmoid=True)
+        self._init_packed()
 
 
 class RelationFunction(Function):

@@ -400,6 +400,54 @@ int hvr_deform_im2col(const void* x, const float* om, void* col, int B, int H, i
                       int dil, int deformable_groups, int modulated, int64_t ldo, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Deformable (position-sensitive) RoI pooling, forward only: the pooling of DCN v1 (DeformRoIPoolingPack) / v2
+ * (ModulatedDeformRoIPoolingPack).  Replaces mmdet/ops/dcn/src/deform_pool_cuda_kernel.cu:30-50 (bilinear rule), :52-140
+ * (DeformablePSROIPoolForwardKernel) and the product with the mask of mmdet/ops/dcn/deform_pool.py:249-252.
+ *   feat       [B][H][W][C]          physical NHWC, `dtype` = HVR_F32 / HVR_BF16 / HVR_F16 (no split-half instance)
+ *   rois       [K][5]                f32 (b, x1, y1, x2, y2); b is clamped into [0, B)
+ *   trans      f32 or NULL (no_trans): row n holds [ncls][2][ps][ps] (x offsets, then y offsets, per class) at row stride ldt
+ *   mask_logit f32 or NULL: row n holds [P][P] at row stride ldm; the mask is its sigmoid
+ *   out        [K][P][P][Cout]       `dtype`, allocated by the caller
+ * P = PH = PW = out_size (square), spp = sample_per_part, gs = group_size, ps = part_size, s = spatial_scale, Cout = out_channels,
+ * ncls = num_classes (1 when trans is NULL).  C == Cout * gs^2 and Cout % ncls == 0.
+ * Every step is f32 and every operation is rounded on its own (no fused multiply-add).  For output (n, ct, ph, pw):
+ *   rnd(v)   = round half AWAY from zero (C roundf)
+ *   start_w  = rnd(x1) * s - 0.5
+ *   end_w    = (rnd(x2) + 1) * s - 0.5                       h alike
+ *   roi_w    = max(end_w - start_w, f32(0.1))
+ *   bin_w    = roi_w / P
+ *   sub_w    = bin_w / spp
+ *   part_w   = floor(float(pw) / P * ps)                     part_h alike
+ *   cls      = ct / (Cout / ncls)
+ *   tx       = trans[n][cls][0][part_h][part_w] * trans_std
+ *   ty       = trans[n][cls][1][part_h][part_w] * trans_std  (both 0 when trans is NULL)
+ *   wstart   = float(pw) * bin_w + start_w
+ *   wstart   = wstart + tx * roi_w                           hstart alike with ty * roi_h
+ *   gw       = clamp(floor(float(pw) * gs / P), 0, gs - 1)   gh alike
+ *   c        = (ct * gs + gh) * gs + gw
+ *   for ih in 0..spp-1, iw in 0..spp-1 (ih outer, iw inner):
+ *       w = wstart + float(iw) * sub_w
+ *       h = hstart + float(ih) * sub_h
+ *       skip the sample if w < -0.5 or w > W - 0.5 or h < -0.5 or h > H - 0.5
+ *       w = clamp(w, 0, W - 1)
+ *       h = clamp(h, 0, H - 1)
+ *       xl = floor(w), xh = ceil(w), yl = floor(h), yh = ceil(h)
+ *       dx = w - xl, dy = h - yl
+ *       sum += (1-dx)(1-dy) v[yl][xl] + (1-dx) dy v[yh][xl] + dx (1-dy) v[yl][xh] + dx dy v[yh][xh]      (v = feat[b][.][.][c])
+ *       count += 1
+ *   out = 0 if count == 0 else sum / count
+ *   out = out * 1 / (1 + expf(-mask_logit[n][ph][pw]))       when mask_logit is given (precise expf, rounded add and divide)
+ * then ONE rounding to `dtype`.  Unlike RoIAlign: the corners are rounded, the -0.5 shift, the minimum size is 0.1, the outside
+ * test is at +-0.5 with an edge clamp, ceil (not floor + 1), the divisor counts the samples inside (an empty bin gives 0), the
+ * offset is indexed by PART and the mask by BIN.
+ * Errors: HVR_EINVAL for a non-square out_size, C != Cout * gs^2, Cout % ncls != 0, trans_std outside [0, 1], ldt < ncls*2*ps*ps,
+ * ldm < P*P, a split-half dtype, null or misaligned pointers.  No host synchronisation, no allocation.
+ * ---------------------------------------------------------------------------------- */
+int hvr_deform_roi_pool_fwd(const void* feat, const float* rois, const float* trans, const float* mask_logit, void* out, int B, int H, int W,
+                            int C, int K, int PH, int PW, int out_channels, int group_size, int part_size, int num_classes,
+                            int sample_per_part, float spatial_scale, float trans_std, int64_t ldt, int64_t ldm, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Greedy NMS.  Replaces nms_cpu.nms / nms_cuda.nms (mmdet/ops/nms/src/nms_cpu.cpp:5-71,
  * nms_kernel.cu:24-136) with no host round trip.  dets [n][5] f32 (x1,y1,x2,y2,score);
  * ge_semantics != 0 suppresses at IoU >= thr (the CPU reference), 0 at IoU > thr (the CUDA
