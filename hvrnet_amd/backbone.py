@@ -1,7 +1,8 @@
 """ResNet-C4 backbone and the res5 shared head, executed by the gfx950 implicit-GEMM kernels.
 
 Host-side mirror of mmdet/models/backbones/resnet.py (Bottleneck 86-266, make_res_layer 269-329,
-ResNet 332-543) and mmdet/models/shared_heads/res_layer.py (ResLayer 13-81): same class names,
+ResNet 332-543), mmdet/models/shared_heads/res_layer.py (ResLayer 13-81), mmdet/models/backbones/resnext.py (the grouped
+Bottleneck 12-91, ResNeXt 157-238) and mmdet/models/shared_heads/resx_layer.py (ResXLayer 15-57): same class names,
 constructor kwargs, sub-module names and parameter shapes, so `build_from_cfg` and reference
 checkpoints work unchanged.  The nn.Conv2d / nn.BatchNorm2d children only HOLD parameters; the
 forward pass runs on packed device buffers:
@@ -15,6 +16,7 @@ requires_grad=False).  There is no CPU path (native.py raises on CPU tensors).
 """
 import collections
 import itertools
+import math
 
 import torch
 import torch.nn as nn
@@ -178,16 +180,21 @@ def _w2d(wb):
 class Bottleneck(nn.Module, PackedMixin):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, style='pytorch', norm_cfg=None, dcn=None):
+    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, style='pytorch', norm_cfg=None, dcn=None, groups=1, base_width=4):
         super(Bottleneck, self).__init__()
         assert style in ['pytorch', 'caffe']
         assert dcn is None or isinstance(dcn, dict)
         self.inplanes, self.planes, self.stride, self.dilation, self.style = inplanes, planes, stride, dilation, style
+        # resnext.py:21-24: the channels of conv1's output, conv2 and conv3's input (a ResNet block: planes)
+        self.groups, self.base_width = groups, base_width
+        self.width = width = planes if groups == 1 else int(math.floor(planes * (base_width / 64))) * groups
+        if groups > 1 and dcn is not None:
+            raise NotImplementedError('dcn on a grouped Bottleneck (the dcn[\'groups\'] form of resnext.py:57-83) is not built')
         # caffe: stride on the first 1x1 (resnet.py:127-132)
         self.conv1_stride, self.conv2_stride = (1, stride) if style == 'pytorch' else (stride, 1)
         eps = (norm_cfg or {}).get('eps', 1e-5)
-        self.conv1 = nn.Conv2d(inplanes, planes, 1, stride=self.conv1_stride, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes, eps=eps)
+        self.conv1 = nn.Conv2d(inplanes, width, 1, stride=self.conv1_stride, bias=False)
+        self.bn1 = nn.BatchNorm2d(width, eps=eps)
         # resnet.py:147-186: conv2 is a (modulated) deformable 3x3 whose offsets (and mask logits) come from conv2_offset, a plain
         # biased 3x3 on the same input; fallback_on_stride keeps the plain conv where conv2 carries a stride
         self.dcn = dcn
@@ -196,18 +203,24 @@ class Bottleneck(nn.Module, PackedMixin):
         self.deformable_groups = int(dcn.get('deformable_groups', 1)) if self.with_dcn else 1
         if self.with_dcn:
             offset_channels = 27 if self.with_modulated_dcn else 18
-            self.conv2_offset = nn.Conv2d(planes, self.deformable_groups * offset_channels, 3, stride=self.conv2_stride, padding=dilation,
+            self.conv2_offset = nn.Conv2d(width, self.deformable_groups * offset_channels, 3, stride=self.conv2_stride, padding=dilation,
                                           dilation=dilation)
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride=self.conv2_stride, padding=dilation, dilation=dilation, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes, eps=eps)
-        self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
+        self.conv2 = nn.Conv2d(width, width, 3, stride=self.conv2_stride, padding=dilation, dilation=dilation, groups=groups, bias=False)
+        self.bn2 = nn.BatchNorm2d(width, eps=eps)
+        self.conv3 = nn.Conv2d(width, planes * 4, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4, eps=eps)
         self.downsample = downsample
         self._init_packed()
 
     def _pack(self, dtype):
-        p = dict(c1=fold_conv_bn(self.conv1, self.bn1, dtype), c2=fold_conv_bn(self.conv2, self.bn2, dtype),
-                 c3=fold_conv_bn(self.conv3, self.bn3, dtype))
+        p = dict(c1=fold_conv_bn(self.conv1, self.bn1, dtype), c3=fold_conv_bn(self.conv3, self.bn3, dtype))
+        if self.groups > 1:
+            # bn2 folded into the grouped weight [width,3,3,width/groups]; the operand forms (grouped, block-diagonal dense) are made by the
+            # route that first needs them (native.GroupedWeight)
+            wg, bg = fold_conv_bn(self.conv2, self.bn2, torch.float32)
+            p['c2'] = (native.GroupedWeight(wg, dtype), bg)
+        else:
+            p['c2'] = fold_conv_bn(self.conv2, self.bn2, dtype)
         if self.with_dcn:
             # the offset conv: Cout padded with zero rows to a multiple the engine takes (N % 4); its output stays f32 in every mode
             wo, bo = fold_conv_bn(self.conv2_offset, None, torch.float32)
@@ -230,13 +243,13 @@ class Bottleneck(nn.Module, PackedMixin):
         nxt, the block that reads the output, rides on the close where hvr_bottleneck_tail_next has a kernel."""
         stride = 1 if compact_in else self.stride
         OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
-        P, C, proj = self.planes, 4 * self.planes, self.downsample is not None
+        P, C, proj = self.width, 4 * self.planes, self.downsample is not None
         # split half has no second-K-segment tail: the projection is its own conv and enters the fused closing 1x1 + next conv1 as the
         # residual (the identity form of hvr_bottleneck_tail_next)
         own_ds = proj and dtype == native.SPLIT
         x_hwc = (H, W, self.inplanes) if proj and not own_ds else None
         if nxt is not None and self.fuse_next and nxt.conv1_stride == 1 and (own_ds or self.fuse_tail or not proj) \
-                and native.tail_next_path(B, OH, OW, P, C, nxt.planes, x_hwc, stride, dtype):
+                and native.tail_next_path(B, OH, OW, P, C, nxt.width, x_hwc, stride, dtype):
             return Step('tail_next', projection=x_hwc is not None, downsample=own_ds)
         if x_hwc is not None and self.fuse_tail and native.tail_path(B, OH, OW, P, C, x_hwc, stride, dtype):
             return Step('tail')
@@ -252,6 +265,8 @@ class Bottleneck(nn.Module, PackedMixin):
             om = native.conv2d_nhwc(h, p['off'][0], p['off'][1], relu=False, stride=s2, pad=self.dilation, dil=self.dilation, out_f32=True)
             return native.deform_conv2d_nhwc(h, om, p['c2'][0], p['c2'][1], True, s2, self.dilation, self.dilation, self.deformable_groups,
                                              self.with_modulated_dcn, out=out)
+        if self.groups > 1:
+            return native.conv3x3_grouped(h, p['c2'][0], p['c2'][1], True, s2, self.dilation, out=out, route=self.grouped_route)
         return native.conv2d_nhwc(h, p['c2'][0], p['c2'][1], relu=True, stride=s2, pad=self.dilation, dil=self.dilation, out=out)
 
     def close(self, x, h, step, out=None, compact_in=False):
@@ -285,7 +300,7 @@ class Bottleneck(nn.Module, PackedMixin):
         3x3 reads neighbours), conv2 at that stride, the close with the residual sampled from x -> the full output at [:, ::stride, ::stride]."""
         assert self.downsample is None and self.stride == 1 and not self.with_dcn
         B, H, W, _ = x.shape
-        hs = torch.empty((B, (H - 1) // stride + 1, (W - 1) // stride + 1, self.planes), dtype=x.dtype, device=x.device)
+        hs = torch.empty((B, (H - 1) // stride + 1, (W - 1) // stride + 1, self.width), dtype=x.dtype, device=x.device)
         self.body(x, h1, conv2_stride=stride, out=hs)
         return native.bottleneck_close_sampled(hs, *_w2d(self.packed(x.device)['c3']), x, stride=stride, relu=True)
 
@@ -306,6 +321,7 @@ class Bottleneck(nn.Module, PackedMixin):
 
     fuse_next = True   # class attributes (tests flip them to compare the fused kernels with the per-conv path); no environment switch
     fuse_tail = True
+    grouped_route = None   # conv2 of a grouped block: None = native.conv3x3_grouped chooses by shape; 'grouped' / 'dense' force one (tests, tools)
 
     def forward(self, x):
         return as_logical(self.forward_nhwc(as_nhwc(x, self.compute_dtype)))
@@ -315,6 +331,8 @@ class Bottleneck(nn.Module, PackedMixin):
         (norm_eval=True, requires_grad=False in both configs), trainable conv weights; f32, physical NHWC."""
         if self.with_dcn:
             raise NotImplementedError('deformable convs are inference only: no backward (col2im + coordinate gradients) is implemented')
+        if self.groups > 1:
+            raise NotImplementedError('grouped Bottlenecks are inference only: the grouped 3x3 conv has no backward')
         from . import train_ops as TO
         out = TO.conv_bn(x, self.conv1, self.bn1, relu=True)
         out = TO.conv_bn(out, self.conv2, self.bn2, relu=True)
@@ -322,13 +340,15 @@ class Bottleneck(nn.Module, PackedMixin):
         return TO.conv_bn(out, self.conv3, self.bn3, resid=identity, relu=True)
 
 
-def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style='pytorch', norm_cfg=None, dcn=None, **_unused):
+def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style='pytorch', norm_cfg=None, dcn=None, groups=1, base_width=4, **_unused):
     downsample = None
     eps = (norm_cfg or {}).get('eps', 1e-5)
     if stride != 1 or inplanes != planes * block.expansion:
         downsample = nn.Sequential(nn.Conv2d(inplanes, planes * block.expansion, 1, stride=stride, bias=False),
                                    nn.BatchNorm2d(planes * block.expansion, eps=eps))
     extra = {} if dcn is None else dict(dcn=dcn)
+    if groups != 1:   # resnext.py:94-154
+        extra.update(groups=groups, base_width=base_width)
     layers = [block(inplanes, planes, stride, dilation, downsample, style=style, norm_cfg=norm_cfg, **extra)]
     inplanes = planes * block.expansion
     for _ in range(1, blocks):
@@ -347,6 +367,7 @@ class ResNet(nn.Module, PackedMixin):
     """Same kwargs as the reference ResNet (resnet.py:372-395); dcn / stage_with_dcn as there (deformable conv2 in the marked
     stages, inference only); gcb / gen_attention / conv_cfg must be None."""
     arch_settings = {d: (Bottleneck, s) for d, s in ARCH_SETTINGS.items()}
+    _block_kwargs = {}   # what every block gets beyond the reference ResNet's arguments (ResNeXt: groups, base_width)
 
     def __init__(self, depth, in_channels=3, num_stages=4, strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1),
                  out_indices=(0, 1, 2, 3), style='pytorch', frozen_stages=-1, conv_cfg=None,
@@ -379,7 +400,7 @@ class ResNet(nn.Module, PackedMixin):
             name = 'layer{}'.format(i + 1)
             stage_dcn = dcn if dcn is not None and stage_with_dcn[i] else None
             self.add_module(name, make_res_layer(block, inplanes, planes, nb, stride=strides[i], dilation=dilations[i],
-                                                 style=style, norm_cfg=norm_cfg, dcn=stage_dcn))
+                                                 style=style, norm_cfg=norm_cfg, dcn=stage_dcn, **self._block_kwargs))
             inplanes = planes * block.expansion
             self.res_layers.append(name)
         self.feat_dim = block.expansion * 64 * 2 ** (len(self.stage_blocks) - 1)
@@ -457,8 +478,8 @@ class ResNet(nn.Module, PackedMixin):
             elif steps and steps[-1].kind == 'tail_next_live':
                 step = Step('close_sampled', stride=1, compact=True) if i in self.compact_stages else Step('conv', compact=True)
             elif nxt is None and self._ends_compact(i) and dtype in native.FUSED_DTYPES \
-                    and native.conv2d_path(B, H, W, blk.planes, 4 * blk.planes, dtype=dtype, tile=native.TILE_HINT) == 1 \
-                    and native.close_sampled_path(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, blk.planes, 4 * blk.planes, H, W, 2, dtype):
+                    and native.conv2d_path(B, H, W, blk.width, 4 * blk.planes, dtype=dtype, tile=native.TILE_HINT) == 1 \
+                    and native.close_sampled_path(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, blk.width, 4 * blk.planes, H, W, 2, dtype):
                 # (the sampled close is the row-panel kernel: the same sums as the full-resolution close only where that one takes it too)
                 step = Step('close_sampled', stride=2)
             else:
@@ -477,10 +498,10 @@ class ResNet(nn.Module, PackedMixin):
         whose output only `last` reads (conv1 from registers, the residual at the live pixels), both kernels exist, the compact map has the
         128 pixels of one panel, and the row-panel kernel takes the close at both sizes (its K order does not depend on the row count)."""
         if i not in self.live_store_stages or not self._dead_pixels(i) or not blk.fuse_next or dtype not in native.FUSED_DTYPES \
-                or blk.downsample is not None or blk.stride != 1 or blk.with_dcn or last.conv1_stride != 1:
+                or blk.downsample is not None or blk.stride != 1 or blk.with_dcn or blk.groups > 1 or last.conv1_stride != 1:
             return False
-        P, C, LH, LW = blk.planes, 4 * blk.planes, (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        if not native.tail_next_live_path(B, H, W, P, C, last.planes, 2, dtype) or B * LH * LW < 128 \
+        P, C, LH, LW = blk.width, 4 * blk.planes, (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        if not native.tail_next_live_path(B, H, W, P, C, last.width, 2, dtype) or B * LH * LW < 128 \
                 or native.conv2d_path(B, H, W, P, C, dtype=dtype, tile=native.TILE_HINT) != 1:
             return False
         if i in self.compact_stages:
@@ -496,8 +517,8 @@ class ResNet(nn.Module, PackedMixin):
             return False
         blocks, nxt = getattr(self, self.res_layers[i]), getattr(self, self.res_layers[i + 1])[0]
         last, ds = blocks[-1], nxt.downsample
-        if len(blocks) < 2 or last.downsample is not None or last.stride != 1 or last.with_dcn:
-            return False
+        if len(blocks) < 2 or last.downsample is not None or last.stride != 1 or last.with_dcn or last.groups > 1:
+            return False   # (a grouped stage runs at full resolution: its compact forms are not built)
         return (nxt.style == 'caffe' and nxt.conv1_stride == 2 and nxt.conv2_stride == 1 and nxt.conv1.kernel_size == (1, 1)
                 and ds is not None and ds[0].kernel_size == (1, 1) and ds[0].stride == (2, 2))
 
@@ -582,13 +603,15 @@ class ResLayer(nn.Module, PackedMixin):
         inplanes = 64 * 2 ** (stage - 1) * Bottleneck.expansion
         self.add_module('layer{}'.format(stage + 1),
                         make_res_layer(Bottleneck, inplanes, planes, stage_block, stride=stride, dilation=dilation, style=style,
-                                       norm_cfg=norm_cfg, dcn=dcn))
+                                       norm_cfg=norm_cfg, dcn=dcn, **self._block_kwargs))
         if external_conv:
             # ConvModule(2048, 256, 1): conv + bias + ReLU, parameters under new_layer_1.conv.*
             self.new_layer_1 = nn.Module()
             self.new_layer_1.conv = nn.Conv2d(2048, 256, 1)
         _freeze(self)
         self._init_packed()
+
+    _block_kwargs = {}   # what every block gets beyond the reference ResLayer's arguments (ResXLayer: groups, base_width)
 
     def init_weights(self, pretrained=None):
         if pretrained is not None:
@@ -631,3 +654,33 @@ class ResLayer(nn.Module, PackedMixin):
     def train(self, mode=True):
         super(ResLayer, self).train(False)
         return self
+
+
+@BACKBONES.register_module
+class ResNeXt(ResNet):
+    """mmdet/models/backbones/resnext.py:157-238: a ResNet whose Bottlenecks run conv1 / conv2 / conv3 at
+    width = floor(planes * base_width / 64) * groups channels with a grouped 3x3 (native.conv3x3_grouped).  groups == 1 is the ResNet.
+    Inference only; dcn is refused on grouped blocks; the grouped stages run at full resolution (no dead-pixel compaction)."""
+    arch_settings = dict(ResNet.arch_settings)
+
+    def __init__(self, groups=1, base_width=4, **kwargs):
+        self.groups, self.base_width = groups, base_width   # (plain attributes: nn.Module takes them ahead of its own __init__)
+        self._block_kwargs = dict(groups=groups, base_width=base_width) if groups != 1 else {}
+        super(ResNeXt, self).__init__(**kwargs)
+
+
+@SHARED_HEADS.register_module
+class ResXLayer(ResLayer):
+    """mmdet/models/shared_heads/resx_layer.py:15-57: ResLayer on grouped Bottlenecks, with the same hard-wired 2048 -> 256 `new_layer_1`."""
+
+    def __init__(self, depth, stage=3, stride=2, dilation=1, groups=1, base_width=4, style='pytorch', norm_cfg=dict(type='BN', requires_grad=True),
+                 norm_eval=True, with_cp=False, external_conv=False, dcn=None):
+        self.groups, self.base_width = groups, base_width   # (plain attributes: nn.Module takes them ahead of its own __init__)
+        self._block_kwargs = dict(groups=groups, base_width=base_width) if groups != 1 else {}
+        super(ResXLayer, self).__init__(depth, stage=stage, stride=stride, dilation=dilation, style=style, norm_cfg=norm_cfg, norm_eval=norm_eval,
+                                        with_cp=with_cp, external_conv=external_conv, dcn=dcn)
+
+    def forward_train_nhwc(self, y):
+        if self.groups > 1:
+            raise NotImplementedError('ResXLayer with groups > 1 is inference only: the grouped 3x3 conv has no backward')
+        return super(ResXLayer, self).forward_train_nhwc(y)

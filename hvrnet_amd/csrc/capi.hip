@@ -90,6 +90,7 @@ hipError_t run_seq_nms(const float*, const float*, int, const int*, int, int, in
                        int*, float*, int*, int, void*, int, hipStream_t);
 size_t seq_nms_workspace_bytes(int P, int F, int R, int ncls, int tubes);
 hipError_t run_stem_fused(const float*, const void*, const float*, void*, int, int, int, int, hipStream_t);
+hipError_t run_gconv3x3(const void*, const void*, void*, const float*, int, int, int, int, int, int, int, int, int, hipStream_t);
 }  // namespace hvr
 
 using namespace hvr;
@@ -590,6 +591,34 @@ int hvr_bottleneck_close_sampled(const hvr_close_sampled_desc* d, void* stream) 
     if (expand_supported(p)) return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_close_sampled");
   }
   return fail(HVR_EUNSUPPORTED, "no sampled-residual closing kernel for C1=%d Cout=%d dtype=%d (%d output pixels)", d->C1, d->Cout, d->dtype, p.M);
+}
+
+// the instance set of gconv3x3.hip (include/hvr_hip.h states it); 0 or the error
+static int gconv_check(const hvr_gconv_desc* d) {
+  if (!d) return fail(HVR_EINVAL, "null descriptor");
+  if (!valid_dtype(d->dtype)) return fail(HVR_EINVAL, "bad dtype %d", d->dtype);
+  if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(HVR_EINVAL, "empty grouped conv input %dx%dx%d", d->B, d->H, d->W);
+  if (d->C <= 0 || d->C % 64 || d->C > 2048) return fail(HVR_EINVAL, "grouped conv: C=%d is not a multiple of 64 in [64, 2048]", d->C);
+  if (d->groups <= 0 || d->C % d->groups) return fail(HVR_EINVAL, "grouped conv: groups=%d does not divide C=%d", d->groups, d->C);
+  const int Cg = d->C / d->groups;
+  if (Cg != 4 && Cg != 8 && Cg != 16 && Cg != 32) return fail(HVR_EINVAL, "grouped conv: C / groups = %d is none of 4 / 8 / 16 / 32", Cg);
+  if (d->stride != 1 && d->stride != 2) return fail(HVR_EINVAL, "grouped conv: stride %d is neither 1 nor 2", d->stride);
+  if (d->pad != d->dil || (d->dil != 1 && d->dil != 2)) return fail(HVR_EINVAL, "grouped conv: pad=%d dil=%d (pad == dil in {1, 2})", d->pad, d->dil);
+  if (!d->x || !d->w || !d->y || !d->bias) return fail(HVR_EINVAL, "grouped conv: null operand pointer (the bias is required)");
+  if (!aligned16(d->x) || !aligned16(d->w) || !aligned16(d->y) || !aligned16(d->bias)) return fail(HVR_EINVAL, "grouped conv: operands must be 16-byte aligned");
+  if ((long)d->B * ((d->H - 1) / d->stride + 1) * ((d->W - 1) / d->stride + 1) > 0x7fffffffL) return fail(HVR_EINVAL, "grouped conv: too many output pixels");
+  if (d->dtype != HVR_BF16 && d->dtype != HVR_F16)
+    return fail(HVR_EUNSUPPORTED, "grouped conv: bf16 and half operands only (f32 / split half: hvr_conv2d_nhwc on the block-diagonal dense weight)");
+  return HVR_OK;
+}
+
+int hvr_conv3x3_grouped_supported(const hvr_gconv_desc* d) { return gconv_check(d) == HVR_OK ? 1 : 0; }
+
+int hvr_conv3x3_grouped(const hvr_gconv_desc* d, void* stream) {
+  const int rc = gconv_check(d);
+  if (rc) return rc;
+  return check_launch(run_gconv3x3(d->x, d->w, d->y, d->bias, d->B, d->H, d->W, d->C, d->C / d->groups, d->stride, d->dil, d->relu, d->dtype,
+                                   (hipStream_t)stream), "hvr_conv3x3_grouped");
 }
 
 int hvr_conv2d_path(const hvr_conv_desc* d) {

@@ -64,6 +64,13 @@ class ConvDesc(ctypes.Structure):
                 ('beta', ctypes.c_float)]
 
 
+class GConvDesc(ctypes.Structure):          # hvr_gconv_desc
+    _fields_ = [('x', ctypes.c_void_p), ('w', ctypes.c_void_p), ('y', ctypes.c_void_p), ('bias', ctypes.c_void_p),
+                ('B', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('C', ctypes.c_int32),
+                ('groups', ctypes.c_int32), ('stride', ctypes.c_int32), ('pad', ctypes.c_int32), ('dil', ctypes.c_int32),
+                ('relu', ctypes.c_int32), ('dtype', ctypes.c_int32)]
+
+
 class TailDesc(ctypes.Structure):
     _fields_ = [('h', ctypes.c_void_p), ('x', ctypes.c_void_p), ('w', ctypes.c_void_p), ('y', ctypes.c_void_p),
                 ('B', ctypes.c_int32), ('OH', ctypes.c_int32), ('OW', ctypes.c_int32), ('C1', ctypes.c_int32),
@@ -114,6 +121,8 @@ SYMBOLS = {
     'hvr_conv2d_nhwc': (_i, [ctypes.POINTER(ConvDesc), _vp]),
     'hvr_conv2d_path': (_i, [ctypes.POINTER(ConvDesc)]),
     'hvr_conv2d_splitk_workspace_bytes': (_sz, [ctypes.POINTER(ConvDesc)]),
+    'hvr_conv3x3_grouped': (_i, [ctypes.POINTER(GConvDesc), _vp]),
+    'hvr_conv3x3_grouped_supported': (_i, [ctypes.POINTER(GConvDesc)]),
     'hvr_bottleneck_tail': (_i, [ctypes.POINTER(TailDesc), _vp]),
     'hvr_bottleneck_tail_supported': (_i, [ctypes.POINTER(TailDesc)]),
     'hvr_bottleneck_tail_next': (_i, [ctypes.POINTER(TailNextDesc), _vp]),
@@ -687,6 +696,74 @@ def conv2d_path(B, H, W, Cin, Cout, k=1, stride=1, pad=0, dil=1, dtype=torch.bfl
                  bias=_PH if bias else None, resid=_PH if resid else None, relu=1, out_f32=int(out_f32),
                  dtype=DTYPE_CODES.get(dtype, HVR_F32), staging=STAGING, tile_hint=tile, zero=_PH)
     return int(lib().hvr_conv2d_path(ctypes.byref(d)))
+
+
+def conv3x3_grouped_supported(B, H, W, C, groups, stride=1, dil=1, dtype=torch.bfloat16, pad=None):
+    """True where hvr_conv3x3_grouped has an instance for a grouped 3x3 of this shape (gconv3x3.hip: bf16 / half, C / groups in
+    {4, 8, 16, 32}, C % 64 == 0 up to 2048, stride 1 / 2, pad == dil in {1, 2}).  Nothing is launched: placeholder addresses."""
+    d = GConvDesc(x=_PH, w=_PH, y=_PH, bias=_PH, B=B, H=H, W=W, C=C, groups=groups, stride=stride, pad=dil if pad is None else pad, dil=dil,
+                  relu=1, dtype=DTYPE_CODES.get(dtype, -1))
+    return bool(lib().hvr_conv3x3_grouped_supported(ctypes.byref(d)))
+
+
+class GroupedWeight(object):
+    """The weight of a grouped 3x3 conv, w [C,3,3,Cg] (f32, or exactly representable in f32), in the operand format `dtype`: the grouped
+    form the kernel reads, and the block-diagonal dense form [C,3,3,C] (exact zeros outside the groups) that conv2d_nhwc takes.  Each
+    is built on first use (pack time) and kept: a model that never leaves the grouped kernel never holds the dense one."""
+
+    def __init__(self, w, dtype):
+        assert w.dim() == 4 and tuple(w.shape[1:3]) == (3, 3) and w.shape[0] % w.shape[3] == 0, tuple(w.shape)
+        self.w32, self.dtype = w.detach().float().contiguous(), dtype
+        self.C, self.Cg = int(w.shape[0]), int(w.shape[3])
+        self.groups = self.C // self.Cg
+        self._grouped = self._dense = None
+
+    def grouped(self):
+        if self._grouped is None:
+            if self.dtype == SPLIT:
+                raise HvrError('a split-half grouped weight has no grouped form (rows of %d elements; the container holds groups of 32): '
+                               'the dense route carries this mode' % self.Cg)
+            self._grouped = self.w32.to(self.dtype)
+        return self._grouped
+
+    def dense(self):
+        if self._dense is None:
+            G, Cg = self.groups, self.Cg
+            full = torch.zeros((G, Cg, 3, 3, G, Cg), dtype=torch.float32, device=self.w32.device)
+            g = torch.arange(G, device=self.w32.device)
+            full[g, :, :, :, g, :] = self.w32.view(G, Cg, 3, 3, Cg)
+            self._dense = as_operand(full.view(self.C, 3, 3, self.C), self.dtype)
+        return self._dense
+
+
+def conv3x3_grouped(x, w, bias, relu, stride, dil, out=None, route=None):
+    """act(grouped 3x3 conv of x [B,H,W,C] (physical NHWC) + bias) -> [B,OH,OW,C], pad = dil (the rule: include/hvr_hip.h,
+    hvr_conv3x3_grouped).  w: a GroupedWeight, or a [C,3,3,Cg] tensor (packed on every call: tests and tools).
+    route: None = the grouped kernel where it has an instance for this shape and format, else conv2d_nhwc on the block-diagonal dense
+    weight; 'grouped' / 'dense' force one (the forced kernel raises HvrError where it has no instance)."""
+    assert route in (None, 'grouped', 'dense'), route
+    _need_cuda(x, bias)
+    gw = w if isinstance(w, GroupedWeight) else GroupedWeight(w, x.dtype)
+    _need_cuda(gw.w32)
+    assert gw.dtype == x.dtype, (gw.dtype, x.dtype)
+    B, H, W, C = x.shape
+    if route is None:
+        route = 'grouped' if C == gw.C and conv3x3_grouped_supported(B, H, W, C, gw.groups, stride, dil, x.dtype) else 'dense'
+    if route == 'dense':
+        return conv2d_nhwc(x, gw.dense(), bias, relu=relu, stride=stride, pad=dil, dil=dil, out=out)
+    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if C != gw.C:
+        raise HvrError('hvr_conv3x3_grouped: x has %d channels, the weight %d' % (C, gw.C))
+    assert x.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == C
+    y = _out(out, (B, OH, OW, C), x.dtype, x.device)
+    # (the library checks the shape before it launches anything: a forced route outside the instance set raises here)
+    d = _point(GConvDesc(B=B, H=H, W=W, C=C, groups=gw.groups, stride=stride, pad=dil, dil=dil, relu=int(relu), dtype=_dt(x)),
+               x=x, w=gw.grouped(), y=y, bias=bias)
+    # bytes it moves: the map in and out once, the weights once
+    tag = 'gconv' if not (_prof and _prof['detail']) else 'gconv %dx%d %d/%d s%d d%d' % (H, W, C, gw.groups, stride, dil)
+    with _span(tag, float((B * H * W * C + B * OH * OW * C + 9 * C * gw.Cg) * x.element_size())):
+        _check(lib().hvr_conv3x3_grouped(ctypes.byref(d), _stream()), 'hvr_conv3x3_grouped')
+    return y
 
 
 def im2col_stem(img, dtype, kp=192):

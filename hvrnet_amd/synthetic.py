@@ -49,15 +49,16 @@ def _bn(g, sd, prefix, c, gamma_scale=1.0):
     sd[prefix + '.num_batches_tracked'] = torch.zeros((), dtype=torch.long)
 
 
-def _res_layer(g, sd, prefix, inplanes, planes, blocks):
+def _res_layer(g, sd, prefix, inplanes, planes, blocks, groups=1, base_width=4):
+    width = planes if groups == 1 else int(math.floor(planes * (base_width / 64))) * groups   # resnext.py:21-24
     for i in range(blocks):
         p = '%s.%d' % (prefix, i)
         cin = inplanes if i == 0 else planes * 4
-        sd[p + '.conv1.weight'] = _conv(g, planes, cin, 1)
-        _bn(g, sd, p + '.bn1', planes)
-        sd[p + '.conv2.weight'] = _conv(g, planes, planes, 3)
-        _bn(g, sd, p + '.bn2', planes)
-        sd[p + '.conv3.weight'] = _conv(g, planes * 4, planes, 1)
+        sd[p + '.conv1.weight'] = _conv(g, width, cin, 1)
+        _bn(g, sd, p + '.bn1', width)
+        sd[p + '.conv2.weight'] = _conv(g, width, width // groups, 3) * math.sqrt(groups)   # (fan_out counts one group's inputs: keep the output's scale)
+        _bn(g, sd, p + '.bn2', width)
+        sd[p + '.conv3.weight'] = _conv(g, planes * 4, width, 1)
         # a live but damped residual branch keeps 33 stacked blocks from blowing up
         _bn(g, sd, p + '.bn3', planes * 4, gamma_scale=0.25)
         if i == 0:
@@ -71,8 +72,8 @@ def _linear(g, sd, prefix, cout, cin, gain, conv=False):
     sd[prefix + '.bias'] = torch.randn(cout, generator=g) * 0.01
 
 
-def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024, roi_feat=256 * 49):
-    """Full detector state dict (f32, CPU) with the reference's key names."""
+def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024, roi_feat=256 * 49, groups=1, base_width=4):
+    """Full detector state dict (f32, CPU) with the reference's key names.  groups / base_width: a ResNeXt backbone + ResXLayer."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
     blocks = STAGE_BLOCKS[depth]
@@ -80,9 +81,9 @@ def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024,
     _bn(g, sd, 'backbone.bn1', 64)
     inplanes = 64
     for i in range(3):
-        _res_layer(g, sd, 'backbone.layer%d' % (i + 1), inplanes, 64 * 2 ** i, blocks[i])
+        _res_layer(g, sd, 'backbone.layer%d' % (i + 1), inplanes, 64 * 2 ** i, blocks[i], groups, base_width)
         inplanes = 64 * 2 ** i * 4
-    _res_layer(g, sd, 'shared_head.layer4', 1024, 512, blocks[3])
+    _res_layer(g, sd, 'shared_head.layer4', 1024, 512, blocks[3], groups, base_width)
     sd['shared_head.new_layer_1.conv.weight'] = _conv(g, 256, 2048, 1) * NEW_LAYER_GAIN
     sd['shared_head.new_layer_1.conv.bias'] = torch.randn(256, generator=g) * 0.01
     # RPN (12 anchors)

@@ -165,6 +165,31 @@ size_t hvr_conv2d_splitk_workspace_bytes(const hvr_conv_desc* d);
  * negative = the descriptor would be rejected. */
 int hvr_conv2d_path(const hvr_conv_desc* d);
 
+/* Grouped 3x3 convolution with fused bias + ReLU: conv2 of a ResNeXt Bottleneck with its frozen BatchNorm folded in
+ * (mmdet/models/backbones/resnext.py:47-56; csrc/gconv3x3.hip).  A descriptor of its own: hvr_conv_desc is unchanged.
+ *   x [B][H][W][C] physical NHWC; w [C][3][3][Cg] with Cg = C / groups: output channel oc belongs to group oc / Cg and reads
+ *   the input channels [g Cg, (g + 1) Cg) of that group g, w[oc][ky][kx][ci] being the weight of input channel g Cg + ci;
+ *   y [B][OH][OW][C] with OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1; bias f32 [C], required; no residual:
+ *     y[b][oy][ox][oc] = act( bias[oc] + sum_{ky, kx, ci} x[b][oy stride + (ky - 1) dil][ox stride + (kx - 1) dil][g Cg + ci] w[oc][ky][kx][ci] )
+ *   with taps outside the map contributing zero (pad == dil) and act = ReLU when relu != 0.  f32 accumulation, ONE rounding to
+ *   the stored format.
+ * Instances: dtype HVR_BF16 or HVR_F16 (x, w and y share it); Cg in {4, 8, 16, 32}; C a multiple of 64, at most 2048;
+ * stride 1 or 2; pad == dil, 1 or 2; x, w, y and bias 16-byte aligned; fewer than 2^31 output pixels.  A shape outside this
+ * set returns HVR_EINVAL, HVR_F32 / HVR_F16S operands HVR_EUNSUPPORTED (both with a message): the caller then runs
+ * hvr_conv2d_nhwc on the block-diagonal dense weight [C][3][3][C], which is the same sum with exact zeros added.  Inside a
+ * 16-channel tile the kernel multiplies the inputs of neighbouring groups by exact zeros (Cg < 16), so a non-finite input
+ * channel reaches the other outputs of its tile, as it would on the dense route.
+ * hvr_conv3x3_grouped_supported: 1 when hvr_conv3x3_grouped runs this descriptor, else 0.  A shape query: nothing is launched,
+ * pointers are inspected for alignment only. */
+typedef struct hvr_gconv_desc {
+  const void* x; const void* w; void* y;
+  const float* bias;
+  int32_t B, H, W, C, groups, stride, pad, dil;
+  int32_t relu, dtype;
+} hvr_gconv_desc;
+int hvr_conv3x3_grouped(const hvr_gconv_desc* d, void* stream);
+int hvr_conv3x3_grouped_supported(const hvr_gconv_desc* d);
+
 /* Closing 1x1 conv of a Bottleneck whose identity path is a projection -- the first block of every stage
  * (mmdet/models/backbones/resnet.py:248-264 with `downsample`, built at resnet.py:283-296):
  *     y = relu( h W3^T + x_s Wd^T + bias )
