@@ -1,12 +1,13 @@
 """hvrnet_amd -- MI355X-native HVRNet video-detection forward path.
 
 Importing the package registers the hot-path components under the reference's names
-(ResNet, ResNeXt, ResLayer, ResXLayer, RPNHead, SingleRoIExtractor, SelsaBBoxHead, HRNMPBBoxHead, SelsaRCNN, HNMBRCNN).
+(ResNet, ResNeXt, Res2Net, ResLayer, ResXLayer, Res2Layer, RPNHead, SingleRoIExtractor, SelsaBBoxHead, HRNMPBBoxHead, SelsaRCNN, HNMBRCNN).
 """
 __version__ = '0.1.0'
 
 from . import registry  # noqa: F401
-from .backbone import ResLayer, ResNet, ResNeXt, ResXLayer, enable_training, set_compute_dtype  # noqa: F401
+from .backbone import (Bottle2neck, Res2Layer, Res2Net, ResLayer, ResNet, ResNeXt, ResXLayer, enable_training, make_res2_layer,  # noqa: F401
+                       set_compute_dtype)
 from .bbox_heads import BBoxHead, HRNMPBBoxHead, SelsaBBoxHead  # noqa: F401
 from .box_ops import (bbox_flip, bbox_mapping, bbox_mapping_back, merge_aug_bboxes, merge_aug_proposals,  # noqa: F401
                       merge_aug_scores)

@@ -684,3 +684,248 @@ class ResXLayer(ResLayer):
         if self.groups > 1:
             raise NotImplementedError('ResXLayer with groups > 1 is inference only: the grouped 3x3 conv has no backward')
         return super(ResXLayer, self).forward_train_nhwc(y)
+
+
+# ---- Res2Net (mmdet/models/backbones/res2net_v1b.py) and its shared head (mmdet/models/shared_heads/res2_layer.py)
+def _scatter_slices(t, dim, width, wp, scale):
+    """t with `scale` slices of `width` along dim -> the same slices at pitch wp, exact zeros in between (the padded-slice layout)."""
+    shape = list(t.shape)
+    shape[dim] = scale * wp
+    out = torch.zeros(shape, dtype=t.dtype, device=t.device)
+    for i in range(scale):
+        out.narrow(dim, i * wp, width).copy_(t.narrow(dim, i * width, width))
+    return out
+
+
+class Bottle2neck(nn.Module, PackedMixin):
+    """res2net_v1b.py:22-100: conv1 1x1 -> `scale` slices of `width` channels; slice i < scale - 1 goes through its own 3x3
+    (+ the previous branch's output in a 'normal' block), the last slice is carried across (through a 3x3 average pool in a 'stage'
+    block); conv3 1x1 + shortcut + ReLU.  Inference only.
+    On the device the slices live at pitch Wp = width rounded up to 32 in one NHWC map of scale * Wp channels, the pad channels held at
+    exact zero by the packed weights (zero rows of conv1 and of the branch weights, zero bias, zero columns of the branch weights and
+    of conv3): every sum is the reference's with exact zeros added."""
+    expansion = 4
+    branch_route = None   # the branch convs: None = native.res2_conv3x3 chooses by shape; 'kernel' / 'composite' force one (tests, tools)
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None, baseWidth=26, scale=4, stype='normal', dilation=1, eps=1e-5):
+        super(Bottle2neck, self).__init__()
+        if scale == 1:
+            raise NotImplementedError('Bottle2neck with scale == 1 (one 3x3 over the whole width, nothing carried) is not built')
+        assert stype in ('normal', 'stage'), stype
+        self.inplanes, self.planes, self.stride, self.dilation = inplanes, planes, stride, dilation
+        width = int(math.floor(planes * (baseWidth / 64.0)))
+        self.conv1 = nn.Conv2d(inplanes, width * scale, kernel_size=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width * scale, eps=eps)
+        self.nums = scale - 1
+        if stype == 'stage':
+            self.pool = nn.AvgPool2d(kernel_size=3, stride=stride, padding=1)
+        self.convs = nn.ModuleList([nn.Conv2d(width, width, kernel_size=3, stride=stride, padding=dilation, dilation=dilation, bias=False)
+                                    for _ in range(self.nums)])
+        self.bns = nn.ModuleList([nn.BatchNorm2d(width, eps=eps) for _ in range(self.nums)])
+        self.conv3 = nn.Conv2d(width * scale, planes * self.expansion, kernel_size=1, bias=False)
+        self.bn3 = nn.BatchNorm2d(planes * self.expansion, eps=eps)
+        self.downsample = downsample
+        self.stype, self.scale, self.width = stype, scale, width
+        self.wp = native.res2_pad_width(width)
+        self._init_packed()
+
+    def _pack(self, dtype):
+        width, wp, scale = self.width, self.wp, self.scale
+        w1, b1 = fold_conv_bn(self.conv1, self.bn1, torch.float32)
+        p = dict(c1=(native.as_operand(_scatter_slices(w1, 0, width, wp, scale), dtype), _scatter_slices(b1, 0, width, wp, scale).contiguous()))
+        p['br'] = []
+        for conv, bn in zip(self.convs, self.bns):
+            w, b = fold_conv_bn(conv, bn, torch.float32)
+            wpad = torch.zeros((wp, 3, 3, wp), dtype=torch.float32, device=w.device)
+            bpad = torch.zeros((wp,), dtype=torch.float32, device=w.device)
+            wpad[:width, :, :, :width], bpad[:width] = w, b
+            p['br'].append((native.Res2Weight(wpad, dtype), bpad))
+        w3, b3 = fold_conv_bn(self.conv3, self.bn3, torch.float32)
+        p['c3'] = (native.as_operand(_scatter_slices(w3, 3, width, wp, scale), dtype), b3)
+        if self.downsample is not None:
+            p['ds'] = fold_conv_bn(self.downsample[1], self.downsample[2], dtype)
+        return p
+
+    def forward_nhwc(self, x, out=None):
+        """x [B,H,W,inplanes] physical NHWC in the compute format -> [B,OH,OW,4*planes]; out as in Bottleneck.close."""
+        p = self.packed(x.device)
+        wp, s = self.wp, self.stride
+        P = native.conv2d_nhwc(x, p['c1'][0], p['c1'][1], relu=True)
+        B, H, W, _ = P.shape
+        Q = torch.empty((B, (H - 1) // s + 1, (W - 1) // s + 1, self.scale * wp), dtype=P.dtype, device=P.device)
+        for i, (w, b) in enumerate(p['br']):
+            prev = self.stype == 'normal' and i > 0   # res2net_v1b.py:76-79: sp + spx[i], sp being the branch before
+            native.res2_conv3x3(P, i * wp, w, b, add=Q if prev else None, add_off=(i - 1) * wp if prev else 0, out=Q, out_off=i * wp, stride=s,
+                                dil=self.dilation, relu=True, route=self.branch_route)
+        if self.stype == 'stage':   # AvgPool2d(3, stride, padding=1): count_include_pad, always / 9
+            native.avgpool_nhwc(P, 3, s, 1, False, True, x_off=self.nums * wp, C=wp, out=Q, out_off=self.nums * wp)
+        else:
+            native.avgpool_nhwc(P, 1, 1, 0, False, True, x_off=self.nums * wp, C=wp, out=Q, out_off=self.nums * wp)
+        identity = x
+        if self.downsample is not None:
+            k = self.downsample[0].kernel_size
+            xi = x if k == 1 else native.avgpool_nhwc(x, k, k, 0, True, False)   # (a 1 x 1 pool at stride 1 is the identity)
+            identity = native.conv2d_nhwc(xi, p['ds'][0], p['ds'][1], relu=False)
+        return native.conv2d_nhwc(Q, p['c3'][0], p['c3'][1], resid=identity, relu=True, out=out)
+
+    def forward(self, x):
+        return as_logical(self.forward_nhwc(as_nhwc(x, self.compute_dtype)))
+
+    def forward_train_nhwc(self, x):
+        raise NotImplementedError('Bottle2neck is inference only: the slice conv and the pitched pool have no backward')
+
+
+def make_res2_layer(block, inplanes, planes, blocks, baseWidth, scale, stride=1, dilation=1, eps=1e-5):
+    """res2net_v1b.py:103-122.  The first block is the 'stage' block: it takes the stride and NOT the dilation; the others are 'normal' at
+    `dilation`.  The shortcut is AvgPool2d(stride, stride, ceil_mode=True, count_include_pad=False) -> 1x1 conv -> BN."""
+    downsample = None
+    if stride != 1 or inplanes != planes * block.expansion:
+        downsample = nn.Sequential(nn.AvgPool2d(kernel_size=stride, stride=stride, ceil_mode=True, count_include_pad=False),
+                                   nn.Conv2d(inplanes, planes * block.expansion, kernel_size=1, stride=1, bias=False),
+                                   nn.BatchNorm2d(planes * block.expansion, eps=eps))
+    layers = [block(inplanes, planes, stride, downsample=downsample, stype='stage', baseWidth=baseWidth, scale=scale, eps=eps)]
+    inplanes = planes * block.expansion
+    for _ in range(1, blocks):
+        layers.append(block(inplanes, planes, baseWidth=baseWidth, scale=scale, dilation=dilation, eps=eps))
+    return nn.Sequential(*layers)
+
+
+def _res2_refuse(conv_cfg, norm_cfg, dcn, gcb=None, gen_attention=None):
+    if dcn is not None or gcb is not None or gen_attention is not None or conv_cfg is not None:
+        raise NotImplementedError('dcn / gcb / gen_attention / conv_cfg are not built for Res2Net (the reference accepts and ignores them)')
+    if (norm_cfg or {}).get('type', 'BN') != 'BN':
+        raise NotImplementedError('only frozen BatchNorm is supported')
+
+
+@BACKBONES.register_module
+class Res2Net(nn.Module, PackedMixin):
+    """res2net_v1b.py:125-271: Res2Net-101 v1b, 26w x 4s, hard-wired -- layers (3, 4, 23, 3), a deep stem of three 3x3 convs, three
+    stages at strides (1, 2, 2) and dilation 1 -- returning ONE map: 1024 channels at stride 16.  The reference ignores strides,
+    dilations, num_stages and out_indices beyond their assertions; arguments it would silently disobey are refused here."""
+    arch_settings = {101: (Bottle2neck, (3, 4, 23, 3))}
+
+    def __init__(self, in_channels=3, num_stages=4, strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1), out_indices=(0, 1, 2, 3), style='pytorch',
+                 frozen_stages=-1, conv_cfg=None, norm_cfg=dict(type='BN', requires_grad=True), norm_eval=True, dcn=None,
+                 stage_with_dcn=(False, False, False, False), gcb=None, stage_with_gcb=(False, False, False, False), gen_attention=None,
+                 stage_with_gen_attention=((), (), (), ()), with_cp=False, zero_init_residual=True):
+        super(Res2Net, self).__init__()
+        _res2_refuse(conv_cfg, norm_cfg, dcn, gcb, gen_attention)
+        assert 1 <= num_stages <= 4 and len(strides) == len(dilations) == num_stages and max(out_indices) < num_stages
+        assert in_channels == 3
+        if tuple(strides[:3]) != (1, 2, 2)[:num_stages] or any(d != 1 for d in dilations):
+            raise ValueError('Res2Net runs three stages at strides (1, 2, 2) and dilation 1 whatever it is given (res2net_v1b.py:188-195): '
+                             'strides=%r dilations=%r would be ignored' % (tuple(strides), tuple(dilations)))
+        self.num_stages, self.strides, self.dilations, self.out_indices = num_stages, strides, dilations, out_indices
+        self.frozen_stages, self.norm_eval, self.style = frozen_stages, norm_eval, style
+        self.baseWidth, self.scale = 26, 4
+        block, layers = self.arch_settings[101]
+        eps = norm_cfg.get('eps', 1e-5)
+        self.conv1 = nn.Sequential(nn.Conv2d(3, 32, 3, 2, 1, bias=False), nn.BatchNorm2d(32, eps=eps), nn.ReLU(inplace=True),
+                                   nn.Conv2d(32, 32, 3, 1, 1, bias=False), nn.BatchNorm2d(32, eps=eps), nn.ReLU(inplace=True),
+                                   nn.Conv2d(32, 64, 3, 1, 1, bias=False))
+        self.bn1 = nn.BatchNorm2d(64, eps=eps)
+        self.layer1 = make_res2_layer(block, 64, 64, layers[0], baseWidth=self.baseWidth, scale=self.scale, eps=eps)
+        self.layer2 = make_res2_layer(block, 256, 128, layers[1], stride=2, baseWidth=self.baseWidth, scale=self.scale, eps=eps)
+        self.layer3 = make_res2_layer(block, 512, 256, layers[2], stride=2, baseWidth=self.baseWidth, scale=self.scale, eps=eps)
+        self.res_layers = ['layer1', 'layer2', 'layer3']
+        self.feat_dim = 1024
+        _freeze(self)
+        self._init_packed()
+
+    def init_weights(self, pretrained=None):
+        """res2net_v1b.py:220-232 (pretrained checkpoints are loaded by the caller via load_state_dict)."""
+        if pretrained is not None:
+            raise NotImplementedError('load checkpoints with load_state_dict (keys match the reference)')
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+        set_compute_dtype(self, self.compute_dtype)
+
+    @staticmethod
+    def stem_channels(dtype):
+        """Channels of the two 32-channel stem maps on the device: 32 zero-padded to the Cin multiple conv2d_nhwc asks of the mode."""
+        return 64 if dtype in (torch.bfloat16, torch.float16) else 32
+
+    def _pack(self, dtype):
+        cp = self.stem_channels(dtype)
+        w0, b0 = fold_conv_bn(self.conv1[0], self.conv1[1], torch.float32)    # [32,3,3,3]: stays f32 (native.stem3x3s2_first)
+        w1, b1 = fold_conv_bn(self.conv1[3], self.conv1[4], torch.float32)    # [32,3,3,32] -> zero rows and columns up to cp
+        w2, b2 = fold_conv_bn(self.conv1[6], self.bn1, torch.float32)         # [64,3,3,32] -> zero columns up to cp
+        w1p = torch.zeros((cp, 3, 3, cp), dtype=torch.float32, device=w1.device)
+        b1p = torch.zeros((cp,), dtype=torch.float32, device=w1.device)
+        w1p[:32, :, :, :32], b1p[:32] = w1, b1
+        w2p = torch.zeros((64, 3, 3, cp), dtype=torch.float32, device=w2.device)
+        w2p[:, :, :, :32] = w2
+        return dict(s0=(w0.contiguous(), b0.contiguous()), s1=(native.as_operand(w1p, dtype), b1p), s2=(native.as_operand(w2p, dtype), b2.contiguous()))
+
+    def out_shape_nhwc(self, B, H, W):
+        """Physical [B,h,w,1024] shape of the returned map for a [B,3,H,W] input: stem 3x3/2 + pool 3x3/2, then strides 1, 2, 2."""
+        h, w = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+        for _ in range(2):
+            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        return (B, h, w, 1024)
+
+    def _stem(self, x, p):
+        """conv1 (three 3x3 convs) + bn1 + ReLU + maxpool 3x3/2 of x [B,3,H,W] -> physical NHWC [B,h,w,64] in the compute format."""
+        dt = self.compute_dtype
+        y = native.stem3x3s2_first(x.contiguous().float(), p['s0'][0], p['s0'][1], dt, channels=self.stem_channels(dt))
+        y = native.conv2d_nhwc(y, p['s1'][0], p['s1'][1], relu=True, pad=1)
+        y = native.conv2d_nhwc(y, p['s2'][0], p['s2'][1], relu=True, pad=1)
+        return native.maxpool3x3s2_nhwc(y)
+
+    def forward(self, x, out=None):
+        """x [B,3,H,W] f32 -> a tuple of ONE logical-NCHW map (res2net_v1b.py:247-262).  out: a contiguous NHWC tensor of
+        out_shape_nhwc(...) in the compute dtype that receives it, e.g. a slice of a larger batch."""
+        if not x.is_cuda:
+            raise NotImplementedError('Res2Net runs on the GPU only (no CPU fallback)')
+        y = self._stem(x, self.packed(x.device))
+        for i, name in enumerate(self.res_layers):
+            blocks = list(getattr(self, name))
+            for j, blk in enumerate(blocks):
+                y = blk.forward_nhwc(y, out if i + 1 == len(self.res_layers) and j + 1 == len(blocks) else None)
+        return (as_logical(y),)
+
+    def forward_train_nhwc(self, x):
+        raise NotImplementedError('Res2Net is inference only: the slice conv and the pitched pool have no backward')
+
+    def train(self, mode=True):
+        super(Res2Net, self).train(False)
+        return self
+
+
+@SHARED_HEADS.register_module
+class Res2Layer(nn.Module, PackedMixin):
+    """res2_layer.py:13-81: layer{stage+1} of Res2Net-101 on Bottle2necks (26w x 4s) + the hard-wired 1x1 2048 -> 256 `new_layer_1`.
+    The C5 form is stride=1, dilation=2: the first block at dilation 1 with a 3x3/1 pool, the other two at dilation 2."""
+
+    def __init__(self, depth, stage=3, stride=2, dilation=1, style='pytorch', norm_cfg=dict(type='BN', requires_grad=True), norm_eval=True,
+                 with_cp=False, external_conv=False, dcn=None):
+        super(Res2Layer, self).__init__()
+        _res2_refuse(None, norm_cfg, dcn)
+        self.norm_eval, self.norm_cfg, self.stage, self.external_conv = norm_eval, norm_cfg, stage, external_conv
+        self.fp16_enabled = False
+        block, stage_blocks = Res2Net.arch_settings[depth]   # (KeyError for any depth but 101, as in the reference)
+        planes = 64 * 2 ** stage
+        inplanes = 64 * 2 ** (stage - 1) * block.expansion
+        self.add_module('layer{}'.format(stage + 1), make_res2_layer(block, inplanes, planes, stage_blocks[stage], baseWidth=26, scale=4, stride=stride,
+                                                                      dilation=dilation, eps=norm_cfg.get('eps', 1e-5)))
+        if external_conv:
+            self.new_layer_1 = nn.Module()   # ConvModule(2048, 256, 1): conv + bias + ReLU, parameters under new_layer_1.conv.*
+            self.new_layer_1.conv = nn.Conv2d(2048, 256, 1)
+        _freeze(self)
+        self._init_packed()
+
+    init_weights = ResLayer.init_weights
+    _pack = ResLayer._pack
+    forward = ResLayer.forward
+
+    def forward_train_nhwc(self, y):
+        raise NotImplementedError('Res2Layer is inference only: the slice conv and the pitched pool have no backward')
+
+    def train(self, mode=True):
+        super(Res2Layer, self).train(False)
+        return self

@@ -91,6 +91,10 @@ hipError_t run_seq_nms(const float*, const float*, int, const int*, int, int, in
 size_t seq_nms_workspace_bytes(int P, int F, int R, int ncls, int tubes);
 hipError_t run_stem_fused(const float*, const void*, const float*, void*, int, int, int, int, hipStream_t);
 hipError_t run_gconv3x3(const void*, const void*, void*, const float*, int, int, int, int, int, int, int, int, int, hipStream_t);
+hipError_t run_res2_conv3x3(const void*, long, const void*, long, void*, long, const void*, const float*, int, int, int, int, int, int, int, int,
+                            hipStream_t);
+hipError_t run_avgpool(const void*, long, void*, long, int, int, int, int, int, int, int, int, int, int, int, hipStream_t);
+hipError_t run_stem3x3s2_first(const float*, const float*, const float*, void*, int, int, int, int, int, hipStream_t);
 }  // namespace hvr
 
 using namespace hvr;
@@ -619,6 +623,108 @@ int hvr_conv3x3_grouped(const hvr_gconv_desc* d, void* stream) {
   if (rc) return rc;
   return check_launch(run_gconv3x3(d->x, d->w, d->y, d->bias, d->B, d->H, d->W, d->C, d->C / d->groups, d->stride, d->dil, d->relu, d->dtype,
                                    (hipStream_t)stream), "hvr_conv3x3_grouped");
+}
+
+// byte range [lo, hi) of a pitched slice: npix pixels at pitch ld elements, C channels from element off on
+static inline void slice_range(const void* base, long ld, long off, long npix, int C, int es, uintptr_t& lo, uintptr_t& hi) {
+  lo = reinterpret_cast<uintptr_t>(base) + (uintptr_t)off * es;
+  hi = lo + (uintptr_t)((npix - 1) * ld + C) * es;
+}
+// 1 when a slice written at (y, ldy, y_off) may share an element with one read at (x, ldx, x_off): the address ranges overlap and the
+// two are not channel-disjoint slices of maps at one pitch
+static int slices_alias(const void* y, long ldy, long y_off, long ny, const void* x, long ldx, long x_off, long nx, int C, int es) {
+  uintptr_t ylo, yhi, xlo, xhi;
+  slice_range(y, ldy, y_off, ny, C, es, ylo, yhi);
+  slice_range(x, ldx, x_off, nx, C, es, xlo, xhi);
+  if (yhi <= xlo || xhi <= ylo) return 0;
+  if (ldx != ldy) return 1;
+  const uintptr_t pitch = (uintptr_t)ldy * es;
+  const uintptr_t d = ylo >= xlo ? (ylo - xlo) % pitch : (pitch - (xlo - ylo) % pitch) % pitch;   // y's first channel inside x's pixel
+  return !(d >= (uintptr_t)C * es && d + (uintptr_t)C * es <= pitch);
+}
+
+// the instance set of res2.hip's slice conv (include/hvr_hip.h states it); 0 or the error
+static int res2_check(const hvr_res2_conv_desc* d) {
+  if (!d) return fail(HVR_EINVAL, "null descriptor");
+  if (!valid_dtype(d->dtype)) return fail(HVR_EINVAL, "bad dtype %d", d->dtype);
+  if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(HVR_EINVAL, "empty slice conv input %dx%dx%d", d->B, d->H, d->W);
+  if (d->Wp != 32 && d->Wp != 64 && d->Wp != 128 && d->Wp != 224) return fail(HVR_EINVAL, "slice conv: Wp=%d is none of 32 / 64 / 128 / 224", d->Wp);
+  if (d->stride != 1 && d->stride != 2) return fail(HVR_EINVAL, "slice conv: stride %d is neither 1 nor 2", d->stride);
+  if (d->pad != d->dil || (d->dil != 1 && d->dil != 2)) return fail(HVR_EINVAL, "slice conv: pad=%d dil=%d (pad == dil in {1, 2})", d->pad, d->dil);
+  if (!d->x || !d->w || !d->y || !d->bias) return fail(HVR_EINVAL, "slice conv: null operand pointer (the bias is required)");
+  if (!aligned16(d->x) || !aligned16(d->w) || !aligned16(d->y) || !aligned16(d->bias) || (d->add && !aligned16(d->add)))
+    return fail(HVR_EINVAL, "slice conv: operands must be 16-byte aligned");
+  if (d->ldx <= 0 || d->ldx % 32 || d->x_off < 0 || d->x_off % 32 || d->x_off + d->Wp > d->ldx)
+    return fail(HVR_EINVAL, "slice conv: x pitch %ld / offset %ld (multiples of 32, offset + Wp <= pitch)", (long)d->ldx, (long)d->x_off);
+  if (d->ldy <= 0 || d->ldy % 32 || d->y_off < 0 || d->y_off % 32 || d->y_off + d->Wp > d->ldy)
+    return fail(HVR_EINVAL, "slice conv: y pitch %ld / offset %ld (multiples of 32, offset + Wp <= pitch)", (long)d->ldy, (long)d->y_off);
+  if (d->add && (d->lda <= 0 || d->lda % 32 || d->add_off < 0 || d->add_off % 32 || d->add_off + d->Wp > d->lda))
+    return fail(HVR_EINVAL, "slice conv: add pitch %ld / offset %ld (multiples of 32, offset + Wp <= pitch)", (long)d->lda, (long)d->add_off);
+  const long nx = (long)d->B * d->H * d->W, ny = (long)d->B * ((d->H - 1) / d->stride + 1) * ((d->W - 1) / d->stride + 1);
+  if (ny > 0x7fffffffL) return fail(HVR_EINVAL, "slice conv: too many output pixels");
+  if (slices_alias(d->y, d->ldy, d->y_off, ny, d->x, d->ldx, d->x_off, nx, d->Wp, 2))
+    return fail(HVR_EINVAL, "slice conv: y aliases x (the output slice shares elements with the input slice)");
+  if (d->add && slices_alias(d->y, d->ldy, d->y_off, ny, d->add, d->lda, d->add_off, nx, d->Wp, 2))
+    return fail(HVR_EINVAL, "slice conv: y aliases add (the output slice shares elements with the added slice)");
+  if (d->dtype != HVR_BF16 && d->dtype != HVR_F16)
+    return fail(HVR_EUNSUPPORTED, "slice conv: bf16 and half operands only (f32 / split half: hvr_conv2d_nhwc on a contiguous copy of the slice)");
+  return HVR_OK;
+}
+
+int hvr_res2_conv3x3_supported(const hvr_res2_conv_desc* d) { return res2_check(d) == HVR_OK ? 1 : 0; }
+
+int hvr_res2_conv3x3(const hvr_res2_conv_desc* d, void* stream) {
+  const int rc = res2_check(d);
+  if (rc) return rc;
+  const char* x = static_cast<const char*>(d->x) + d->x_off * 2;
+  const char* a = d->add ? static_cast<const char*>(d->add) + d->add_off * 2 : nullptr;
+  char* y = static_cast<char*>(d->y) + d->y_off * 2;
+  return check_launch(run_res2_conv3x3(x, d->ldx, a, d->lda, y, d->ldy, d->w, d->bias, d->B, d->H, d->W, d->Wp, d->stride, d->dil, d->relu, d->dtype,
+                                       (hipStream_t)stream), "hvr_res2_conv3x3");
+}
+
+int hvr_avgpool_nhwc(const hvr_pool_desc* d, void* stream) {
+  if (!d) return fail(HVR_EINVAL, "null descriptor");
+  if (!valid_dtype(d->dtype)) return fail(HVR_EINVAL, "bad dtype %d", d->dtype);
+  if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->C <= 0) return fail(HVR_EINVAL, "empty pool input %dx%dx%dx%d", d->B, d->H, d->W, d->C);
+  if (d->k < 1 || d->k > 3) return fail(HVR_EINVAL, "avgpool: k=%d is none of 1 / 2 / 3", d->k);
+  if (d->stride != 1 && d->stride != 2) return fail(HVR_EINVAL, "avgpool: stride %d is neither 1 nor 2", d->stride);
+  if (d->pad < 0 || d->pad > d->k / 2) return fail(HVR_EINVAL, "avgpool: pad=%d (at most k / 2 = %d)", d->pad, d->k / 2);
+  if (d->H + 2 * d->pad < d->k || d->W + 2 * d->pad < d->k) return fail(HVR_EINVAL, "avgpool: the %dx%d map is smaller than the window", d->H, d->W);
+  if (d->C % 4 || d->ldx <= 0 || d->ldx % 4 || d->x_off < 0 || d->x_off % 4 || d->x_off + d->C > d->ldx || d->ldy <= 0 || d->ldy % 4 || d->y_off < 0 ||
+      d->y_off % 4 || d->y_off + d->C > d->ldy)
+    return fail(HVR_EINVAL, "avgpool: C=%d, pitches %ld / %ld, offsets %ld / %ld (multiples of 4, offset + C <= pitch)", d->C, (long)d->ldx, (long)d->ldy,
+                (long)d->x_off, (long)d->y_off);
+  if (!d->x || !d->y || !aligned16(d->x) || !aligned16(d->y)) return fail(HVR_EINVAL, "avgpool: x and y must be 16-byte aligned device pointers");
+  if (d->dtype == HVR_F16S) return fail(HVR_EUNSUPPORTED, "avgpool: no split-half instance (pool the f32 form)");
+  int O[2];
+  const int I[2] = {d->H, d->W};
+  for (int i = 0; i < 2; ++i) {
+    const int span = I[i] + 2 * d->pad - d->k;
+    O[i] = (d->ceil_mode ? (span + d->stride - 1) / d->stride : span / d->stride) + 1;
+    if (d->ceil_mode && (O[i] - 1) * d->stride >= I[i] + d->pad) --O[i];   // the last window starts inside the map or its left padding
+  }
+  const int es = elem_size(d->dtype);
+  const long nx = (long)d->B * d->H * d->W, ny = (long)d->B * O[0] * O[1];
+  if (ny * (d->C / 4) > 0x7fffffffL * 256) return fail(HVR_EINVAL, "avgpool: too many output elements");
+  uintptr_t xlo, xhi, ylo, yhi;
+  slice_range(d->x, d->ldx, d->x_off, nx, d->C, es, xlo, xhi);
+  slice_range(d->y, d->ldy, d->y_off, ny, d->C, es, ylo, yhi);
+  if (!(yhi <= xlo || xhi <= ylo)) return fail(HVR_EINVAL, "avgpool: y aliases x");
+  return check_launch(run_avgpool(static_cast<const char*>(d->x) + d->x_off * es, d->ldx, static_cast<char*>(d->y) + d->y_off * es, d->ldy, d->B, d->H,
+                                  d->W, O[0], O[1], d->C, d->k, d->stride, d->pad, d->count_include_pad ? 1 : 0, d->dtype, (hipStream_t)stream),
+                      "hvr_avgpool_nhwc");
+}
+
+int hvr_stem3x3s2_first(const float* img, const float* w, const float* bias, void* y, int B, int H, int W, int ldy, int dtype, void* stream) {
+  if (!img || !w || !bias || !y || !aligned16(img) || !aligned16(w) || !aligned16(bias) || !aligned16(y))
+    return fail(HVR_EINVAL, "stem3x3s2_first: operands must be 16-byte aligned device pointers");
+  if (B <= 0 || H <= 0 || W <= 0) return fail(HVR_EINVAL, "empty image %dx%dx%d", B, H, W);
+  if (ldy < 32 || ldy % 4) return fail(HVR_EINVAL, "stem3x3s2_first: ldy=%d (a multiple of 4, at least 32)", ldy);
+  if (dtype != HVR_F32 && dtype != HVR_BF16 && dtype != HVR_F16)
+    return fail(HVR_EUNSUPPORTED, "stem3x3s2_first: f32, bf16 or half output (split half: cast the f32 output)");
+  if ((long)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) > 0x7fffffffL) return fail(HVR_EINVAL, "stem3x3s2_first: too many output pixels");
+  return check_launch(run_stem3x3s2_first(img, w, bias, y, B, H, W, ldy, dtype, (hipStream_t)stream), "hvr_stem3x3s2_first");
 }
 
 int hvr_conv2d_path(const hvr_conv_desc* d) {

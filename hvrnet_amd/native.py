@@ -71,6 +71,22 @@ class GConvDesc(ctypes.Structure):          # hvr_gconv_desc
                 ('relu', ctypes.c_int32), ('dtype', ctypes.c_int32)]
 
 
+class Res2ConvDesc(ctypes.Structure):       # hvr_res2_conv_desc
+    _fields_ = [('x', ctypes.c_void_p), ('add', ctypes.c_void_p), ('y', ctypes.c_void_p), ('w', ctypes.c_void_p), ('bias', ctypes.c_void_p),
+                ('ldx', ctypes.c_int64), ('lda', ctypes.c_int64), ('ldy', ctypes.c_int64),
+                ('x_off', ctypes.c_int64), ('add_off', ctypes.c_int64), ('y_off', ctypes.c_int64),
+                ('B', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('Wp', ctypes.c_int32),
+                ('stride', ctypes.c_int32), ('pad', ctypes.c_int32), ('dil', ctypes.c_int32), ('relu', ctypes.c_int32), ('dtype', ctypes.c_int32)]
+
+
+class PoolDesc(ctypes.Structure):           # hvr_pool_desc
+    _fields_ = [('x', ctypes.c_void_p), ('y', ctypes.c_void_p),
+                ('ldx', ctypes.c_int64), ('ldy', ctypes.c_int64), ('x_off', ctypes.c_int64), ('y_off', ctypes.c_int64),
+                ('B', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('C', ctypes.c_int32), ('k', ctypes.c_int32),
+                ('stride', ctypes.c_int32), ('pad', ctypes.c_int32), ('ceil_mode', ctypes.c_int32), ('count_include_pad', ctypes.c_int32),
+                ('dtype', ctypes.c_int32)]
+
+
 class TailDesc(ctypes.Structure):
     _fields_ = [('h', ctypes.c_void_p), ('x', ctypes.c_void_p), ('w', ctypes.c_void_p), ('y', ctypes.c_void_p),
                 ('B', ctypes.c_int32), ('OH', ctypes.c_int32), ('OW', ctypes.c_int32), ('C1', ctypes.c_int32),
@@ -123,6 +139,10 @@ SYMBOLS = {
     'hvr_conv2d_splitk_workspace_bytes': (_sz, [ctypes.POINTER(ConvDesc)]),
     'hvr_conv3x3_grouped': (_i, [ctypes.POINTER(GConvDesc), _vp]),
     'hvr_conv3x3_grouped_supported': (_i, [ctypes.POINTER(GConvDesc)]),
+    'hvr_res2_conv3x3': (_i, [ctypes.POINTER(Res2ConvDesc), _vp]),
+    'hvr_res2_conv3x3_supported': (_i, [ctypes.POINTER(Res2ConvDesc)]),
+    'hvr_avgpool_nhwc': (_i, [ctypes.POINTER(PoolDesc), _vp]),
+    'hvr_stem3x3s2_first': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'hvr_bottleneck_tail': (_i, [ctypes.POINTER(TailDesc), _vp]),
     'hvr_bottleneck_tail_supported': (_i, [ctypes.POINTER(TailDesc)]),
     'hvr_bottleneck_tail_next': (_i, [ctypes.POINTER(TailNextDesc), _vp]),
@@ -764,6 +784,168 @@ def conv3x3_grouped(x, w, bias, relu, stride, dil, out=None, route=None):
     with _span(tag, float((B * H * W * C + B * OH * OW * C + 9 * C * gw.Cg) * x.element_size())):
         _check(lib().hvr_conv3x3_grouped(ctypes.byref(d), _stream()), 'hvr_conv3x3_grouped')
     return y
+
+
+# ---- Res2Net: the 3x3 conv over a channel slice with a pre-add, the pitched average pool, the first stem conv (csrc/res2.hip)
+RES2_WIDTHS = (32, 64, 128, 224)   # the padded slice widths hvr_res2_conv3x3 has instances for
+
+
+def res2_pad_width(width):
+    """Wp: a Bottle2neck's slice width rounded up to a multiple of 32 (26 / 52 / 104 / 208 -> 32 / 64 / 128 / 224)."""
+    return (int(width) + 31) // 32 * 32
+
+
+def res2_conv3x3_supported(B, H, W, Wp, stride=1, dil=1, dtype=torch.bfloat16, pad=None, ldx=None, x_off=0, ldy=None, y_off=0, add=False, lda=None,
+                           add_off=0):
+    """True where hvr_res2_conv3x3 has an instance for a slice conv of this shape (res2.hip: bf16 / half, Wp in RES2_WIDTHS, stride 1 / 2,
+    pad == dil in {1, 2}, pitches and offsets multiples of 32).  Nothing is launched: placeholder addresses, 1 GiB apart."""
+    ldx, ldy, lda = (4 * Wp if v is None else v for v in (ldx, ldy, lda))
+    d = Res2ConvDesc(x=_PH, add=(_PH + (2 << 30)) if add else None, y=_PH + (1 << 30), w=_PH, bias=_PH, ldx=ldx, lda=lda, ldy=ldy, x_off=x_off,
+                     add_off=add_off, y_off=y_off, B=B, H=H, W=W, Wp=Wp, stride=stride, pad=dil if pad is None else pad, dil=dil, relu=1,
+                     dtype=DTYPE_CODES.get(dtype, -1))
+    return bool(lib().hvr_res2_conv3x3_supported(ctypes.byref(d)))
+
+
+class Res2Weight(object):
+    """The weight of one branch conv of a Bottle2neck, w [Wp,3,3,Wp] (f32; rows and columns from the real width on are exact zeros), in
+    the operand format `dtype`: the form the slice kernel reads, and the form conv2d_nhwc takes on the composite route, whose input
+    channels are zero-padded to the Cin multiple of the mode.  Each is built on first use (pack time) and kept."""
+
+    def __init__(self, w, dtype):
+        assert w.dim() == 4 and tuple(w.shape[1:3]) == (3, 3) and w.shape[0] == w.shape[3] and w.shape[0] % 32 == 0, tuple(w.shape)
+        self.w32, self.dtype, self.Wp = w.detach().float().contiguous(), dtype, int(w.shape[0])
+        self.cin = (self.Wp + kstep(dtype) - 1) // kstep(dtype) * kstep(dtype) if dtype != SPLIT else self.Wp
+        self._kernel = self._dense = None
+
+    def kernel(self):
+        if self._kernel is None:
+            if self.dtype not in (torch.bfloat16, torch.float16):
+                raise HvrError('hvr_res2_conv3x3 has bf16 and half instances only: the composite route carries %s' % DTYPE_NAMES.get(self.dtype))
+            self._kernel = self.w32.to(self.dtype)
+        return self._kernel
+
+    def dense(self):
+        if self._dense is None:
+            self._dense = as_operand(torch.nn.functional.pad(self.w32, (0, self.cin - self.Wp)), self.dtype)
+        return self._dense
+
+
+def _slice_args(t, off, Wp, what):
+    assert t.dim() == 4 and t.is_contiguous(), '%s: a contiguous physical NHWC map' % what
+    if off < 0 or off + Wp > t.shape[3]:
+        raise HvrError('hvr_res2_conv3x3: %s slice [%d, %d) lies outside the map\'s %d channels' % (what, off, off + Wp, t.shape[3]))
+    return int(t.shape[3]), int(off)
+
+
+def res2_conv3x3(x, x_off, w, bias, add=None, add_off=0, out=None, out_off=0, stride=1, dil=1, relu=True, route=None):
+    """One branch conv of a Bottle2neck (the rule: include/hvr_hip.h, hvr_res2_conv3x3): the 3x3 conv, pad = dil, of the Wp channels of
+    x [B,H,W,Cx] from x_off on -- with `add`, of round(f32(that slice) + f32(add's Wp channels from add_off on)) -- plus bias, ReLU, written
+    to the Wp channels of out [B,OH,OW,Cy] from out_off on (out=None: a fresh [B,OH,OW,Wp] map).  w: a Res2Weight, or a [Wp,3,3,Wp]
+    tensor (packed on every call: tests and tools).  Returns out.
+    route: None = the slice kernel where it has an instance for this shape and format, else 'composite'; 'kernel' / 'composite' force one
+    (the forced kernel raises HvrError where it has no instance).  The composite route is made of calls older than the kernel: the
+    slice copied out (channels zero-padded to the mode's Cin multiple), the add in f32 and its rounding in torch, conv2d_nhwc, the copy
+    into the output slice; it carries f32 and split half.  Neither route touches the host."""
+    assert route in (None, 'kernel', 'composite'), route
+    _need_cuda(x, bias, add, out)
+    rw = w if isinstance(w, Res2Weight) else Res2Weight(w, x.dtype)
+    _need_cuda(rw.w32)
+    assert rw.dtype == x.dtype, (rw.dtype, x.dtype)
+    Wp = rw.Wp
+    B, H, W, _ = x.shape
+    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if out is None:
+        out, out_off = torch.empty((B, OH, OW, Wp), dtype=x.dtype, device=x.device), 0
+    assert tuple(out.shape[:3]) == (B, OH, OW) and out.dtype == x.dtype, (tuple(out.shape), (B, OH, OW))
+    assert add is None or (tuple(add.shape[:3]) == (B, H, W) and add.dtype == x.dtype), 'add has x\'s spatial size and format'
+    assert bias.dtype == torch.float32 and bias.numel() == Wp
+    ldx, x_off = _slice_args(x, x_off, Wp, 'x')
+    ldy, out_off = _slice_args(out, out_off, Wp, 'out')
+    lda, add_off = _slice_args(add, add_off, Wp, 'add') if add is not None else (0, 0)
+    d = Res2ConvDesc(ldx=ldx, lda=lda, ldy=ldy, x_off=x_off, add_off=add_off, y_off=out_off, B=B, H=H, W=W, Wp=Wp, stride=stride, pad=dil, dil=dil,
+                     relu=int(relu), dtype=_dt(x))
+    _point(d, x=x, add=add, y=out, bias=bias)
+    if route is None:
+        d.w = _PH
+        route = 'kernel' if Wp in RES2_KERNEL_WIDTHS.get(x.dtype, ()) and lib().hvr_res2_conv3x3_supported(ctypes.byref(d)) else 'composite'
+    if route == 'kernel':
+        # (the library checks the descriptor before it launches anything: a forced route outside the instance set raises here; f32 and
+        # split half have no kernel form of the weight, the library refuses the format before it looks at the address)
+        d.w = rw.kernel().data_ptr() if x.dtype in (torch.bfloat16, torch.float16) else _PH
+        tag = 'res2conv' if not (_prof and _prof['detail']) else 'res2conv %dx%d %d s%d d%d%s' % (H, W, Wp, stride, dil, '+add' if add is not None else '')
+        # bytes it moves: the slice (and the added one) in, the slice out, the weights once
+        with _span(tag, float((B * H * W * Wp * (2 if add is not None else 1) + B * OH * OW * Wp + 9 * Wp * Wp) * x.element_size())):
+            _check(lib().hvr_res2_conv3x3(ctypes.byref(d), _stream()), 'hvr_res2_conv3x3')
+        return out
+    xs = x[..., x_off:x_off + Wp]
+    if add is not None:
+        a = add[..., add_off:add_off + Wp]
+        if x.dtype == SPLIT:
+            s = cast(cast(xs.contiguous(), torch.float32) + cast(a.contiguous(), torch.float32), SPLIT)
+        else:
+            s = (xs.float() + a.float()).to(x.dtype)
+    else:
+        s = xs
+    if rw.cin != Wp:
+        s = torch.nn.functional.pad(s, (0, rw.cin - Wp))
+    y = conv2d_nhwc(s.contiguous(), rw.dense(), bias, relu=relu, stride=stride, pad=dil, dil=dil)
+    out[..., out_off:out_off + Wp].copy_(y)
+    return out
+
+
+# The widths at which the automatic route takes the slice kernel, per format (tools/res2_bench.py: the kernel against the composite
+# route at the stage shapes of a window; DESIGN.md section 8i).  Every other width, f32 and split half run the composite route.
+RES2_KERNEL_WIDTHS = {torch.bfloat16: (32, 64, 128), torch.float16: (32, 64, 128)}
+
+
+def avgpool_out_hw(H, W, k, stride, pad=0, ceil_mode=False):
+    """torch.nn.AvgPool2d's output size."""
+    out = []
+    for n in (H, W):
+        span = n + 2 * pad - k
+        o = (-(-span // stride) if ceil_mode else span // stride) + 1
+        if ceil_mode and (o - 1) * stride >= n + pad:
+            o -= 1
+        out.append(o)
+    return tuple(out)
+
+
+def avgpool_nhwc(x, k, stride=1, pad=0, ceil_mode=False, count_include_pad=True, x_off=0, C=None, out=None, out_off=0):
+    """k x k average pool (torch.nn.AvgPool2d's sizes and divisors; the rule: include/hvr_hip.h, hvr_avgpool_nhwc) of the C channels of
+    x [B,H,W,Cx] from x_off on (C=None: all behind x_off) into the C channels of out [B,OH,OW,Cy] from out_off on (out=None: a fresh
+    [B,OH,OW,C] map).  k = 1, stride 1 copies the slice.  Split half is pooled in f32 (cast out and back, as maxpool3x3s2_nhwc)."""
+    _need_cuda(x, out)
+    assert x.dim() == 4 and x.is_contiguous()
+    B, H, W, Cx = x.shape
+    C = Cx - x_off if C is None else C
+    OH, OW = avgpool_out_hw(H, W, k, stride, pad, ceil_mode)
+    if out is None:
+        out, out_off = torch.empty((B, OH, OW, C), dtype=x.dtype, device=x.device), 0
+    assert out.dim() == 4 and out.is_contiguous() and tuple(out.shape[:3]) == (B, OH, OW) and out.dtype == x.dtype, (tuple(out.shape), (B, OH, OW))
+    if x.dtype == SPLIT:
+        y = avgpool_nhwc(cast(x[..., x_off:x_off + C].contiguous(), torch.float32), k, stride, pad, ceil_mode, count_include_pad)
+        out[..., out_off:out_off + C].copy_(cast(y, SPLIT))
+        return out
+    d = PoolDesc(x=x.data_ptr(), y=out.data_ptr(), ldx=Cx, ldy=out.shape[3], x_off=x_off, y_off=out_off, B=B, H=H, W=W, C=C, k=k, stride=stride,
+                 pad=pad, ceil_mode=int(ceil_mode), count_include_pad=int(count_include_pad), dtype=_dt(x))
+    with _span('avgpool', float((B * H * W * C + B * OH * OW * C) * x.element_size())):
+        _check(lib().hvr_avgpool_nhwc(ctypes.byref(d), _stream()), 'hvr_avgpool_nhwc')
+    return out
+
+
+def stem3x3s2_first(img, w, bias, dtype, channels=32):
+    """The first conv of Res2Net's deep stem (3 -> 32, 3x3 / 2, pad 1, folded BN bias, ReLU) of img [B,3,H,W] f32 NCHW -> physical NHWC
+    [B,OH,OW,channels] in the compute format `dtype`; channels 32 onwards are exact zeros (the K padding of the conv that follows).
+    w f32 [32,3,3,3] as [n,ky,kx,c], bias f32 [32].  Split half: f32 out, then cast."""
+    _need_cuda(img, w, bias)
+    assert img.dtype == torch.float32 and img.is_contiguous() and img.shape[1] == 3
+    assert w.dtype == torch.float32 and tuple(w.shape) == (32, 3, 3, 3) and w.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == 32
+    B, _, H, W = img.shape
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.empty((B, OH, OW, channels), dtype=torch.float32 if dtype == SPLIT else dtype, device=img.device)
+    with _span('stem', 2.0 * B * OH * OW * 32 * 27):
+        _check(lib().hvr_stem3x3s2_first(_ptr(img), _ptr(w), _ptr(bias), _ptr(y), B, H, W, channels, _dt(y), _stream()), 'hvr_stem3x3s2_first')
+    return cast(y, SPLIT) if dtype == SPLIT else y
 
 
 def im2col_stem(img, dtype, kp=192):

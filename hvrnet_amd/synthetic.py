@@ -66,24 +66,59 @@ def _res_layer(g, sd, prefix, inplanes, planes, blocks, groups=1, base_width=4):
             _bn(g, sd, p + '.downsample.1', planes * 4)
 
 
+def _res2_layer(g, sd, prefix, inplanes, planes, blocks, base_width=26, scale=4):
+    """Keys of make_res2_layer (res2net_v1b.py:103-122) in the reference's order: conv1, bn1, convs, bns, conv3, bn3, then the
+    pool -> 1x1 -> BN shortcut of the first block under downsample.1 / downsample.2 (the pool is downsample.0)."""
+    width = int(math.floor(planes * (base_width / 64.0)))
+    for i in range(blocks):
+        p = '%s.%d' % (prefix, i)
+        cin = inplanes if i == 0 else planes * 4
+        sd[p + '.conv1.weight'] = _conv(g, width * scale, cin, 1)
+        _bn(g, sd, p + '.bn1', width * scale)
+        for j in range(scale - 1):
+            sd[p + '.convs.%d.weight' % j] = _conv(g, width, width, 3)
+        for j in range(scale - 1):
+            _bn(g, sd, p + '.bns.%d' % j, width)
+        sd[p + '.conv3.weight'] = _conv(g, planes * 4, width * scale, 1)
+        _bn(g, sd, p + '.bn3', planes * 4, gamma_scale=0.25)
+        if i == 0:
+            sd[p + '.downsample.1.weight'] = _conv(g, planes * 4, cin, 1)
+            _bn(g, sd, p + '.downsample.2', planes * 4)
+
+
 def _linear(g, sd, prefix, cout, cin, gain, conv=False):
     w = torch.randn((cout, cin), generator=g) * (0.01 * gain)
     sd[prefix + '.weight'] = w.view(cout, cin, 1, 1) if conv else w
     sd[prefix + '.bias'] = torch.randn(cout, generator=g) * 0.01
 
 
-def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024, roi_feat=256 * 49, groups=1, base_width=4):
-    """Full detector state dict (f32, CPU) with the reference's key names.  groups / base_width: a ResNeXt backbone + ResXLayer."""
+def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024, roi_feat=256 * 49, groups=1, base_width=4, arch='resnet'):
+    """Full detector state dict (f32, CPU) with the reference's key names.  groups / base_width: a ResNeXt backbone + ResXLayer.
+    arch='res2net': a Res2Net backbone (101 layers, 26w x 4s, deep stem) + Res2Layer; the heads' keys are the same."""
+    assert arch in ('resnet', 'res2net'), arch
     g = torch.Generator().manual_seed(seed)
     sd = {}
     blocks = STAGE_BLOCKS[depth]
-    sd['backbone.conv1.weight'] = _conv(g, 64, 3, 7)
-    _bn(g, sd, 'backbone.bn1', 64)
-    inplanes = 64
-    for i in range(3):
-        _res_layer(g, sd, 'backbone.layer%d' % (i + 1), inplanes, 64 * 2 ** i, blocks[i], groups, base_width)
-        inplanes = 64 * 2 ** i * 4
-    _res_layer(g, sd, 'shared_head.layer4', 1024, 512, blocks[3], groups, base_width)
+    if arch == 'res2net':
+        assert depth == 101 and groups == 1, 'Res2Net is the 101-layer 26w x 4s net only'
+        for idx, (co, ci) in ((0, (32, 3)), (3, (32, 32)), (6, (64, 32))):   # res2net_v1b.py:174-182: conv1.0 / .1 / .3 / .4 / .6
+            sd['backbone.conv1.%d.weight' % idx] = _conv(g, co, ci, 3)
+            if idx < 6:
+                _bn(g, sd, 'backbone.conv1.%d' % (idx + 1), co)
+        _bn(g, sd, 'backbone.bn1', 64)
+        inplanes = 64
+        for i in range(3):
+            _res2_layer(g, sd, 'backbone.layer%d' % (i + 1), inplanes, 64 * 2 ** i, blocks[i])
+            inplanes = 64 * 2 ** i * 4
+        _res2_layer(g, sd, 'shared_head.layer4', 1024, 512, blocks[3])
+    else:
+        sd['backbone.conv1.weight'] = _conv(g, 64, 3, 7)
+        _bn(g, sd, 'backbone.bn1', 64)
+        inplanes = 64
+        for i in range(3):
+            _res_layer(g, sd, 'backbone.layer%d' % (i + 1), inplanes, 64 * 2 ** i, blocks[i], groups, base_width)
+            inplanes = 64 * 2 ** i * 4
+        _res_layer(g, sd, 'shared_head.layer4', 1024, 512, blocks[3], groups, base_width)
     sd['shared_head.new_layer_1.conv.weight'] = _conv(g, 256, 2048, 1) * NEW_LAYER_GAIN
     sd['shared_head.new_layer_1.conv.bias'] = torch.randn(256, generator=g) * 0.01
     # RPN (12 anchors)

@@ -190,6 +190,56 @@ typedef struct hvr_gconv_desc {
 int hvr_conv3x3_grouped(const hvr_gconv_desc* d, void* stream);
 int hvr_conv3x3_grouped_supported(const hvr_gconv_desc* d);
 
+/* 3x3 convolution over a channel slice of a wider NHWC map, with an optional pre-add, fused bias + ReLU: one branch of a Res2Net
+ * Bottle2neck with its frozen BatchNorm folded in (mmdet/models/backbones/res2net_v1b.py:75-81; csrc/res2.hip).  A descriptor of its
+ * own: hvr_conv_desc is unchanged.
+ *   x, add and y are pitched maps: pixel (b, iy, ix) of x starts at element ((b H + iy) W + ix) ldx, and the slice is the Wp channels
+ *   from x_off on; add (optional, NULL: none) has x's spatial size, pitch lda and slice offset add_off; y has the output's spatial size
+ *   OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1, pitch ldy and offset y_off.  w [Wp][3][3][Wp], bias f32 [Wp], required:
+ *     y[b][oy][ox][y_off + n] = act( bias[n] + sum_{ky, kx, c} s[b][oy stride + (ky - 1) dil][ox stride + (kx - 1) dil][c] w[n][ky][kx][c] )
+ *     s[..][c] = x[..][x_off + c]                                                       when add == NULL
+ *     s[..][c] = round_dtype( f32(x[..][x_off + c]) + f32(add[..][add_off + c]) )       otherwise (round to nearest even)
+ *   with taps outside the map contributing zero (pad == dil) and act = ReLU when relu != 0.  f32 accumulation, ONE rounding of the
+ *   result to the stored format.  Channels of x, add and y outside the slices are neither read nor written.
+ * Instances: dtype HVR_BF16 or HVR_F16 (x, add, w and y share it); Wp in {32, 64, 128, 224}; stride 1 or 2; pad == dil, 1 or 2;
+ * pitches and offsets multiples of 32 elements with offset + Wp <= pitch; x, add, y, w and bias 16-byte aligned; fewer than 2^31
+ * output pixels; no element of y's slice may be an element of x's or add's slice (slices of ONE map at the same pitch that do not
+ * share a channel are fine; any other overlap of the address ranges is refused).  A shape outside this set returns HVR_EINVAL,
+ * HVR_F32 / HVR_F16S operands HVR_EUNSUPPORTED (both with a message): the caller then composes the same sum from
+ * hvr_conv2d_nhwc on a contiguous copy of the slice.
+ * hvr_res2_conv3x3_supported: 1 when hvr_res2_conv3x3 runs this descriptor, else 0.  A shape query: nothing is launched, pointers
+ * are inspected for alignment and overlap only. */
+typedef struct hvr_res2_conv_desc {
+  const void* x; const void* add; void* y; const void* w;
+  const float* bias;
+  int64_t ldx, lda, ldy, x_off, add_off, y_off;
+  int32_t B, H, W, Wp, stride, pad, dil;
+  int32_t relu, dtype;
+} hvr_res2_conv_desc;
+int hvr_res2_conv3x3(const hvr_res2_conv_desc* d, void* stream);
+int hvr_res2_conv3x3_supported(const hvr_res2_conv_desc* d);
+
+/* Average pool over a channel slice of a pitched NHWC map (addressing as above: x / ldx / x_off -> y / ldy / y_off, C channels):
+ * k x k windows, k in {1, 2, 3}, stride 1 or 2, pad <= k / 2, torch.nn.AvgPool2d's output size (ceil_mode: ceil instead of floor, and
+ * the last window must start inside the map or its left padding) and divisor (count_include_pad: the window clipped to the padded
+ * map, else the number of elements inside the map).  The sum runs in f32 in raster tap order, is multiplied by the f32 reciprocal
+ * of the divisor and rounded once; a 1 x 1 window copies the slice bit for bit.  dtype HVR_F32, HVR_BF16 or HVR_F16 (HVR_F16S:
+ * HVR_EUNSUPPORTED; pool the f32 form); C, pitches and offsets multiples of 4 with offset + C <= pitch; x and y 16-byte aligned
+ * and not overlapping.  Serves a Bottle2neck's 'stage' pool (k 3, pad 1, include pad), the shortcut pool of make_res2_layer
+ * (k = stride, ceil, exclude pad) and the carried slice of a 'normal' block (k 1). */
+typedef struct hvr_pool_desc {
+  const void* x; void* y;
+  int64_t ldx, ldy, x_off, y_off;
+  int32_t B, H, W, C, k, stride, pad, ceil_mode, count_include_pad, dtype;
+} hvr_pool_desc;
+int hvr_avgpool_nhwc(const hvr_pool_desc* d, void* stream);
+
+/* First conv of Res2Net's deep stem (res2net_v1b.py:174-177: Conv 3 -> 32, 3x3, stride 2, pad 1 + frozen BN + ReLU) read from the
+ * f32 NCHW image img [B][3][H][W]: w f32 [32][3][3][3] as [n][ky][kx][c] and bias f32 [32] with the BN folded in; y [B][OH][OW][ldy]
+ * NHWC in `dtype` (HVR_F32, HVR_BF16 or HVR_F16), OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1.  f32 FMAs, one rounding.  ldy >= 32,
+ * a multiple of 4: channels 32 .. ldy - 1 of every pixel are written as exact zeros (the K padding of the conv that follows). */
+int hvr_stem3x3s2_first(const float* img, const float* w, const float* bias, void* y, int B, int H, int W, int ldy, int dtype, void* stream);
+
 /* Closing 1x1 conv of a Bottleneck whose identity path is a projection -- the first block of every stage
  * (mmdet/models/backbones/resnet.py:248-264 with `downsample`, built at resnet.py:283-296):
  *     y = relu( h W3^T + x_s Wd^T + bias )
