@@ -154,7 +154,8 @@ def enable_training(module):
 
 class Step(collections.namedtuple('Step', 'kind projection downsample stride compact h1_in', defaults=(False, False, None, False, False))):
     """How one Bottleneck of a stage closes (ResNet.stage_route).  kind: the native entry -- 'tail', 'tail_next' (`projection`: the shortcut
-    as a second K segment, else the identity form), 'tail_next_live', 'close_sampled' (at `stride` 2 from the full-resolution input) or 'conv'.
+    as a second K segment, else the identity form), 'tail_next_live', 'close_sampled' (at `stride` 2 from the full-resolution input), 'conv' or
+    'gcb' (a block with a context block: the closing 1x1 without residual or ReLU, then native.context_block with both).
     downsample: the projection shortcut is a conv of its own in front.  compact ('close_sampled' at stride 1, 'conv'): the dense close on the
     compact map that a tail_next_live block left.  h1_in: the block's conv1 output arrived from the block before."""
 
@@ -180,10 +181,12 @@ def _w2d(wb):
 class Bottleneck(nn.Module, PackedMixin):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, style='pytorch', norm_cfg=None, dcn=None, groups=1, base_width=4):
+    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, style='pytorch', norm_cfg=None, dcn=None, groups=1, base_width=4,
+                 gcb=None):
         super(Bottleneck, self).__init__()
         assert style in ['pytorch', 'caffe']
         assert dcn is None or isinstance(dcn, dict)
+        assert gcb is None or isinstance(gcb, dict)
         self.inplanes, self.planes, self.stride, self.dilation, self.style = inplanes, planes, stride, dilation, style
         # resnext.py:21-24: the channels of conv1's output, conv2 and conv3's input (a ResNet block: planes)
         self.groups, self.base_width = groups, base_width
@@ -210,6 +213,11 @@ class Bottleneck(nn.Module, PackedMixin):
         self.conv3 = nn.Conv2d(width, planes * 4, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4, eps=eps)
         self.downsample = downsample
+        # resnet.py:199-201,249-250: the global context block acts on bn3's output, in front of the residual add
+        self.gcb, self.with_gcb = gcb, gcb is not None
+        if self.with_gcb:
+            from .ops import ContextBlock   # (ops imports this module)
+            self.context_block = ContextBlock(inplanes=planes * self.expansion, **gcb)
         self._init_packed()
 
     def _pack(self, dtype):
@@ -244,6 +252,8 @@ class Bottleneck(nn.Module, PackedMixin):
         stride = 1 if compact_in else self.stride
         OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
         P, C, proj = self.width, 4 * self.planes, self.downsample is not None
+        if self.with_gcb:   # the context block sits between conv3 and the residual add: no fused close, whatever fuse_next / fuse_tail say
+            return Step('gcb', downsample=proj)
         # split half has no second-K-segment tail: the projection is its own conv and enters the fused closing 1x1 + next conv1 as the
         # residual (the identity form of hvr_bottleneck_tail_next)
         own_ds = proj and dtype == native.SPLIT
@@ -270,9 +280,14 @@ class Bottleneck(nn.Module, PackedMixin):
         return native.conv2d_nhwc(h, p['c2'][0], p['c2'][1], relu=True, stride=s2, pad=self.dilation, dil=self.dilation, out=out)
 
     def close(self, x, h, step, out=None, compact_in=False):
-        """The plain close ('tail' or 'conv') -> y.  out: where y goes (a contiguous [B,OH,OW,4*planes] tensor), e.g. a frame group's slice."""
+        """The plain close ('tail', 'conv' or 'gcb') -> y.  out: where y goes (a contiguous [B,OH,OW,4*planes] tensor), e.g. a frame group's slice."""
         p = self.packed(x.device)
         stride = 1 if compact_in else self.stride
+        if step.kind == 'gcb':
+            # u = bn3(conv3(h)) as a map of its own (the pool reads every pixel of it), then relu(context_block(u) + identity) in the apply
+            identity = native.conv2d_nhwc(x, p['ds'][0], p['ds'][1], relu=False, stride=stride) if step.downsample else x
+            u = native.conv2d_nhwc(h, p['c3'][0], p['c3'][1], relu=False)
+            return self.context_block.forward_nhwc(u, resid=identity, relu=True, out=out)
         if step.kind == 'tail':
             # relu(conv3(h) + downsample(x)) in one pass: the identity map is never written (resnet.py:248-264)
             return native.bottleneck_tail(h, x, p['tail'][0], p['tail'][1], stride2=stride, relu=True, out=out)
@@ -333,6 +348,8 @@ class Bottleneck(nn.Module, PackedMixin):
             raise NotImplementedError('deformable convs are inference only: no backward (col2im + coordinate gradients) is implemented')
         if self.groups > 1:
             raise NotImplementedError('grouped Bottlenecks are inference only: the grouped 3x3 conv has no backward')
+        if self.with_gcb:
+            raise NotImplementedError('Bottlenecks with a context block are inference only: the pool has no backward')
         from . import train_ops as TO
         out = TO.conv_bn(x, self.conv1, self.bn1, relu=True)
         out = TO.conv_bn(out, self.conv2, self.bn2, relu=True)
@@ -340,7 +357,8 @@ class Bottleneck(nn.Module, PackedMixin):
         return TO.conv_bn(out, self.conv3, self.bn3, resid=identity, relu=True)
 
 
-def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style='pytorch', norm_cfg=None, dcn=None, groups=1, base_width=4, **_unused):
+def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style='pytorch', norm_cfg=None, dcn=None, groups=1, base_width=4, gcb=None,
+                   **_unused):
     downsample = None
     eps = (norm_cfg or {}).get('eps', 1e-5)
     if stride != 1 or inplanes != planes * block.expansion:
@@ -349,6 +367,8 @@ def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style=
     extra = {} if dcn is None else dict(dcn=dcn)
     if groups != 1:   # resnext.py:94-154
         extra.update(groups=groups, base_width=base_width)
+    if gcb is not None:
+        extra.update(gcb=gcb)
     layers = [block(inplanes, planes, stride, dilation, downsample, style=style, norm_cfg=norm_cfg, **extra)]
     inplanes = planes * block.expansion
     for _ in range(1, blocks):
@@ -365,7 +385,8 @@ def _freeze(module):
 @BACKBONES.register_module
 class ResNet(nn.Module, PackedMixin):
     """Same kwargs as the reference ResNet (resnet.py:372-395); dcn / stage_with_dcn as there (deformable conv2 in the marked
-    stages, inference only); gcb / gen_attention / conv_cfg must be None."""
+    stages, inference only); gcb / stage_with_gcb as there (a global context block between bn3 and the residual add of every block of the
+    marked stages, inference only); gen_attention / conv_cfg must be None."""
     arch_settings = {d: (Bottleneck, s) for d, s in ARCH_SETTINGS.items()}
     _block_kwargs = {}   # what every block gets beyond the reference ResNet's arguments (ResNeXt: groups, base_width)
 
@@ -377,11 +398,17 @@ class ResNet(nn.Module, PackedMixin):
         super(ResNet, self).__init__()
         if depth not in self.arch_settings:
             raise KeyError('invalid depth {} for resnet'.format(depth))
-        if gcb is not None or gen_attention is not None or conv_cfg is not None:
-            raise NotImplementedError('gcb / gen_attention / conv_cfg are outside the HVR hot path')
+        if gen_attention is not None or conv_cfg is not None:
+            raise NotImplementedError('gen_attention / conv_cfg are outside the HVR hot path')
         if dcn is not None:
             assert len(stage_with_dcn) == num_stages
         self.dcn, self.stage_with_dcn = dcn, stage_with_dcn
+        if gcb is not None:
+            assert len(stage_with_gcb) == num_stages
+            if not any(stage_with_gcb):
+                # (the reference builds the plain net then and drops the dict without a word; an argument that would be disobeyed is refused)
+                raise NotImplementedError('gcb is given but stage_with_gcb marks no stage: no context block would be built; mark a stage or pass gcb=None')
+        self.gcb, self.stage_with_gcb = gcb, stage_with_gcb
         if norm_cfg.get('type', 'BN') != 'BN':
             raise NotImplementedError('only frozen BatchNorm is supported')
         assert 1 <= num_stages <= 4 and len(strides) == len(dilations) == num_stages and max(out_indices) < num_stages
@@ -399,8 +426,9 @@ class ResNet(nn.Module, PackedMixin):
             planes = 64 * 2 ** i
             name = 'layer{}'.format(i + 1)
             stage_dcn = dcn if dcn is not None and stage_with_dcn[i] else None
+            stage_gcb = gcb if gcb is not None and stage_with_gcb[i] else None
             self.add_module(name, make_res_layer(block, inplanes, planes, nb, stride=strides[i], dilation=dilations[i],
-                                                 style=style, norm_cfg=norm_cfg, dcn=stage_dcn, **self._block_kwargs))
+                                                 style=style, norm_cfg=norm_cfg, dcn=stage_dcn, gcb=stage_gcb, **self._block_kwargs))
             inplanes = planes * block.expansion
             self.res_layers.append(name)
         self.feat_dim = block.expansion * 64 * 2 ** (len(self.stage_blocks) - 1)
@@ -498,8 +526,9 @@ class ResNet(nn.Module, PackedMixin):
         whose output only `last` reads (conv1 from registers, the residual at the live pixels), both kernels exist, the compact map has the
         128 pixels of one panel, and the row-panel kernel takes the close at both sizes (its K order does not depend on the row count)."""
         if i not in self.live_store_stages or not self._dead_pixels(i) or not blk.fuse_next or dtype not in native.FUSED_DTYPES \
-                or blk.downsample is not None or blk.stride != 1 or blk.with_dcn or blk.groups > 1 or last.conv1_stride != 1:
-            return False
+                or blk.downsample is not None or blk.stride != 1 or blk.with_dcn or blk.groups > 1 or last.conv1_stride != 1 \
+                or blk.with_gcb or last.with_gcb:
+            return False   # (a context block pools over every pixel of its block's map: nothing of a gcb stage is compacted)
         P, C, LH, LW = blk.width, 4 * blk.planes, (H - 1) // 2 + 1, (W - 1) // 2 + 1
         if not native.tail_next_live_path(B, H, W, P, C, last.width, 2, dtype) or B * LH * LW < 128 \
                 or native.conv2d_path(B, H, W, P, C, dtype=dtype, tile=native.TILE_HINT) != 1:
@@ -517,8 +546,9 @@ class ResNet(nn.Module, PackedMixin):
             return False
         blocks, nxt = getattr(self, self.res_layers[i]), getattr(self, self.res_layers[i + 1])[0]
         last, ds = blocks[-1], nxt.downsample
-        if len(blocks) < 2 or last.downsample is not None or last.stride != 1 or last.with_dcn or last.groups > 1:
-            return False   # (a grouped stage runs at full resolution: its compact forms are not built)
+        if len(blocks) < 2 or last.downsample is not None or last.stride != 1 or last.with_dcn or last.groups > 1 \
+                or any(b.with_gcb for b in blocks):
+            return False   # (a grouped stage runs at full resolution: its compact forms are not built; a context block needs every pixel)
         return (nxt.style == 'caffe' and nxt.conv1_stride == 2 and nxt.conv2_stride == 1 and nxt.conv1.kernel_size == (1, 1)
                 and ds is not None and ds[0].kernel_size == (1, 1) and ds[0].stride == (2, 2))
 

@@ -95,6 +95,10 @@ hipError_t run_res2_conv3x3(const void*, long, const void*, long, void*, long, c
                             hipStream_t);
 hipError_t run_avgpool(const void*, long, void*, long, int, int, int, int, int, int, int, int, int, int, int, hipStream_t);
 hipError_t run_stem3x3s2_first(const float*, const float*, const float*, void*, int, int, int, int, int, hipStream_t);
+void gcb_split(int B, int P, int* S, int* chunk);
+hipError_t run_gcb_pool(const void*, const float*, float*, int, int, int, int, hipStream_t);
+hipError_t run_gcb_transform(const float*, int, int, int, int, const float* const*, const float* const*, float*, float*, hipStream_t);
+hipError_t run_gcb_apply(const void*, const float*, const float*, const void*, void*, int, int, int, int, int, hipStream_t);
 }  // namespace hvr
 
 using namespace hvr;
@@ -714,6 +718,70 @@ int hvr_avgpool_nhwc(const hvr_pool_desc* d, void* stream) {
   return check_launch(run_avgpool(static_cast<const char*>(d->x) + d->x_off * es, d->ldx, static_cast<char*>(d->y) + d->y_off * es, d->ldy, d->B, d->H,
                                   d->W, O[0], O[1], d->C, d->k, d->stride, d->pad, d->count_include_pad ? 1 : 0, d->dtype, (hipStream_t)stream),
                       "hvr_avgpool_nhwc");
+}
+
+// ---- global context block (gcb.hip)
+static int gcb_shape(const char* what, int B, int P, int C) {
+  if (B <= 0 || P <= 0 || C <= 0) return fail(HVR_EINVAL, "%s: empty map B=%d P=%d C=%d", what, B, P, C);
+  if (C % 64 || C > 2048) return fail(HVR_EUNSUPPORTED, "%s: C=%d is no multiple of 64 up to 2048", what, C);
+  if ((long)B * P > 0x7fffffffL / 4) return fail(HVR_EUNSUPPORTED, "%s: %ld pixels", what, (long)B * P);
+  return HVR_OK;
+}
+int hvr_gcb_supported(int C, int dtype) { return C > 0 && C % 64 == 0 && C <= 2048 && (dtype == HVR_F32 || dtype == HVR_BF16 || dtype == HVR_F16); }
+int hvr_gcb_splits(int B, int P, int C) {
+  if (B <= 0 || P <= 0 || C <= 0) return 0;
+  int S, chunk;
+  gcb_split(B, P, &S, &chunk);
+  return S;
+}
+size_t hvr_gcb_workspace_bytes(int B, int P, int C) {
+  const int S = hvr_gcb_splits(B, P, C);
+  return align256((size_t)B * S * (C + 4) * sizeof(float));
+}
+int hvr_gcb_pool(const void* u, const float* wm, void* ws, size_t ws_bytes, int B, int P, int C, int dtype, void* stream) {
+  if (!valid_dtype(dtype)) return fail(HVR_EINVAL, "hvr_gcb_pool: bad dtype %d", dtype);
+  if (dtype == HVR_F16S) return fail(HVR_EUNSUPPORTED, "hvr_gcb_pool: no split-half instance (pool the f32 form)");
+  if (int rc = gcb_shape("hvr_gcb_pool", B, P, C)) return rc;
+  if (!u || !ws || !aligned16(u) || !aligned16(ws) || (wm && !aligned16(wm))) return fail(HVR_EINVAL, "hvr_gcb_pool: u, wm and ws must be 16-byte aligned device pointers");
+  if (ws_bytes < hvr_gcb_workspace_bytes(B, P, C)) return fail(HVR_EWORKSPACE, "hvr_gcb_pool: workspace of %zu bytes, %zu needed", ws_bytes, hvr_gcb_workspace_bytes(B, P, C));
+  return check_launch(run_gcb_pool(u, wm, (float*)ws, B, P, C, dtype, (hipStream_t)stream), "hvr_gcb_pool");
+}
+int hvr_gcb_transform(const void* ws, size_t ws_bytes, int B, int P, int C, int R, const hvr_gcb_mlp* mul, const hvr_gcb_mlp* add, float* m, float* t,
+                      void* stream) {
+  if (int rc = gcb_shape("hvr_gcb_transform", B, P, C)) return rc;
+  if (R < 1 || R > 2048) return fail(R < 1 ? HVR_EINVAL : HVR_EUNSUPPORTED, "hvr_gcb_transform: %d bottleneck channels (1 .. 2048)", R);
+  if (!mul && !add) return fail(HVR_EINVAL, "hvr_gcb_transform: neither fusion branch given");
+  if (!ws || !aligned16(ws) || (mul && !m) || (add && !t)) return fail(HVR_EINVAL, "hvr_gcb_transform: null or misaligned pointer");
+  const size_t slab_bytes = (size_t)B * hvr_gcb_splits(B, P, C) * (C + 4) * sizeof(float);   // (the partials themselves: hvr_gcb_workspace_bytes rounds up)
+  if (ws_bytes < slab_bytes) return fail(HVR_EWORKSPACE, "hvr_gcb_transform: partials of %zu bytes, %zu needed", ws_bytes, slab_bytes);
+  const float* pm[6];
+  const float* pa[6];
+  for (int k = 0; k < 2; ++k) {
+    const hvr_gcb_mlp* w = k == 0 ? mul : add;
+    if (!w) continue;
+    const float** dst = k == 0 ? pm : pa;
+    dst[0] = w->w1; dst[1] = w->b1; dst[2] = w->gamma; dst[3] = w->beta; dst[4] = w->w2t; dst[5] = w->b2;
+    for (int i = 0; i < 6; ++i)
+      if (!dst[i]) return fail(HVR_EINVAL, "hvr_gcb_transform: null weight pointer");
+    if (!aligned16(w->w1)) return fail(HVR_EINVAL, "hvr_gcb_transform: w1 must be 16-byte aligned");
+  }
+  return check_launch(run_gcb_transform((const float*)ws, B, P, C, R, mul ? pm : nullptr, add ? pa : nullptr, m, t, (hipStream_t)stream), "hvr_gcb_transform");
+}
+int hvr_gcb_apply(const void* u, const float* m, const float* t, const void* resid, void* y, int B, int P, int C, int relu, int dtype, void* stream) {
+  if (!valid_dtype(dtype)) return fail(HVR_EINVAL, "hvr_gcb_apply: bad dtype %d", dtype);
+  if (dtype == HVR_F16S) return fail(HVR_EUNSUPPORTED, "hvr_gcb_apply: no split-half instance (apply on the f32 form)");
+  if (int rc = gcb_shape("hvr_gcb_apply", B, P, C)) return rc;
+  if (!u || !y || !aligned16(u) || !aligned16(y) || (resid && !aligned16(resid)) || (m && !aligned16(m)) || (t && !aligned16(t)))
+    return fail(HVR_EINVAL, "hvr_gcb_apply: operands must be 16-byte aligned device pointers");
+  // y may BE u or resid (same address); any other overlap would let one lane read what another has written
+  const size_t bytes = (size_t)B * P * C * elem_size(dtype);
+  const void* ins[2] = {u, resid};
+  for (const void* x : ins) {
+    if (!x || x == y) continue;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(y);
+    if (a < b + bytes && b < a + bytes) return fail(HVR_EINVAL, "hvr_gcb_apply: y overlaps an input without being it");
+  }
+  return check_launch(run_gcb_apply(u, m, t, resid, y, B, P, C, relu ? 1 : 0, dtype, (hipStream_t)stream), "hvr_gcb_apply");
 }
 
 int hvr_stem3x3s2_first(const float* img, const float* w, const float* bias, void* y, int B, int H, int W, int ldy, int dtype, void* stream) {

@@ -87,6 +87,10 @@ class PoolDesc(ctypes.Structure):           # hvr_pool_desc
                 ('dtype', ctypes.c_int32)]
 
 
+class GcbMlp(ctypes.Structure):             # hvr_gcb_mlp
+    _fields_ = [(n, ctypes.c_void_p) for n in ('w1', 'b1', 'gamma', 'beta', 'w2t', 'b2')]
+
+
 class TailDesc(ctypes.Structure):
     _fields_ = [('h', ctypes.c_void_p), ('x', ctypes.c_void_p), ('w', ctypes.c_void_p), ('y', ctypes.c_void_p),
                 ('B', ctypes.c_int32), ('OH', ctypes.c_int32), ('OW', ctypes.c_int32), ('C1', ctypes.c_int32),
@@ -197,6 +201,12 @@ SYMBOLS = {
     'hvr_deform_im2col_supported': (_i, [_i, _i, _i]),
     'hvr_deform_im2col': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i, _vp]),
     'hvr_deform_roi_pool_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i64, _i64, _i, _vp]),
+    'hvr_gcb_supported': (_i, [_i, _i]),
+    'hvr_gcb_splits': (_i, [_i, _i, _i]),
+    'hvr_gcb_workspace_bytes': (_sz, [_i, _i, _i]),
+    'hvr_gcb_pool': (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    'hvr_gcb_transform': (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(GcbMlp), ctypes.POINTER(GcbMlp), _vp, _vp, _vp]),
+    'hvr_gcb_apply': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'hvr_nms_workspace_bytes': (_sz, [_i]),
     'hvr_nms_first': (_i, [_vp, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'hvr_nms': (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -1686,6 +1696,118 @@ def deform_roi_pool(feat_nhwc, rois, trans, mask_logit, out_size, out_channels, 
                                              int(out_channels), int(group_size), part_size, ncls, int(sample_per_part), float(spatial_scale),
                                              float(trans_std), ldt, ldm, _dt(feat_nhwc), _stream()), 'hvr_deform_roi_pool_fwd')
     return out
+
+
+# ---- global context block (csrc/gcb.hip; the rule: include/hvr_hip.h)
+def gcb_supported(C, dtype):
+    """True when the context-block kernels take maps of C channels in the compute format `dtype` (C a multiple of 64 up to 2048; split
+    half runs the f32 kernels, cast in and out).  Every other shape is refused with HvrError: there is no second path."""
+    return bool(lib().hvr_gcb_supported(int(C), DTYPE_CODES[torch.float32 if dtype == SPLIT else dtype]))
+
+
+def gcb_splits(B, P, C):
+    """The runs the pool cuts a frame's P pixels into: a function of the shape only."""
+    return int(lib().hvr_gcb_splits(int(B), int(P), int(C)))
+
+
+def _gcb_map(u, what):
+    if u.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise HvrError('%s: a %s map (float32 / bfloat16 / float16; split half goes through context_block)' % (what, u.dtype))
+    if u.dim() != 4 or not u.is_contiguous():
+        raise HvrError('%s: the map must be a contiguous physical NHWC tensor, got shape %s strides %s' % (what, tuple(u.shape), u.stride()))
+    B, H, W, C = u.shape
+    if not gcb_supported(C, u.dtype):
+        raise HvrError('%s: C=%d is no multiple of 64 up to 2048 (no kernel, no fallback)' % (what, C))
+    return B, H * W, C
+
+
+def _gcb_f32(t, shape, what):
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise HvrError('%s must be a contiguous float32 tensor of shape %s, got %s %s' % (what, tuple(shape), t.dtype, tuple(t.shape)))
+    return t
+
+
+def gcb_pool(u, wm=None):
+    """One pass over u [B,H,W,C] (bf16 / half / f32): per frame and pixel run an online-softmax partial (max, sum, acc[C]) of the attention
+    pool with mask weights wm f32 [C] (None: the average pool) -> the f32 workspace slab hvr_gcb_transform reads (a view of
+    native._workspace: valid until the next gcb_pool on this stream)."""
+    _need_cuda(u, wm)
+    B, P, C = _gcb_map(u, 'gcb_pool')
+    if wm is not None:
+        _gcb_f32(wm, (C,), 'gcb_pool: wm')
+    nbytes = lib().hvr_gcb_workspace_bytes(B, P, C)
+    ws = _workspace(nbytes, u.device, 'gcb')
+    with _span('gcb_pool', float(B * P * C * u.element_size())):
+        _check(lib().hvr_gcb_pool(_ptr(u), _ptr(wm), _ptr(ws), nbytes, B, P, C, _dt(u), _stream()), 'hvr_gcb_pool')
+    return ws[:nbytes].view(torch.float32)[:B * gcb_splits(B, P, C) * (C + 4)].view(B, -1, C + 4)
+
+
+def _gcb_mlp(branch, C, what):
+    if branch is None:
+        return None, None
+    w1, b1, gamma, beta, w2t, b2 = branch
+    R = w1.shape[0]
+    _gcb_f32(w1, (R, C), what + ' w1'), _gcb_f32(b1, (R,), what + ' b1'), _gcb_f32(gamma, (R,), what + ' gamma')
+    _gcb_f32(beta, (R,), what + ' beta'), _gcb_f32(w2t, (R, C), what + ' w2t'), _gcb_f32(b2, (C,), what + ' b2')
+    return GcbMlp(*[t.data_ptr() for t in branch]), R
+
+
+def gcb_transform(partials, P, mul=None, add=None):
+    """partials [B,S,C+4] (gcb_pool's, of frames of P pixels) -> (m [B,C] f32 or None, t [B,C] f32 or None): the context of every frame
+    through the bottleneck transforms.  mul / add: (w1 [R,C], b1 [R], ln_weight [R], ln_bias [R], w2t [R,C] = W2 transposed, b2 [C]), all
+    f32, or None for an absent branch; m = sigmoid(transform_mul(ctx)), t = transform_add(ctx)."""
+    _need_cuda(partials)
+    if mul is None and add is None:
+        raise HvrError('gcb_transform: neither fusion branch given')
+    B, S, C4 = partials.shape
+    C = C4 - 4
+    if partials.dtype != torch.float32 or not partials.is_contiguous() or S != gcb_splits(B, P, C):
+        raise HvrError('gcb_transform: partials %s %s are not gcb_pool\'s of %d frames of %d pixels' % (partials.dtype, tuple(partials.shape), B, P))
+    sm, Rm = _gcb_mlp(mul, C, 'gcb_transform: mul')
+    sa, Ra = _gcb_mlp(add, C, 'gcb_transform: add')
+    if Rm is not None and Ra is not None and Rm != Ra:
+        raise HvrError('gcb_transform: the branches have %d and %d bottleneck channels' % (Rm, Ra))
+    m = torch.empty((B, C), dtype=torch.float32, device=partials.device) if mul is not None else None
+    t = torch.empty((B, C), dtype=torch.float32, device=partials.device) if add is not None else None
+    with _span('gcb_transform', float(partials.numel() * 4)):
+        _check(lib().hvr_gcb_transform(_ptr(partials), partials.numel() * 4, B, P, C, Rm if Rm is not None else Ra,
+                                       ctypes.byref(sm) if sm is not None else None, ctypes.byref(sa) if sa is not None else None, _ptr(m), _ptr(t),
+                                       _stream()), 'hvr_gcb_transform')
+    return m, t
+
+
+def gcb_apply(u, m=None, t=None, resid=None, relu=False, out=None):
+    """y = act(u * m[n,c] + t[n,c] (+ resid)) in f32, rounded once into u's format.  u [B,H,W,C] bf16 / half / f32, m / t f32 [B,C] or None
+    (1 / 0), resid like u or None.  out: a contiguous tensor like u; it may BE u (or resid)."""
+    _need_cuda(u, m, t, resid, out)
+    B, P, C = _gcb_map(u, 'gcb_apply')
+    for x, what in ((m, 'm'), (t, 't')):
+        if x is not None:
+            _gcb_f32(x, (B, C), 'gcb_apply: ' + what)
+    for x, what in ((resid, 'resid'), (out, 'out')):
+        if x is not None and (x.dtype != u.dtype or tuple(x.shape) != tuple(u.shape) or not x.is_contiguous()):
+            raise HvrError('gcb_apply: %s is %s %s, the map %s %s (same format, same shape, contiguous)' % (what, x.dtype, tuple(x.shape), u.dtype, tuple(u.shape)))
+    out = torch.empty_like(u) if out is None else out
+    with _span('gcb_apply', float((2 + (resid is not None)) * B * P * C * u.element_size())):
+        _check(lib().hvr_gcb_apply(_ptr(u), _ptr(m), _ptr(t), _ptr(resid), _ptr(out), B, P, C, int(bool(relu)), _dt(u), _stream()), 'hvr_gcb_apply')
+    return out
+
+
+def context_block(u, packed, resid=None, relu=False, out=None):
+    """The whole block on u [B,H,W,C] in a compute format: pool -> transform -> apply (three launches) -> act(u * m + t (+ resid)).
+    packed: dict(wm=f32 [C] or None ('avg'), mul=branch or None, add=branch or None) as gcb_transform takes them (ops.ContextBlock.packed).
+    Split half goes through f32 and back, as avgpool_nhwc does.  out as in gcb_apply."""
+    _need_cuda(u)
+    if u.dtype == SPLIT:
+        y = context_block(cast(u, torch.float32), packed, None if resid is None else cast(resid, torch.float32), relu)
+        y = cast(y, SPLIT)
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
+    B, P, C = _gcb_map(u, 'context_block')
+    m, t = gcb_transform(gcb_pool(u, packed.get('wm')), P, packed.get('mul'), packed.get('add'))
+    return gcb_apply(u, m, t, resid, relu, out)
 
 
 def nms_first(dets, iou_thr, max_keep, ge_semantics=True):

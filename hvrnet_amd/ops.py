@@ -292,6 +292,74 @@ class ModulatedDeformRoIPoolingPack(_DeformRoIPoolingPackBase):
         self._init_packed()
 
 
+class ContextBlock(nn.Module, PackedMixin):
+    """mmdet/ops/context_block.py:13-104, the global context block of GCNet: the reference's constructor arguments, assertions,
+    parameter names and shapes (conv_mask.*, channel_add_conv.{0,1,3}.*, channel_mul_conv.{0,1,3}.*, LayerNorm weights [planes,1,1]), so
+    checkpoints load strictly.  GPU forward only, inference only: pool, transform and apply are native.gcb_* (three launches, no
+    torch kernel).  conv_mask.bias shifts every logit of a frame alike and cancels in the softmax: it is loaded and not used."""
+
+    def __init__(self, inplanes, ratio, pooling_type='att', fusion_types=('channel_add', )):
+        super(ContextBlock, self).__init__()
+        assert pooling_type in ['avg', 'att']
+        assert isinstance(fusion_types, (list, tuple))
+        valid_fusion_types = ['channel_add', 'channel_mul']
+        assert all([f in valid_fusion_types for f in fusion_types])
+        assert len(fusion_types) > 0, 'at least one fusion should be used'
+        self.inplanes, self.ratio, self.planes = inplanes, ratio, int(inplanes * ratio)   # (int() truncates)
+        self.pooling_type, self.fusion_types = pooling_type, fusion_types
+        if pooling_type == 'att':
+            self.conv_mask = nn.Conv2d(inplanes, 1, kernel_size=1)
+            self.softmax = nn.Softmax(dim=2)
+        else:
+            self.avg_pool = nn.AdaptiveAvgPool2d(1)
+
+        def branch():
+            return nn.Sequential(nn.Conv2d(self.inplanes, self.planes, kernel_size=1), nn.LayerNorm([self.planes, 1, 1]), nn.ReLU(inplace=True),
+                                 nn.Conv2d(self.planes, self.inplanes, kernel_size=1))
+        self.channel_add_conv = branch() if 'channel_add' in fusion_types else None
+        self.channel_mul_conv = branch() if 'channel_mul' in fusion_types else None
+        self.reset_parameters()
+        self._init_packed()
+
+    def reset_parameters(self):
+        """context_block.py:54-62: kaiming (fan_in, normal, zero bias) on the mask; the LAST conv of each branch zero, so that a fresh block
+        adds 0 (channel_add) or scales by sigmoid(0) = 1/2 (channel_mul)."""
+        if self.pooling_type == 'att':
+            nn.init.kaiming_normal_(self.conv_mask.weight, a=0, mode='fan_in', nonlinearity='relu')
+            nn.init.constant_(self.conv_mask.bias, 0)
+            self.conv_mask.inited = True
+        for seq in (self.channel_add_conv, self.channel_mul_conv):
+            if seq is not None:
+                nn.init.constant_(seq[-1].weight, 0)
+                nn.init.constant_(seq[-1].bias, 0)
+
+    def _pack(self, dtype):
+        """f32 in every compute format (include/hvr_hip.h: everything between the map and the apply is f32); W2 transposed."""
+        def f32(t, *shape):
+            return t.detach().float().reshape(*shape).contiguous()
+
+        def branch(seq):
+            if seq is None:
+                return None
+            C, R = self.inplanes, self.planes
+            return (f32(seq[0].weight, R, C), f32(seq[0].bias, R), f32(seq[1].weight, R), f32(seq[1].bias, R),
+                    f32(seq[3].weight, C, R).t().contiguous(), f32(seq[3].bias, C))
+        return dict(wm=f32(self.conv_mask.weight, self.inplanes) if self.pooling_type == 'att' else None,
+                    mul=branch(self.channel_mul_conv), add=branch(self.channel_add_conv))
+
+    def forward_nhwc(self, u, resid=None, relu=False, out=None):
+        """u physical NHWC in a compute format -> act(block(u) (+ resid)); a Bottleneck hands in its identity and relu=True."""
+        if self.planes < 1:
+            raise native.HvrError('ContextBlock: int(%d * %r) = 0 bottleneck channels' % (self.inplanes, self.ratio))
+        return native.context_block(u, self.packed(u.device), resid, relu, out)
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise NotImplementedError('ContextBlock runs on the GPU only (no CPU fallback)')
+        from .backbone import as_logical, as_nhwc
+        return as_logical(self.forward_nhwc(as_nhwc(x, self.compute_dtype)))   # (in the compute format, as Bottleneck.forward)
+
+
 class RelationFunction(Function):
     """o = softmax(scale * q k^T) v with a HIP backward (the reference differentiates torch.bmm / nn.Softmax / torch.mm,
     selsa_bbox_head.py:166-182, through autograd).  Backward = one score pass (probabilities recomputed, not stored),

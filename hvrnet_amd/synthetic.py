@@ -49,7 +49,25 @@ def _bn(g, sd, prefix, c, gamma_scale=1.0):
     sd[prefix + '.num_batches_tracked'] = torch.zeros((), dtype=torch.long)
 
 
-def _res_layer(g, sd, prefix, inplanes, planes, blocks, groups=1, base_width=4):
+def _gcb(g, sd, prefix, c, ratio, pooling_type='att', fusion_types=('channel_add', )):
+    """Keys of a ContextBlock (context_block.py:31-51).  The reference zeroes the last conv of each branch, which makes a fresh block the
+    identity (channel_add) or a constant 1/2 (channel_mul): here it gets values, so that the block shows in the output."""
+    r = int(c * ratio)
+    if pooling_type == 'att':
+        sd[prefix + '.conv_mask.weight'] = torch.randn((1, c, 1, 1), generator=g) * math.sqrt(2.0 / c)
+        sd[prefix + '.conv_mask.bias'] = torch.randn(1, generator=g) * 0.1
+    for name in ('channel_add', 'channel_mul'):   # (the reference registers add first)
+        if name in fusion_types:
+            q = '%s.%s_conv' % (prefix, name)
+            sd[q + '.0.weight'] = torch.randn((r, c, 1, 1), generator=g) * math.sqrt(2.0 / c)
+            sd[q + '.0.bias'] = torch.randn(r, generator=g) * 0.1
+            sd[q + '.1.weight'] = (torch.rand(r, generator=g) + 0.5).view(r, 1, 1)
+            sd[q + '.1.bias'] = (torch.randn(r, generator=g) * 0.1).view(r, 1, 1)
+            sd[q + '.3.weight'] = torch.randn((c, r, 1, 1), generator=g) * (0.25 * math.sqrt(1.0 / r))
+            sd[q + '.3.bias'] = torch.randn(c, generator=g) * 0.05
+
+
+def _res_layer(g, sd, prefix, inplanes, planes, blocks, groups=1, base_width=4, gcb=None):
     width = planes if groups == 1 else int(math.floor(planes * (base_width / 64))) * groups   # resnext.py:21-24
     for i in range(blocks):
         p = '%s.%d' % (prefix, i)
@@ -64,6 +82,8 @@ def _res_layer(g, sd, prefix, inplanes, planes, blocks, groups=1, base_width=4):
         if i == 0:
             sd[p + '.downsample.0.weight'] = _conv(g, planes * 4, cin, 1)
             _bn(g, sd, p + '.downsample.1', planes * 4)
+        if gcb is not None:
+            _gcb(g, sd, p + '.context_block', planes * 4, **gcb)
 
 
 def _res2_layer(g, sd, prefix, inplanes, planes, blocks, base_width=26, scale=4):
@@ -92,10 +112,14 @@ def _linear(g, sd, prefix, cout, cin, gain, conv=False):
     sd[prefix + '.bias'] = torch.randn(cout, generator=g) * 0.01
 
 
-def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024, roi_feat=256 * 49, groups=1, base_width=4, arch='resnet'):
+def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024, roi_feat=256 * 49, groups=1, base_width=4, arch='resnet',
+                     gcb=None, stage_with_gcb=(False, True, True)):
     """Full detector state dict (f32, CPU) with the reference's key names.  groups / base_width: a ResNeXt backbone + ResXLayer.
-    arch='res2net': a Res2Net backbone (101 layers, 26w x 4s, deep stem) + Res2Layer; the heads' keys are the same."""
+    arch='res2net': a Res2Net backbone (101 layers, 26w x 4s, deep stem) + Res2Layer; the heads' keys are the same.
+    gcb: dict(ratio=..., pooling_type=..., fusion_types=...) adds the context-block keys to the backbone stages marked in stage_with_gcb
+    (ResNet / ResNeXt), with non-zero last convs; None (the default) leaves every key and value as before."""
     assert arch in ('resnet', 'res2net'), arch
+    assert gcb is None or arch == 'resnet', 'Res2Net takes no context blocks'
     g = torch.Generator().manual_seed(seed)
     sd = {}
     blocks = STAGE_BLOCKS[depth]
@@ -116,7 +140,8 @@ def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024,
         _bn(g, sd, 'backbone.bn1', 64)
         inplanes = 64
         for i in range(3):
-            _res_layer(g, sd, 'backbone.layer%d' % (i + 1), inplanes, 64 * 2 ** i, blocks[i], groups, base_width)
+            _res_layer(g, sd, 'backbone.layer%d' % (i + 1), inplanes, 64 * 2 ** i, blocks[i], groups, base_width,
+                       gcb if gcb is not None and stage_with_gcb[i] else None)
             inplanes = 64 * 2 ** i * 4
         _res_layer(g, sd, 'shared_head.layer4', 1024, 512, blocks[3], groups, base_width)
     sd['shared_head.new_layer_1.conv.weight'] = _conv(g, 256, 2048, 1) * NEW_LAYER_GAIN

@@ -234,6 +234,41 @@ typedef struct hvr_pool_desc {
 } hvr_pool_desc;
 int hvr_avgpool_nhwc(const hvr_pool_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Global context block (GCNet), forward only.  Replaces mmdet/ops/context_block.py:64-104 and the residual add + ReLU behind it
+ * in a Bottleneck (resnet.py:249-264).  u [B][P][C] is a physical NHWC map (P = H * W pixels per frame) in `dtype` = HVR_F32 /
+ * HVR_BF16 / HVR_F16 (HVR_F16S: HVR_EUNSUPPORTED; run the f32 form); C a multiple of 64 up to 2048, any P >= 1, any B >= 1
+ * (hvr_gcb_supported answers 1 / 0 for C and dtype; anything else is refused, there is no other path).  The rule, per frame n:
+ *   pool       l[p]   = sum_c u[p][c] * wm[c]                   (wm NULL, the 'avg' pooling: l = 0)
+ *              a[p]   = exp(l[p] - max_q l[q]) / sum_q exp(l[q] - max_q l[q])
+ *              ctx[c] = sum_p a[p] * u[p][c]
+ *              (conv_mask's bias shifts every logit of a frame alike and cancels: it is not an argument)
+ *   transform  h = W1 ctx + b1                                  W1 [R][C], R = int(C * ratio) >= 1
+ *              g = relu((h - mean(h)) / sqrt(var(h) + 1e-5) * gamma + beta)      var = the BIASED variance over the R values
+ *              o = W2 g + b2                                    passed TRANSPOSED: w2t [R][C]
+ *              m[n][c] = 1 / (1 + exp(-o_mul[c]))               t[n][c] = o_add[c]
+ *   apply      y = act(u * m[n][c] + t[n][c] (+ resid))         the product first, then t, then resid; act = ReLU when relu != 0
+ * u is read in its stored format; everything from the logits to m and t is f32 (f32 weights, f32 accumulation); the apply is f32
+ * and rounds ONCE into `dtype`.  The pool is an online softmax: the pixels of a frame are cut into S = hvr_gcb_splits(B, P, C)
+ * runs (a function of the shape only), every run keeps a running maximum, sum and acc[C] that is rescaled when the maximum grows,
+ * and writes ONE f32 partial (max, sum, 0, 0, acc[C]) to ws [B][S][C + 4]; the transform takes the maximum over the runs, rescales
+ * and divides.  No float atomics: two runs of a call give the same bits.  An absent fusion branch is a NULL hvr_gcb_mlp pointer (and a
+ * NULL m or t in the apply: m = 1, t = 0); at least one must be given.  y may be u or resid itself (same address), no other
+ * overlap.  ws: hvr_gcb_workspace_bytes(B, P, C) bytes, 16-byte aligned, written by hvr_gcb_pool and read by hvr_gcb_transform on
+ * the same stream.  No host synchronisation, no allocation.
+ * ---------------------------------------------------------------------------------- */
+typedef struct hvr_gcb_mlp {
+  const float* w1; const float* b1; const float* gamma; const float* beta; const float* w2t; const float* b2;
+} hvr_gcb_mlp;
+int hvr_gcb_supported(int C, int dtype);
+int hvr_gcb_splits(int B, int P, int C);
+size_t hvr_gcb_workspace_bytes(int B, int P, int C);
+int hvr_gcb_pool(const void* u, const float* wm, void* ws, size_t ws_bytes, int B, int P, int C, int dtype, void* stream);
+int hvr_gcb_transform(const void* ws, size_t ws_bytes, int B, int P, int C, int R, const hvr_gcb_mlp* mul, const hvr_gcb_mlp* add, float* m,
+                      float* t, void* stream);
+int hvr_gcb_apply(const void* u, const float* m, const float* t, const void* resid, void* y, int B, int P, int C, int relu, int dtype,
+                  void* stream);
+
 /* First conv of Res2Net's deep stem (res2net_v1b.py:174-177: Conv 3 -> 32, 3x3, stride 2, pad 1 + frozen BN + ReLU) read from the
  * f32 NCHW image img [B][3][H][W]: w f32 [32][3][3][3] as [n][ky][kx][c] and bias f32 [32] with the BN folded in; y [B][OH][OW][ldy]
  * NHWC in `dtype` (HVR_F32, HVR_BF16 or HVR_F16), OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1.  f32 FMAs, one rounding.  ldy >= 32,
