@@ -182,17 +182,20 @@ class Bottleneck(nn.Module, PackedMixin):
     expansion = 4
 
     def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, style='pytorch', norm_cfg=None, dcn=None, groups=1, base_width=4,
-                 gcb=None):
+                 gcb=None, gen_attention=None):
         super(Bottleneck, self).__init__()
         assert style in ['pytorch', 'caffe']
         assert dcn is None or isinstance(dcn, dict)
         assert gcb is None or isinstance(gcb, dict)
+        assert gen_attention is None or isinstance(gen_attention, dict)
         self.inplanes, self.planes, self.stride, self.dilation, self.style = inplanes, planes, stride, dilation, style
         # resnext.py:21-24: the channels of conv1's output, conv2 and conv3's input (a ResNet block: planes)
         self.groups, self.base_width = groups, base_width
         self.width = width = planes if groups == 1 else int(math.floor(planes * (base_width / 64))) * groups
         if groups > 1 and dcn is not None:
             raise NotImplementedError('dcn on a grouped Bottleneck (the dcn[\'groups\'] form of resnext.py:57-83) is not built')
+        if groups > 1 and gen_attention is not None:
+            raise NotImplementedError('gen_attention on a grouped Bottleneck is not built (the reference\'s resnext.py accepts the argument and drops it)')
         # caffe: stride on the first 1x1 (resnet.py:127-132)
         self.conv1_stride, self.conv2_stride = (1, stride) if style == 'pytorch' else (stride, 1)
         eps = (norm_cfg or {}).get('eps', 1e-5)
@@ -218,6 +221,11 @@ class Bottleneck(nn.Module, PackedMixin):
         if self.with_gcb:
             from .ops import ContextBlock   # (ops imports this module)
             self.context_block = ContextBlock(inplanes=planes * self.expansion, **gcb)
+        # resnet.py:203-206,243-244: the generalized attention block acts on relu(bn2(conv2)), in front of conv3
+        self.gen_attention, self.with_gen_attention = gen_attention, gen_attention is not None
+        if self.with_gen_attention:
+            from .ops import GeneralizedAttention   # (ops imports this module)
+            self.gen_attention_block = GeneralizedAttention(planes, **gen_attention)
         self._init_packed()
 
     def _pack(self, dtype):
@@ -265,9 +273,14 @@ class Bottleneck(nn.Module, PackedMixin):
             return Step('tail')
         return Step('conv', downsample=proj)
 
-    def body(self, x, h1=None, compact_in=False, conv2_stride=None, out=None):
+    def body(self, x, h1=None, compact_in=False, conv2_stride=None, out=None, conv2_only=False):
         """conv1 (unless h1, its output, was handed in by the block before) and conv2 or the deformable pair -> the closing 1x1's input.
-        compact_in (a caffe-style stride-2 block): x holds only the pixels the strided 1x1 convs read, so they run at stride 1."""
+        compact_in (a caffe-style stride-2 block): x holds only the pixels the strided 1x1 convs read, so they run at stride 1.
+        A block with a generalized attention block applies it here, to conv2's output at every pixel (conv2_only: without it): every close
+        that only reads h ('conv', 'tail', 'tail_next', 'gcb') stays available to it; the sampled and compact forms are not (ResNet._dead_pixels)."""
+        if self.with_gen_attention and not conv2_only:
+            assert conv2_stride is None, 'a block with gen_attention has no sampled form'
+            return self.gen_attention_block.forward_nhwc(self.body(x, h1, compact_in, conv2_only=True), out=out)
         p = self.packed(x.device if h1 is None else h1.device)
         h = h1 if h1 is not None else native.conv2d_nhwc(x, p['c1'][0], p['c1'][1], relu=True, stride=1 if compact_in else self.conv1_stride)
         s2 = self.conv2_stride if conv2_stride is None else conv2_stride
@@ -278,6 +291,9 @@ class Bottleneck(nn.Module, PackedMixin):
         if self.groups > 1:
             return native.conv3x3_grouped(h, p['c2'][0], p['c2'][1], True, s2, self.dilation, out=out, route=self.grouped_route)
         return native.conv2d_nhwc(h, p['c2'][0], p['c2'][1], relu=True, stride=s2, pad=self.dilation, dil=self.dilation, out=out)
+
+    def _conv2(self, x, h1, compact_in, conv2_stride, out):
+        return self.body(x, h1, compact_in, conv2_stride, out, conv2_only=True)
 
     def close(self, x, h, step, out=None, compact_in=False):
         """The plain close ('tail', 'conv' or 'gcb') -> y.  out: where y goes (a contiguous [B,OH,OW,4*planes] tensor), e.g. a frame group's slice."""
@@ -313,7 +329,7 @@ class Bottleneck(nn.Module, PackedMixin):
     def close_sampled(self, x, h1=None, stride=2):
         """'close_sampled' at stride 2, the whole of an identity block whose output only a stride-`stride` 1x1 consumer reads: conv1 everywhere (the
         3x3 reads neighbours), conv2 at that stride, the close with the residual sampled from x -> the full output at [:, ::stride, ::stride]."""
-        assert self.downsample is None and self.stride == 1 and not self.with_dcn
+        assert self.downsample is None and self.stride == 1 and not self.with_dcn and not self.with_gen_attention
         B, H, W, _ = x.shape
         hs = torch.empty((B, (H - 1) // stride + 1, (W - 1) // stride + 1, self.width), dtype=x.dtype, device=x.device)
         self.body(x, h1, conv2_stride=stride, out=hs)
@@ -322,7 +338,7 @@ class Bottleneck(nn.Module, PackedMixin):
     def close_compact(self, x_live, h1, stride=2, plain=False):
         """The same block behind close_next_live: x_live is its input at [:, ::stride, ::stride] only, h1 its conv1 output at full resolution,
         and the close is dense on the compact map: 'close_sampled' at stride 1, or with `plain` 'conv' (the same row-panel kernel and sums)."""
-        assert self.downsample is None and self.stride == 1 and not self.with_dcn
+        assert self.downsample is None and self.stride == 1 and not self.with_dcn and not self.with_gen_attention
         assert tuple(x_live.shape[1:3]) == ((h1.shape[1] - 1) // stride + 1, (h1.shape[2] - 1) // stride + 1)
         w3, b3 = self.packed(h1.device)['c3']
         hs = self.body(None, h1, conv2_stride=stride)
@@ -350,6 +366,8 @@ class Bottleneck(nn.Module, PackedMixin):
             raise NotImplementedError('grouped Bottlenecks are inference only: the grouped 3x3 conv has no backward')
         if self.with_gcb:
             raise NotImplementedError('Bottlenecks with a context block are inference only: the pool has no backward')
+        if self.with_gen_attention:
+            raise NotImplementedError('Bottlenecks with a generalized attention block are inference only: the attention core has no backward')
         from . import train_ops as TO
         out = TO.conv_bn(x, self.conv1, self.bn1, relu=True)
         out = TO.conv_bn(out, self.conv2, self.bn2, relu=True)
@@ -358,7 +376,7 @@ class Bottleneck(nn.Module, PackedMixin):
 
 
 def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style='pytorch', norm_cfg=None, dcn=None, groups=1, base_width=4, gcb=None,
-                   **_unused):
+                   gen_attention=None, gen_attention_blocks=(), **_unused):
     downsample = None
     eps = (norm_cfg or {}).get('eps', 1e-5)
     if stride != 1 or inplanes != planes * block.expansion:
@@ -369,10 +387,13 @@ def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style=
         extra.update(groups=groups, base_width=base_width)
     if gcb is not None:
         extra.update(gcb=gcb)
-    layers = [block(inplanes, planes, stride, dilation, downsample, style=style, norm_cfg=norm_cfg, **extra)]
+
+    def att(i):   # resnet.py:310-327: the blocks of the stage named in gen_attention_blocks
+        return dict(gen_attention=gen_attention) if gen_attention is not None and i in gen_attention_blocks else {}
+    layers = [block(inplanes, planes, stride, dilation, downsample, style=style, norm_cfg=norm_cfg, **extra, **att(0))]
     inplanes = planes * block.expansion
-    for _ in range(1, blocks):
-        layers.append(block(inplanes, planes, 1, dilation, style=style, norm_cfg=norm_cfg, **extra))
+    for i in range(1, blocks):
+        layers.append(block(inplanes, planes, 1, dilation, style=style, norm_cfg=norm_cfg, **extra, **att(i)))
     return nn.Sequential(*layers)
 
 
@@ -386,7 +407,8 @@ def _freeze(module):
 class ResNet(nn.Module, PackedMixin):
     """Same kwargs as the reference ResNet (resnet.py:372-395); dcn / stage_with_dcn as there (deformable conv2 in the marked
     stages, inference only); gcb / stage_with_gcb as there (a global context block between bn3 and the residual add of every block of the
-    marked stages, inference only); gen_attention / conv_cfg must be None."""
+    marked stages, inference only); gen_attention / stage_with_gen_attention as there (a generalized attention block between conv2 and conv3
+    of the blocks named per stage, inference only); conv_cfg must be None."""
     arch_settings = {d: (Bottleneck, s) for d, s in ARCH_SETTINGS.items()}
     _block_kwargs = {}   # what every block gets beyond the reference ResNet's arguments (ResNeXt: groups, base_width)
 
@@ -398,8 +420,22 @@ class ResNet(nn.Module, PackedMixin):
         super(ResNet, self).__init__()
         if depth not in self.arch_settings:
             raise KeyError('invalid depth {} for resnet'.format(depth))
-        if gen_attention is not None or conv_cfg is not None:
-            raise NotImplementedError('gen_attention / conv_cfg are outside the HVR hot path')
+        if conv_cfg is not None:
+            raise NotImplementedError('conv_cfg is outside the HVR hot path')
+        block, stage_blocks = self.arch_settings[depth]
+        if gen_attention is not None:
+            assert isinstance(gen_attention, dict), gen_attention
+            marked = [tuple(stage_with_gen_attention[i]) if i < len(stage_with_gen_attention) else () for i in range(num_stages)]
+            for i, idx in enumerate(marked):
+                for j in idx:
+                    if not 0 <= j < stage_blocks[i]:
+                        raise ValueError('stage_with_gen_attention[%d] names block %r, stage %d of depth %d has blocks 0 .. %d: the reference would '
+                                         'build no attention block there and say nothing' % (i, j, i + 1, depth, stage_blocks[i] - 1))
+            if not any(marked):
+                # (the reference builds the plain net then and drops the dict without a word; an argument that would be disobeyed is refused)
+                raise NotImplementedError('gen_attention is given but stage_with_gen_attention marks no block: no attention block would be built; '
+                                          'mark a block or pass gen_attention=None')
+        self.gen_attention, self.stage_with_gen_attention = gen_attention, stage_with_gen_attention
         if dcn is not None:
             assert len(stage_with_dcn) == num_stages
         self.dcn, self.stage_with_dcn = dcn, stage_with_dcn
@@ -416,7 +452,6 @@ class ResNet(nn.Module, PackedMixin):
         self.depth, self.num_stages, self.strides, self.dilations = depth, num_stages, strides, dilations
         self.out_indices, self.style, self.frozen_stages, self.norm_eval = out_indices, style, frozen_stages, norm_eval
         self.zero_init_residual = zero_init_residual
-        block, stage_blocks = self.arch_settings[depth]
         self.stage_blocks = stage_blocks[:num_stages]
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64, eps=norm_cfg.get('eps', 1e-5))
@@ -427,8 +462,11 @@ class ResNet(nn.Module, PackedMixin):
             name = 'layer{}'.format(i + 1)
             stage_dcn = dcn if dcn is not None and stage_with_dcn[i] else None
             stage_gcb = gcb if gcb is not None and stage_with_gcb[i] else None
+            stage_att = tuple(stage_with_gen_attention[i]) if gen_attention is not None and i < len(stage_with_gen_attention) else ()
             self.add_module(name, make_res_layer(block, inplanes, planes, nb, stride=strides[i], dilation=dilations[i],
-                                                 style=style, norm_cfg=norm_cfg, dcn=stage_dcn, gcb=stage_gcb, **self._block_kwargs))
+                                                 style=style, norm_cfg=norm_cfg, dcn=stage_dcn, gcb=stage_gcb,
+                                                 **(dict(gen_attention=gen_attention, gen_attention_blocks=stage_att) if stage_att else {}),
+                                                 **self._block_kwargs))
             inplanes = planes * block.expansion
             self.res_layers.append(name)
         self.feat_dim = block.expansion * 64 * 2 ** (len(self.stage_blocks) - 1)
@@ -547,8 +585,10 @@ class ResNet(nn.Module, PackedMixin):
         blocks, nxt = getattr(self, self.res_layers[i]), getattr(self, self.res_layers[i + 1])[0]
         last, ds = blocks[-1], nxt.downsample
         if len(blocks) < 2 or last.downsample is not None or last.stride != 1 or last.with_dcn or last.groups > 1 \
-                or any(b.with_gcb for b in blocks):
-            return False   # (a grouped stage runs at full resolution: its compact forms are not built; a context block needs every pixel)
+                or any(b.with_gcb or b.with_gen_attention for b in blocks):
+            # (a grouped stage runs at full resolution: its compact forms are not built; a context block needs every pixel, and a generalized
+            # attention block needs conv2 at every pixel)
+            return False
         return (nxt.style == 'caffe' and nxt.conv1_stride == 2 and nxt.conv2_stride == 1 and nxt.conv1.kernel_size == (1, 1)
                 and ds is not None and ds[0].kernel_size == (1, 1) and ds[0].stride == (2, 2))
 
@@ -601,6 +641,8 @@ class ResNet(nn.Module, PackedMixin):
         """Training forward in the compute dtype (f32 = parity mode, bf16 = throughput mode with f32 master weights): the
         frozen stem and stages (`frozen_stages`, BatchNorm everywhere) run the inference kernels without a graph, the remaining stages are autograd graphs of HIP convs (Bottleneck.forward_train_nhwc).
         -> the last out_indices map, physical NHWC."""
+        if self.gen_attention is not None:
+            raise NotImplementedError('a ResNet with generalized attention blocks is inference only: the attention core has no backward')
         with torch.no_grad():
             y = self._stem(x, self.packed(x.device))
             for i, name in enumerate(self.res_layers):
@@ -696,6 +738,8 @@ class ResNeXt(ResNet):
     def __init__(self, groups=1, base_width=4, **kwargs):
         self.groups, self.base_width = groups, base_width   # (plain attributes: nn.Module takes them ahead of its own __init__)
         self._block_kwargs = dict(groups=groups, base_width=base_width) if groups != 1 else {}
+        if kwargs.get('gen_attention') is not None:
+            raise NotImplementedError('gen_attention on ResNeXt is not built: the reference\'s resnext.py accepts the argument and silently drops it')
         super(ResNeXt, self).__init__(**kwargs)
 
 

@@ -99,6 +99,11 @@ void gcb_split(int B, int P, int* S, int* chunk);
 hipError_t run_gcb_pool(const void*, const float*, float*, int, int, int, int, hipStream_t);
 hipError_t run_gcb_transform(const float*, int, int, int, int, const float* const*, const float* const*, float*, float*, hipStream_t);
 hipError_t run_gcb_apply(const void*, const float*, const float*, const void*, void*, int, int, int, int, int, hipStream_t);
+int gen_attn_query_tile();
+int gen_attn_key_block();
+int gen_attn_max_pos();
+hipError_t run_gen_attn(const void*, const void*, const void*, const float*, const void*, const void*, const float*, const float*, void*, int, int, int,
+                        int, int, int, int, int, int, hipStream_t);
 }  // namespace hvr
 
 using namespace hvr;
@@ -782,6 +787,32 @@ int hvr_gcb_apply(const void* u, const float* m, const float* t, const void* res
     if (a < b + bytes && b < a + bytes) return fail(HVR_EINVAL, "hvr_gcb_apply: y overlaps an input without being it");
   }
   return check_launch(run_gcb_apply(u, m, t, resid, y, B, P, C, relu ? 1 : 0, dtype, (hipStream_t)stream), "hvr_gcb_apply");
+}
+
+// ---- generalized attention core (gen_attn.hip)
+int hvr_gen_attn_supported(int d, int heads, int Hk, int Wk, int dtype) {
+  return (d == 16 || d == 32 || d == 64) && heads >= 1 && Hk >= 1 && Wk >= 1 && (long)Hk + Wk <= gen_attn_max_pos() && (dtype == HVR_BF16 || dtype == HVR_F16);
+}
+int hvr_gen_attn_query_tile(void) { return gen_attn_query_tile(); }
+int hvr_gen_attn_key_block(void) { return gen_attn_key_block(); }
+int hvr_gen_attn_fwd(const hvr_gen_attn_desc* d, void* stream) {
+  if (!d) return fail(HVR_EINVAL, "hvr_gen_attn_fwd: null descriptor");
+  if (d->B <= 0 || d->heads <= 0 || d->H <= 0 || d->W <= 0 || d->Hk <= 0 || d->Wk <= 0 || d->d <= 0)
+    return fail(HVR_EINVAL, "hvr_gen_attn_fwd: empty problem B=%d heads=%d d=%d H=%d W=%d Hk=%d Wk=%d", d->B, d->heads, d->d, d->H, d->W, d->Hk, d->Wk);
+  if (!hvr_gen_attn_supported(d->d, d->heads, d->Hk, d->Wk, d->dtype))
+    return fail(HVR_EUNSUPPORTED, "hvr_gen_attn_fwd: d=%d (16 / 32 / 64), Hk + Wk = %d (<= %d), dtype %d (bf16 / half)", d->d, d->Hk + d->Wk, gen_attn_max_pos(), d->dtype);
+  if ((long)d->heads * d->d > 65536 || (long)d->H * d->W > 0x7fffffffL / 4 || (long)d->Hk * d->Wk > 0x7fffffffL / 4 || d->heads > 65535 || d->B > 65535)
+    return fail(HVR_EUNSUPPORTED, "hvr_gen_attn_fwd: problem too large");
+  if (!d->v || !d->o) return fail(HVR_EINVAL, "hvr_gen_attn_fwd: v and o are required");
+  if (!d->q != !(d->qk || d->px)) return fail(HVR_EINVAL, "hvr_gen_attn_fwd: q is given exactly when the q.k term or the q.P terms are");
+  if (!d->k != !(d->qk || d->appr_bias)) return fail(HVR_EINVAL, "hvr_gen_attn_fwd: k is given exactly when the q.k term or appr_bias is");
+  if (!d->px != !d->py || !d->gx != !d->gy) return fail(HVR_EINVAL, "hvr_gen_attn_fwd: the x and y tables come in pairs");
+  if (!d->k && !d->gx && !d->px) return fail(HVR_EINVAL, "hvr_gen_attn_fwd: no energy term given");
+  const void* ptrs[9] = {d->q, d->k, d->v, d->appr_bias, d->px, d->py, d->gx, d->gy, d->o};
+  for (const void* p : ptrs)
+    if (p && !aligned16(p)) return fail(HVR_EINVAL, "hvr_gen_attn_fwd: operands must be 16-byte aligned device pointers");
+  return check_launch(run_gen_attn(d->q, d->k, d->v, d->appr_bias, d->px, d->py, d->gx, d->gy, d->o, d->B, d->heads, d->d, d->H, d->W, d->Hk, d->Wk,
+                                   d->qk ? 1 : 0, d->dtype, (hipStream_t)stream), "hvr_gen_attn_fwd");
 }
 
 int hvr_stem3x3s2_first(const float* img, const float* w, const float* bias, void* y, int B, int H, int W, int ldy, int dtype, void* stream) {

@@ -226,6 +226,9 @@ class _WindowDetector(TwoStageDetector):
         """The RoI layer of the training paths: they differentiate through RoIAlign; every other roi_layer (the deformable
         pooling packs of ops.py) is inference only."""
         from . import ops
+        if getattr(self.backbone, 'gen_attention', None) is not None:
+            # (HNMBRCNN.forward_train would run such a backbone frozen, under no_grad; the block is inference only everywhere, as stated)
+            raise NotImplementedError('a detector whose backbone holds generalized attention blocks is inference only: the attention core has no backward')
         layer = self.bbox_roi_extractor.roi_layers[0]
         if not isinstance(layer, ops.RoIAlign):
             raise NotImplementedError('training runs through RoIAlign only: roi_layer %s is inference only (it has no backward)'

@@ -91,6 +91,11 @@ class GcbMlp(ctypes.Structure):             # hvr_gcb_mlp
     _fields_ = [(n, ctypes.c_void_p) for n in ('w1', 'b1', 'gamma', 'beta', 'w2t', 'b2')]
 
 
+class GenAttnDesc(ctypes.Structure):         # hvr_gen_attn_desc
+    _fields_ = [(n, ctypes.c_void_p) for n in ('q', 'k', 'v', 'appr_bias', 'px', 'py', 'gx', 'gy', 'o')] + \
+               [(n, ctypes.c_int32) for n in ('B', 'heads', 'd', 'H', 'W', 'Hk', 'Wk', 'qk', 'dtype')]
+
+
 class TailDesc(ctypes.Structure):
     _fields_ = [('h', ctypes.c_void_p), ('x', ctypes.c_void_p), ('w', ctypes.c_void_p), ('y', ctypes.c_void_p),
                 ('B', ctypes.c_int32), ('OH', ctypes.c_int32), ('OW', ctypes.c_int32), ('C1', ctypes.c_int32),
@@ -207,6 +212,10 @@ SYMBOLS = {
     'hvr_gcb_pool': (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     'hvr_gcb_transform': (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(GcbMlp), ctypes.POINTER(GcbMlp), _vp, _vp, _vp]),
     'hvr_gcb_apply': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'hvr_gen_attn_supported': (_i, [_i, _i, _i, _i, _i]),
+    'hvr_gen_attn_query_tile': (_i, []),
+    'hvr_gen_attn_key_block': (_i, []),
+    'hvr_gen_attn_fwd': (_i, [ctypes.POINTER(GenAttnDesc), _vp]),
     'hvr_nms_workspace_bytes': (_sz, [_i]),
     'hvr_nms_first': (_i, [_vp, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'hvr_nms': (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -1808,6 +1817,111 @@ def context_block(u, packed, resid=None, relu=False, out=None):
     B, P, C = _gcb_map(u, 'context_block')
     m, t = gcb_transform(gcb_pool(u, packed.get('wm')), P, packed.get('mul'), packed.get('add'))
     return gcb_apply(u, m, t, resid, relu, out)
+
+
+# ---- generalized attention core (csrc/gen_attn.hip; the rule: include/hvr_hip.h)
+GEN_ATTN_ENERGY_CAP = 256 << 20   # bytes of f32 the composite route holds at a time in the energies and their softmax together (it works through the image rows in chunks)
+# (d, heads, H, W, Hk, Wk) at which the committed run of tools/gen_attention_bench.py shows the kernel SLOWER than the composite: the
+# automatic route says composite there
+GEN_ATTN_COMPOSITE_SHAPES = frozenset()
+
+
+def gen_attn_supported(d, heads, Hk, Wk, dtype):
+    """True when csrc/gen_attn.hip has an instance: d in (16, 32, 64), Hk + Wk <= 512, bf16 or half.  Pure (no GPU)."""
+    return dtype in (torch.bfloat16, torch.float16) and bool(lib().hvr_gen_attn_supported(int(d), int(heads), int(Hk), int(Wk), DTYPE_CODES[dtype]))
+
+
+def gen_attn_tiles():
+    """(queries per workgroup, keys per step of the online softmax) of the kernel."""
+    return int(lib().hvr_gen_attn_query_tile()), int(lib().hvr_gen_attn_key_block())
+
+
+def gen_attn_route(d, heads, H, W, Hk, Wk, dtype, channels=None, route=None):
+    """'kernel' or 'composite' for a core of this shape; route='kernel' raises where there is no instance.  channels: the width of the q / k / v
+    maps when it is not heads * d (zero-padded maps: composite)."""
+    ok = gen_attn_supported(d, heads, Hk, Wk, dtype) and (channels is None or channels == heads * d)
+    if route == 'kernel' and not ok:
+        raise HvrError('gen_attention: no kernel for d=%d heads=%d Hk+Wk=%d %s channels=%s (d in 16 / 32 / 64, Hk + Wk <= 512, bf16 / half, '
+                       'maps of heads * d channels)' % (d, heads, Hk + Wk, dtype, channels))
+    if route is not None:
+        assert route in ('kernel', 'composite'), route
+        return route
+    return 'kernel' if ok and (d, heads, H, W, Hk, Wk) not in GEN_ATTN_COMPOSITE_SHAPES else 'composite'
+
+
+def _gen_attention_composite(q, k, v, heads, d, H, W, Hk, Wk, appr_bias, px, py, gx, gy, qk, out):
+    """The reference's formulation (generalized_attention.py:240-368) in torch: energies by matmul, softmax, matmul, in f32 on the stored
+    operands, over chunks of image rows; one rounding into the map's format.  The chunk is sized so that the energies AND their softmax,
+    the two buffers of [B, heads, rows * W, Mk] f32 that are alive together, stay under GEN_ATTN_ENERGY_CAP (a single image row may
+    exceed it).  (q + appr_bias) k is ONE matmul, as in the reference; the position terms are added to it in place."""
+    B, Mk, Cq = v.shape[0], Hk * Wk, heads * d
+    f = lambda t: t.reshape(B, -1, t.shape[-1])[..., :Cq].float().view(B, -1, heads, d)   # noqa: E731
+    v4 = f(v).permute(0, 2, 1, 3)                                             # [B,h,Mk,d]
+    kT = f(k).permute(0, 2, 3, 1) if k is not None else None                 # [B,h,d,Mk]
+    q5 = f(q).view(B, H, W, heads, d).permute(0, 3, 1, 2, 4) if q is not None else None    # [B,h,H,W,d]
+    ab = appr_bias.view(1, heads, 1, 1, d) if appr_bias is not None else None
+    rows = max(1, GEN_ATTN_ENERGY_CAP // max(1, 2 * B * heads * W * Mk * 4))
+    o = out.view(B, H, W, -1)
+    for y0 in range(0, H, rows):
+        y1 = min(H, y0 + rows)
+        R = y1 - y0
+        qr = q5[:, :, y0:y1] if q5 is not None else None
+        if qk:
+            e = torch.matmul((qr + ab if ab is not None else qr).reshape(B, heads, R * W, d), kT).view(B, heads, R, W, Hk, Wk)
+        elif ab is not None:
+            e = torch.matmul(ab.reshape(1, heads, 1, d).expand(B, heads, 1, d), kT).view(B, heads, 1, 1, Hk, Wk).expand(B, heads, R, W, Hk, Wk).contiguous()
+        else:
+            e = torch.zeros((B, heads, R, W, Hk, Wk), dtype=torch.float32, device=v.device)
+        if px is not None:
+            e += torch.einsum('bhywd,hwkd->bhywk', qr, px.float()).unsqueeze(4)
+            e += torch.einsum('bhywd,hykd->bhywk', qr, py[:, y0:y1].float()).unsqueeze(5)
+        if gx is not None:
+            e += gx.view(1, heads, 1, W, 1, Wk)
+            e += gy[:, y0:y1].reshape(1, heads, R, 1, Hk, 1)
+        a = torch.softmax(e.view(B, heads, R * W, Mk), 3)
+        del e
+        o[:, y0:y1, :, :Cq] = torch.matmul(a, v4).permute(0, 2, 1, 3).reshape(B, R, W, Cq).to(out.dtype)
+    return out
+
+
+def gen_attention(q, k, v, heads, d, H, W, Hk, Wk, appr_bias=None, px=None, py=None, gx=None, gy=None, qk=True, channels=None, route=None):
+    """The attention core of a GeneralizedAttention block (the rule: include/hvr_hip.h) -> o [B, H * W, cq].  q [B, H * W, cq] or None, k and
+    v [B, Hk * Wk, cq] (k or None), contiguous physical NHWC maps of cq >= heads * d channels in bf16 / half / f32, head m in channels
+    [m d, (m + 1) d) (channels past heads * d are padding: zeros in, zeros out).  appr_bias f32 [heads * d]; px [heads,W,Wk,d] and
+    py [heads,H,Hk,d] in the maps' format; gx [heads,W,Wk] and gy [heads,H,Hk] f32.  qk: the q . k term is present.  A type whose
+    energies do not depend on the query ('0010') is called with H = W = 1 and gives the frame's one row.
+    route: None picks the kernel where csrc/gen_attn.hip has an instance (and the measured table does not send the shape to the
+    composite), 'kernel' raises where it has none, 'composite' is the reference's formulation in torch over chunks of rows."""
+    _need_cuda(q, k, v, appr_bias, px, py, gx, gy)
+    if v.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise HvrError('gen_attention: %s maps (float32 / bfloat16 / float16; split half runs the f32 form)' % v.dtype)
+    B, cq = v.shape[0], v.shape[-1]
+    Cq = heads * d if channels is None else channels
+    P, Mk = H * W, Hk * Wk
+    if Cq != heads * d or cq < Cq:
+        raise HvrError('gen_attention: %d heads of %d channels in maps of %d (%s logical)' % (heads, d, cq, channels))
+    if (q is None) != (not (qk or px is not None)) or (k is None) != (not (qk or appr_bias is not None)):
+        raise HvrError('gen_attention: q is given exactly when the q.k or q.P terms are, k exactly when the q.k term or appr_bias is')
+    if (px is None) != (py is None) or (gx is None) != (gy is None) or (k is None and gx is None and px is None):
+        raise HvrError('gen_attention: the position tables come in pairs, and at least one energy term is needed')
+    for t, n, what in ((q, P, 'q'), (k, Mk, 'k'), (v, Mk, 'v')):
+        if t is not None and (t.dtype != v.dtype or t.numel() != B * n * cq or not t.is_contiguous()):
+            raise HvrError('gen_attention: %s is %s %s, expected a contiguous %s map of %d x %d x %d' % (what, t.dtype, tuple(t.shape), v.dtype, B, n, cq))
+    for t, shape, dt, what in ((appr_bias, (Cq,), torch.float32, 'appr_bias'), (px, (heads, W, Wk, d), v.dtype, 'px'), (py, (heads, H, Hk, d), v.dtype, 'py'),
+                               (gx, (heads, W, Wk), torch.float32, 'gx'), (gy, (heads, H, Hk), torch.float32, 'gy')):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise HvrError('gen_attention: %s is %s %s, expected contiguous %s %s' % (what, t.dtype, tuple(t.shape), dt, shape))
+    which = gen_attn_route(d, heads, H, W, Hk, Wk, v.dtype, cq, route)
+    if which == 'composite':
+        out = torch.zeros((B, P, cq), dtype=v.dtype, device=v.device) if cq != Cq else torch.empty((B, P, cq), dtype=v.dtype, device=v.device)
+        with _span('gen_attention_composite', 4.0 * B * heads * P * Mk * d):
+            return _gen_attention_composite(q, k, v, heads, d, H, W, Hk, Wk, appr_bias, px, py, gx, gy, qk, out)
+    out = torch.empty((B, P, cq), dtype=v.dtype, device=v.device)
+    desc = _point(GenAttnDesc(B=B, heads=heads, d=d, H=H, W=W, Hk=Hk, Wk=Wk, qk=int(bool(qk)), dtype=_dt(v)),
+                  q=q, k=k, v=v, appr_bias=appr_bias, px=px, py=py, gx=gx, gy=gy, o=out)
+    with _span('gen_attention', 4.0 * B * heads * P * Mk * d):
+        _check(lib().hvr_gen_attn_fwd(ctypes.byref(desc), _stream()), 'hvr_gen_attn_fwd')
+    return out
 
 
 def nms_first(dets, iou_thr, max_keep, ge_semantics=True):

@@ -360,6 +360,174 @@ class ContextBlock(nn.Module, PackedMixin):
         return as_logical(self.forward_nhwc(as_nhwc(x, self.compute_dtype)))   # (in the compute format, as Bottleneck.forward)
 
 
+class GeneralizedAttention(nn.Module, PackedMixin):
+    """mmdet/models/plugins/generalized_attention.py:10-383, the block of 'An Empirical Study of Spatial Attention Mechanisms in Deep
+    Networks': the reference's constructor arguments, parameter names, shapes, registration order and initialisation, so checkpoints load
+    strictly.  GPU forward only, inference only.  The three projections and the closing conv are native.conv2d_nhwc calls (the key / value
+    subsampling x[:, :, ::s, ::s] is the stride of a 1x1 conv; gamma is folded into proj_conv at pack time, the residual rides on its
+    epilogue); the attention core is native.gen_attention (csrc/gen_attn.hip, or the torch composite where the kernel has no instance).
+    The position tables depend on the weights and on (H, W) only: they are built in f64 on first use and cached per device, compute
+    format and (H, W) until the packed weights are dropped -- a new frame size builds new tables, so warm up before a graph capture.
+    Refused: spatial_range >= 0 and q_stride > 1 (the reference cannot build or run them) and the four attention types with bit 1 set
+    and bit 3 clear (the reference multiplies Py with the TRANSPOSED query map there: generalized_attention.py:308-326)."""
+    core_route = None   # the attention core: None = native.gen_attention chooses by shape; 'kernel' / 'composite' force one (tests, tools)
+
+    def __init__(self, in_dim, spatial_range=-1, num_heads=9, position_embedding_dim=-1, position_magnitude=1, kv_stride=2, q_stride=1,
+                 attention_type='1111'):
+        super(GeneralizedAttention, self).__init__()
+        bits = [bool(int(c)) for c in attention_type]
+        if len(bits) != 4 or not any(bits):
+            raise ValueError('attention_type is four binary digits with at least one set, got %r' % (attention_type,))
+        if bits[1] and not bits[3]:
+            raise NotImplementedError('attention_type %r (query content x relative position without the geometry bias) does not compute in the '
+                                      'reference: it raises for H != W and multiplies Py with the transposed query map for H == W '
+                                      '(generalized_attention.py:308-326); there is nothing to reproduce' % (attention_type,))
+        if q_stride != 1:
+            raise NotImplementedError('q_stride > 1 raises in the reference (the residual add cannot broadcast): not built')
+        if spatial_range >= 0:
+            raise NotImplementedError('spatial_range >= 0 (the local constraint map) is not built: only -1, attention over every key')
+        if kv_stride < 1 or num_heads < 1 or in_dim // num_heads < 1:
+            raise ValueError('kv_stride >= 1, num_heads >= 1 and in_dim // num_heads >= 1 are required')
+        self.position_embedding_dim = position_embedding_dim if position_embedding_dim > 0 else in_dim
+        self.position_magnitude, self.num_heads, self.channel_in, self.spatial_range = position_magnitude, num_heads, in_dim, spatial_range
+        self.kv_stride, self.q_stride, self.attention_type = kv_stride, q_stride, bits
+        self.qk_embed_dim = self.v_dim = in_dim // num_heads
+        out_c = self.qk_embed_dim * num_heads
+        if bits[0] or bits[1]:
+            self.query_conv = nn.Conv2d(in_dim, out_c, kernel_size=1, bias=False)
+        if bits[0] or bits[2]:
+            self.key_conv = nn.Conv2d(in_dim, out_c, kernel_size=1, bias=False)
+        self.value_conv = nn.Conv2d(in_dim, out_c, kernel_size=1, bias=False)
+        if bits[1] or bits[3]:
+            if len(np.arange(0, self.position_embedding_dim / 4)) * 2 != self.position_embedding_dim // 2:
+                raise ValueError('position_embedding_dim=%d: the embedding has %d entries, the fc %d inputs (a multiple of 4 is needed)'
+                                 % (self.position_embedding_dim, len(np.arange(0, self.position_embedding_dim / 4)) * 2, self.position_embedding_dim // 2))
+            self.appr_geom_fc_x = nn.Linear(self.position_embedding_dim // 2, out_c, bias=False)
+            self.appr_geom_fc_y = nn.Linear(self.position_embedding_dim // 2, out_c, bias=False)
+        stdv = 1.0 / np.sqrt(self.qk_embed_dim * 2)
+        if bits[2]:
+            self.appr_bias = nn.Parameter(-2 * stdv * torch.rand(out_c) + stdv)
+        if bits[3]:
+            self.geom_bias = nn.Parameter(-2 * stdv * torch.rand(out_c) + stdv)
+        self.proj_conv = nn.Conv2d(out_c, in_dim, kernel_size=1, bias=True)
+        self.gamma = nn.Parameter(torch.zeros(1))
+        self.init_weights()
+        self._tables = {}
+        self._init_packed()
+
+    def init_weights(self):
+        """generalized_attention.py:374-383: kaiming-uniform with a = 1 on fan_in (|w| <= sqrt(3 / fan_in)) for every conv and fc, zero bias."""
+        for m in self.modules():
+            if isinstance(m, (nn.Conv2d, nn.Linear)):
+                nn.init.kaiming_uniform_(m.weight, a=1, mode='fan_in', nonlinearity='leaky_relu')
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+
+    def _drop_packed(self):
+        super(GeneralizedAttention, self)._drop_packed()
+        self._tables = {}
+
+    @staticmethod
+    def _device_dtype(dtype):
+        return torch.float32 if dtype == native.SPLIT else dtype   # split half runs the f32 form, cast in and out (as the context block)
+
+    def _pack(self, dtype):
+        """The projections with zero rows / columns up to the conv entries' channel multiples (cin: in_dim, cq: heads * d), gamma folded
+        into proj_conv's weight and bias, appr_bias in f32."""
+        dt = self._device_dtype(dtype)
+        mult = 64 if dt in (torch.bfloat16, torch.float16) else 32
+        C, Cq = self.channel_in, self.qk_embed_dim * self.num_heads
+        cin, cq = -(-C // mult) * mult, -(-Cq // mult) * mult
+        dev = self.value_conv.weight.device
+
+        def proj(conv):
+            w = torch.zeros((cq, 1, 1, cin), dtype=torch.float32, device=dev)
+            w[:Cq, 0, 0, :C] = conv.weight.detach().float().reshape(Cq, C)
+            return w.to(dt).contiguous()
+        p = dict(cin=cin, cq=cq, v=proj(self.value_conv))
+        if hasattr(self, 'query_conv'):
+            p['q'] = proj(self.query_conv)
+        if hasattr(self, 'key_conv'):
+            p['k'] = proj(self.key_conv)
+        g = self.gamma.detach().double().reshape(())
+        wo = torch.zeros((C, 1, 1, cq), dtype=torch.float64, device=dev)
+        wo[:, 0, 0, :Cq] = self.proj_conv.weight.detach().double().reshape(C, Cq) * g
+        p['o'] = (wo.float().to(dt).contiguous(), (self.proj_conv.bias.detach().double() * g).float().contiguous())
+        if self.attention_type[2]:
+            p['ab'] = self.appr_bias.detach().float().contiguous()
+        return p
+
+    def position_tables(self, H, W, device, dtype=None):
+        """dict(px [heads,W,Wk,d], py [heads,H,Hk,d] in the compute format; gx [heads,W,Wk], gy [heads,H,Hk] f32 = geom_bias . Px / Py) for an
+        [H, W] map -- built in f64 (generalized_attention.py:152-194,226-238), cached.  px / py only for a type with bit 1, gx / gy with bit 3."""
+        dt = self._device_dtype(self.compute_dtype if dtype is None else dtype)
+        key = (str(device), dt, int(H), int(W))
+        if key not in self._tables:
+            s, heads, d = self.kv_stride, self.num_heads, self.qk_embed_dim
+            F = self.position_embedding_dim
+            omega = 1000.0 ** ((4.0 / F) * np.arange(0, F / 4, dtype=np.float64))
+            t = {}
+            for axis, n, fc in (('x', W, self.appr_geom_fc_x), ('y', H, self.appr_geom_fc_y)):
+                nk = (n - 1) // s + 1
+                diff = (np.arange(n, dtype=np.float64)[:, None] - s * np.arange(nk, dtype=np.float64)[None, :]) * self.position_magnitude
+                ang = diff[:, :, None] / omega
+                emb = np.concatenate([np.sin(ang), np.cos(ang)], axis=2)                        # [n, nk, F / 2]
+                tab = (emb @ fc.weight.detach().double().cpu().numpy().T) / np.sqrt(2.0)        # [n, nk, heads * d]
+                tab = tab.reshape(n, nk, heads, d).transpose(2, 0, 1, 3)                        # [heads, n, nk, d]
+                if self.attention_type[1]:
+                    t['p' + axis] = torch.from_numpy(np.ascontiguousarray(tab)).float().to(device).to(dt).contiguous()
+                if self.attention_type[3]:
+                    gb = self.geom_bias.detach().double().cpu().numpy().reshape(heads, 1, 1, d)
+                    t['g' + axis] = torch.from_numpy(np.ascontiguousarray((tab * gb).sum(3))).float().to(device).contiguous()
+            self._tables[key] = t
+        return self._tables[key]
+
+    def forward_nhwc(self, h, out=None):
+        """h [B,H,W,in_dim] physical NHWC in a compute format -> gamma * proj_conv(attention(h)) + h; out: where it goes (like h)."""
+        native._need_cuda(h)
+        if h.dtype == native.SPLIT:
+            y = native.cast(self._forward_dev(native.cast(h, torch.float32), None), native.SPLIT)
+            if out is not None:
+                out.copy_(y)
+                return out
+            return y
+        return self._forward_dev(h, out)
+
+    def _forward_dev(self, h, out):
+        p = self.packed(h.device)
+        B, H, W, C = h.shape
+        t0, t1, t2, t3 = self.attention_type
+        s, heads, d = self.kv_stride, self.num_heads, self.qk_embed_dim
+        Cq, cq = heads * d, p['cq']
+        x = h
+        if p['cin'] != C:   # (an in_dim the conv entries do not take: zero channels up to their multiple, against zero weight columns)
+            x = torch.zeros((B, H, W, p['cin']), dtype=h.dtype, device=h.device)
+            x[..., :C] = h
+        Hk, Wk = (H - 1) // s + 1, (W - 1) // s + 1
+        q = native.conv2d_nhwc(x, p['q']) if (t0 or t1) else None
+        k = native.conv2d_nhwc(x, p['k'], stride=s) if (t0 or t2) else None
+        v = native.conv2d_nhwc(x, p['v'], stride=s)
+        tabs = self.position_tables(H, W, h.device, h.dtype) if (t1 or t3) else {}
+        one_row = not (t0 or t1 or t3)   # '0010': the energies do not depend on the query, every pixel of a frame gets the same row
+        qh, qw = (1, 1) if one_row else (H, W)
+        o = native.gen_attention(q, k, v, heads, d, qh, qw, Hk, Wk, appr_bias=p.get('ab'), px=tabs.get('px'), py=tabs.get('py'), gx=tabs.get('gx'),
+                                 gy=tabs.get('gy'), qk=t0, channels=Cq, route=self.core_route)          # [B, qh * qw, cq]
+        wo, bo = p['o']
+        if not one_row:
+            return native.conv2d_nhwc(o.view(B, H, W, cq), wo, bo, resid=h, relu=False, out=out)
+        if native.gcb_supported(C, h.dtype):
+            # the frame's one row through proj_conv in f32, then y = h + r[n, c]: the context block's apply with m absent
+            r = native.conv2d_nhwc(o.view(B, 1, 1, cq), wo, bo, relu=False, out_f32=True).view(B, C)
+            return native.gcb_apply(h, None, r, None, False, out)
+        return native.conv2d_nhwc(o.view(B, 1, 1, cq).expand(B, H, W, cq).contiguous(), wo, bo, resid=h, relu=False, out=out)
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise NotImplementedError('GeneralizedAttention runs on the GPU only (no CPU fallback)')
+        from .backbone import as_logical, as_nhwc
+        return as_logical(self.forward_nhwc(as_nhwc(x, self.compute_dtype)))   # (in the compute format, as Bottleneck.forward)
+
+
 class RelationFunction(Function):
     """o = softmax(scale * q k^T) v with a HIP backward (the reference differentiates torch.bmm / nn.Softmax / torch.mm,
     selsa_bbox_head.py:166-182, through autograd).  Backward = one score pass (probabilities recomputed, not stored),

@@ -67,7 +67,37 @@ def _gcb(g, sd, prefix, c, ratio, pooling_type='att', fusion_types=('channel_add
             sd[q + '.3.bias'] = torch.randn(c, generator=g) * 0.05
 
 
-def _res_layer(g, sd, prefix, inplanes, planes, blocks, groups=1, base_width=4, gcb=None):
+def _gen_attention(g, sd, prefix, c, num_heads=9, position_embedding_dim=-1, attention_type='1111', **_shape_free):
+    """Keys of a GeneralizedAttention block (generalized_attention.py:60-109) in the reference's order.  The reference starts gamma at 0,
+    which makes a fresh block the identity: here gamma, the biases and proj_conv's bias get values, so that the block shows in the output.
+    The projections are scaled so that the energies of a unit-scale map spread over a few units (peaky rows, not one-hot)."""
+    t = [bool(int(b)) for b in attention_type]
+    d = c // num_heads
+    oc, f = d * num_heads, (position_embedding_dim if position_embedding_dim > 0 else c) // 2
+
+    def u(shape, fan_in, gain=1.0):   # kaiming-uniform, a = 1
+        return (torch.rand(shape, generator=g) * 2.0 - 1.0) * (gain * math.sqrt(3.0 / fan_in))
+    if t[0] or t[1]:
+        sd[prefix + '.query_conv.weight'] = u((oc, c, 1, 1), c, 1.5)
+    if t[0] or t[2]:
+        sd[prefix + '.key_conv.weight'] = u((oc, c, 1, 1), c, 1.5)
+    sd[prefix + '.value_conv.weight'] = u((oc, c, 1, 1), c)
+    if t[1] or t[3]:
+        sd[prefix + '.appr_geom_fc_x.weight'] = u((oc, f), f)
+        sd[prefix + '.appr_geom_fc_y.weight'] = u((oc, f), f)
+    sd[prefix + '.proj_conv.weight'] = u((c, oc, 1, 1), oc)
+    sd[prefix + '.proj_conv.bias'] = torch.randn(c, generator=g) * 0.05
+    sd[prefix + '.gamma'] = torch.rand(1, generator=g) * 0.5 + 0.5
+    # (parameters registered with nn.Parameter come first in a state dict, the sub-modules' behind them: state_dict() order is not asserted
+    # by load_state_dict, the key SET is)
+    stdv = 1.0 / math.sqrt(2 * d)
+    if t[2]:
+        sd[prefix + '.appr_bias'] = (torch.rand(oc, generator=g) * 2.0 - 1.0) * stdv
+    if t[3]:
+        sd[prefix + '.geom_bias'] = (torch.rand(oc, generator=g) * 2.0 - 1.0) * stdv
+
+
+def _res_layer(g, sd, prefix, inplanes, planes, blocks, groups=1, base_width=4, gcb=None, gen_attention=None, gen_attention_blocks=()):
     width = planes if groups == 1 else int(math.floor(planes * (base_width / 64))) * groups   # resnext.py:21-24
     for i in range(blocks):
         p = '%s.%d' % (prefix, i)
@@ -84,6 +114,8 @@ def _res_layer(g, sd, prefix, inplanes, planes, blocks, groups=1, base_width=4, 
             _bn(g, sd, p + '.downsample.1', planes * 4)
         if gcb is not None:
             _gcb(g, sd, p + '.context_block', planes * 4, **gcb)
+        if gen_attention is not None and i in gen_attention_blocks:
+            _gen_attention(g, sd, p + '.gen_attention_block', planes, **gen_attention)
 
 
 def _res2_layer(g, sd, prefix, inplanes, planes, blocks, base_width=26, scale=4):
@@ -113,13 +145,16 @@ def _linear(g, sd, prefix, cout, cin, gain, conv=False):
 
 
 def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024, roi_feat=256 * 49, groups=1, base_width=4, arch='resnet',
-                     gcb=None, stage_with_gcb=(False, True, True)):
+                     gcb=None, stage_with_gcb=(False, True, True), gen_attention=None, stage_with_gen_attention=((), (), ())):
     """Full detector state dict (f32, CPU) with the reference's key names.  groups / base_width: a ResNeXt backbone + ResXLayer.
     arch='res2net': a Res2Net backbone (101 layers, 26w x 4s, deep stem) + Res2Layer; the heads' keys are the same.
     gcb: dict(ratio=..., pooling_type=..., fusion_types=...) adds the context-block keys to the backbone stages marked in stage_with_gcb
-    (ResNet / ResNeXt), with non-zero last convs; None (the default) leaves every key and value as before."""
+    (ResNet / ResNeXt), with non-zero last convs; None (the default) leaves every key and value as before.
+    gen_attention: the dict ResNet takes adds the keys of a generalized attention block to the blocks stage_with_gen_attention names per
+    stage (ResNet), with non-zero gamma and biases; None (the default) leaves every key and value as before."""
     assert arch in ('resnet', 'res2net'), arch
     assert gcb is None or arch == 'resnet', 'Res2Net takes no context blocks'
+    assert gen_attention is None or (arch == 'resnet' and groups == 1), 'only ResNet takes generalized attention blocks'
     g = torch.Generator().manual_seed(seed)
     sd = {}
     blocks = STAGE_BLOCKS[depth]
@@ -141,7 +176,8 @@ def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024,
         inplanes = 64
         for i in range(3):
             _res_layer(g, sd, 'backbone.layer%d' % (i + 1), inplanes, 64 * 2 ** i, blocks[i], groups, base_width,
-                       gcb if gcb is not None and stage_with_gcb[i] else None)
+                       gcb if gcb is not None and stage_with_gcb[i] else None, gen_attention,
+                       tuple(stage_with_gen_attention[i]) if gen_attention is not None and i < len(stage_with_gen_attention) else ())
             inplanes = 64 * 2 ** i * 4
         _res_layer(g, sd, 'shared_head.layer4', 1024, 512, blocks[3], groups, base_width)
     sd['shared_head.new_layer_1.conv.weight'] = _conv(g, 256, 2048, 1) * NEW_LAYER_GAIN

@@ -269,6 +269,38 @@ int hvr_gcb_transform(const void* ws, size_t ws_bytes, int B, int P, int C, int 
 int hvr_gcb_apply(const void* u, const float* m, const float* t, const void* resid, void* y, int B, int P, int C, int relu, int dtype,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Generalized (empirical) attention core, forward only.  Replaces the energy, softmax and weighted sum of
+ * mmdet/models/plugins/generalized_attention.py:240-368 (spatial_range = -1, q_stride = 1); the projections in front and the closing
+ * conv behind it are hvr_conv2d_nhwc calls.  q [B][H*W][heads*d], k and v [B][Hk*Wk][heads*d] are physical NHWC maps in `dtype` =
+ * HVR_BF16 / HVR_F16, head m in channels [m*d, (m+1)*d); d in {16, 32, 64}, heads >= 1, Hk + Wk <= 512 (hvr_gen_attn_supported
+ * answers 1 / 0; anything else is refused, the caller's other route is torch).  The rule, per frame n, head m, query pixel
+ * p = (y, x) and key j = (yk, xk) = (j / Wk, j % Wk):
+ *   E[p][j] = [qk] q[p] . k[j]  +  [appr_bias] appr_bias_m . k[j]
+ *             + [px] q[p] . px[m][x][xk]  +  [gx] gx[m][x][xk]  +  [py] q[p] . py[m][y][yk]  +  [gy] gy[m][y][yk]
+ *   A[p][.] = softmax_j E[p][.]          o[p] = sum_j A[p][j] v[j]                          (no 1 / sqrt(d) scale)
+ * px [heads][W][Wk][d] and py [heads][H][Hk][d] are in `dtype`; appr_bias [heads*d], gx [heads][W][Wk] and gy [heads][H][Hk] are f32
+ * (gx = geom_bias . Px and so on: the caller folds what does not depend on the frame).  A NULL pointer drops its term; q is given
+ * exactly when qk or px / py are, k exactly when qk or appr_bias is.  q, k, v, px, py are read as stored; every product is accumulated
+ * in f32 (the q . k and A v sums on the MFMA, the others as FMAs), the energies, the running maximum and the exp are f32.  The
+ * probabilities exp(E - max) are rounded ONCE into `dtype` as the MFMA operand, and the normaliser sums those ROUNDED values in f32,
+ * so a v that is constant over the keys comes back as itself; o = acc / sum is rounded ONCE into `dtype`.  The keys are taken
+ * hvr_gen_attn_key_block() at a time with an online softmax (running maximum, running sum, accumulator rescaled by
+ * exp(max_old - max_new)); a workgroup owns hvr_gen_attn_query_tile() consecutive pixels, which may span image rows.  E and A never
+ * exist in memory.  No float atomics, a fixed order of operations: two runs of a call give the same bits.  No workspace, no host
+ * synchronisation, no allocation.
+ * ---------------------------------------------------------------------------------- */
+typedef struct hvr_gen_attn_desc {
+  const void* q; const void* k; const void* v; const float* appr_bias;
+  const void* px; const void* py; const float* gx; const float* gy;
+  void* o;
+  int32_t B, heads, d, H, W, Hk, Wk, qk, dtype;
+} hvr_gen_attn_desc;
+int hvr_gen_attn_supported(int d, int heads, int Hk, int Wk, int dtype);
+int hvr_gen_attn_query_tile(void);
+int hvr_gen_attn_key_block(void);
+int hvr_gen_attn_fwd(const hvr_gen_attn_desc* d, void* stream);
+
 /* First conv of Res2Net's deep stem (res2net_v1b.py:174-177: Conv 3 -> 32, 3x3, stride 2, pad 1 + frozen BN + ReLU) read from the
  * f32 NCHW image img [B][3][H][W]: w f32 [32][3][3][3] as [n][ky][kx][c] and bias f32 [32] with the BN folded in; y [B][OH][OW][ldy]
  * NHWC in `dtype` (HVR_F32, HVR_BF16 or HVR_F16), OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1.  f32 FMAs, one rounding.  ldy >= 32,
