@@ -82,6 +82,7 @@ hipError_t run_rpn_gather(const float*, const long long*, const int*, int, int, 
 hipError_t run_multiclass_nms(const float*, const float*, int, int, float, float, int, float*, long long*, int*, void*,
                               hipStream_t);
 size_t multiclass_nms_workspace_bytes(int R, int ncls);
+int multiclass_nms_max_candidates();
 hipError_t run_soft_nms(const float*, int, float, int, float, float, float*, long long*, int*, hipStream_t);
 hipError_t run_multiclass_soft_nms(const float*, const float*, int, int, int, float, float, int, float, float, int, float*, long long*, int*,
                                    void*, hipStream_t);
@@ -1658,6 +1659,10 @@ int hvr_rpn_wide_frames(int frames) { return rpn_wide_max_frames(frames); }
 
 int hvr_rpn_proposals(const hvr_rpn_desc* d, void* ws, size_t ws_bytes, void* stream) {
   if (!d || !ws) return fail(HVR_EINVAL, "null pointer");
+  if (d->T <= 0) return fail(HVR_EINVAL, "hvr_rpn_proposals needs T >= 1 frames, got %d", d->T);
+  if (d->A <= 0) return fail(HVR_EINVAL, "hvr_rpn_proposals needs A >= 1 base anchors, got %d", d->A);
+  if (d->nms_post <= 0) return fail(HVR_EINVAL, "hvr_rpn_proposals needs nms_post > 0");
+  if (d->max_num <= 0) return fail(HVR_EINVAL, "hvr_rpn_proposals needs max_num > 0");
   if (d->A > 32) return fail(HVR_EUNSUPPORTED, "at most 32 base anchors");
   const long n_anchor = (long)d->H * d->W * d->A;
   const int npre = rpn_npre(d->H, d->W, d->A, d->nms_pre);
@@ -1719,8 +1724,13 @@ int hvr_multiclass_nms(const float* boxes, const float* scores, int R, int ncls,
     (void)run_zero_fill(n_out, sizeof(int32_t), (hipStream_t)stream);
     return HVR_OK;
   }
+  if (R < 0 || R > 512) return fail(HVR_EUNSUPPORTED, "hvr_multiclass_nms supports R <= 512, got %d", R);
+  if (ncls < 2 || ncls - 1 > 128) return fail(HVR_EUNSUPPORTED, "hvr_multiclass_nms supports 1 .. 128 foreground classes");
+  if (max_num <= 0) return fail(HVR_EINVAL, "hvr_multiclass_nms needs max_num > 0");
+  if ((long)(ncls - 1) * R > multiclass_nms_max_candidates())
+    return fail(HVR_EUNSUPPORTED, "hvr_multiclass_nms supports (ncls - 1) * R <= %d candidates (the merge kernel's list in LDS), got %ld",
+                multiclass_nms_max_candidates(), (long)(ncls - 1) * R);
   if (!boxes || !scores || !dets || !labels || !ws) return fail(HVR_EINVAL, "null pointer");
-  if (R > 512) return fail(HVR_EUNSUPPORTED, "hvr_multiclass_nms supports R <= 512, got %d", R);
   if (ws_bytes < hvr_multiclass_nms_workspace_bytes(R, ncls)) return fail(HVR_EWORKSPACE, "multiclass nms workspace too small");
   return check_launch(run_multiclass_nms(boxes, scores, R, ncls, score_thr, iou_thr, max_num, dets, (long long*)labels, n_out,
                                          ws, (hipStream_t)stream),

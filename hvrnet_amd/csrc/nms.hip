@@ -8,7 +8,9 @@
 //   * multi-class NMS of the RCNN head <- mmdet/core/post_processing/bbox_nms.py:6-66
 //
 // Integer / index work: bit-exact against the CPU reference semantics.  Tie rule (unspecified in the
-// reference, which relies on torch.sort/topk): higher score first, then lower index.
+// reference, which relies on torch.sort/topk): higher score first, then lower index.  "Higher" is float_key's order of the bit
+// patterns: it agrees with the float order except that -0.0 sorts AFTER +0.0 (the two compare equal as floats); scores are
+// sigmoids / softmax outputs, never a negative zero, and tests/nms_refs.py keeps the pair out of its tie families.
 #include <cstdlib>
 #include <atomic>
 #include "common.h"
@@ -1282,9 +1284,19 @@ hipError_t run_rpn_gather(const float* props, const long long* keep, const int* 
   return hipGetLastError();
 }
 
+// The merge kernel keeps the whole candidate list, next_pow2((ncls - 1) * R) entries of 8 bytes, in LDS: the longest list it can hold.
+// One statement of the limit for the launcher, the workspace query and the entry point's refusal (capi.hip).
+constexpr size_t MC_MERGE_LDS_CAP = 160 * 1024 - 3072;
+int multiclass_nms_max_candidates() {
+  int p = 1;
+  while ((size_t)p * 2 * 8 <= MC_MERGE_LDS_CAP) p <<= 1;
+  return p;   // 16384: 30 classes x 512 rows fit, 128 x 512 do not
+}
+
 hipError_t run_multiclass_nms(const float* boxes, const float* scores, int R, int ncls, float score_thr, float iou_thr,
                               int max_num, float* dets, long long* labels, int* n_out, void* ws, hipStream_t s) {
-  if (R > MC_MAX_R || ncls - 1 > 128 || R <= 0) return hipErrorInvalidValue;
+  if (R > MC_MAX_R || ncls < 2 || ncls - 1 > 128 || R <= 0 || max_num <= 0) return hipErrorInvalidValue;
+  if ((long)(ncls - 1) * R > multiclass_nms_max_candidates()) return hipErrorInvalidValue;   // (before anything is launched)
   unsigned char* keepflag = (unsigned char*)ws;
   int* kcount = (int*)((char*)ws + (((size_t)(ncls - 1) * R + 255) & ~(size_t)255));
   hipLaunchKernelGGL(mc_nms_class_kernel, dim3(ncls - 1), dim3(1024), 0, s, boxes, scores, R, ncls, score_thr, iou_thr, keepflag, kcount);
@@ -1295,18 +1307,19 @@ hipError_t run_multiclass_nms(const float* boxes, const float* scores, int R, in
   // never run (max_num >= every possible survivor count) the kernel sorts the survivor list in place instead (sp2 = 0)
   int sp2 = 1;
   while (sp2 < max_num) sp2 <<= 1;
-  if (max_num >= (ncls - 1) * R || (size_t)np2 * 8 + (size_t)sp2 * 8 > 160 * 1024 - 3072) sp2 = 0;
+  if (max_num >= (ncls - 1) * R || (size_t)np2 * 8 + (size_t)sp2 * 8 > MC_MERGE_LDS_CAP) sp2 = 0;
   const size_t lds = (size_t)np2 * 8 + (size_t)sp2 * 8;
-  if (lds > 160 * 1024 - 3072) return hipErrorInvalidValue;
   static std::atomic<unsigned> attr_dev{0};   // (the attribute is per device)
   per_device_once(attr_dev, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mc_nms_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 3072);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mc_nms_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MC_MERGE_LDS_CAP);
   });
   hipLaunchKernelGGL(mc_nms_merge_kernel, dim3(1), dim3(1024), lds, s, boxes, scores, R, ncls, keepflag, kcount, max_num, sp2, dets, labels, n_out);
   return hipGetLastError();
 }
 
+// 0 for a shape outside the envelope (R in 1 .. 512, 1 .. 128 foreground classes, a candidate list the merge kernel holds)
 size_t multiclass_nms_workspace_bytes(int R, int ncls) {
+  if (R <= 0 || R > MC_MAX_R || ncls < 2 || ncls - 1 > 128 || (long)(ncls - 1) * R > multiclass_nms_max_candidates()) return 0;
   return (((size_t)(ncls - 1) * R + 255) & ~(size_t)255) + (size_t)(ncls - 1) * sizeof(int) + 256;
 }
 

@@ -614,6 +614,7 @@ int hvr_nms_first(const float* dets, int n, float thr, int ge_semantics, int max
  *   cls [T][H][W][A] f32 logits, reg [T][H][W][A*4] f32 (NHWC conv outputs),
  *   base_anchors host [A][4] f32, means/stds host [4] f32.
  *   proposals [T][max_num][5] f32, counts [T] int32 (rows beyond counts[t] are untouched).
+ * T >= 1, A >= 1, nms_post > 0 and max_num > 0 (else HVR_EINVAL, nothing launched); nms_pre <= 0 means no top-k.
  * ---------------------------------------------------------------------------------- */
 typedef struct hvr_rpn_desc {
   const float* cls; const float* reg;
@@ -642,7 +643,11 @@ int hvr_rpn_wide_frames(int frames);
  * logits [R][ldl] f32 with class logits at cls_off.. and 4 deltas at reg_off..;
  * rois [R][5]; scores [R][ncls]; boxes [R][4]; dets [max_num][5]; labels [max_num] int64
  * (0-based foreground class); *n_out device int32; rows [*n_out, max_num) of dets / labels come back zeroed (R > 0:
- * the caller's buffers need no initialisation).  R <= 512.
+ * the caller's buffers need no initialisation).
+ * hvr_multiclass_nms: max_num > 0 (else HVR_EINVAL); R <= 512, 1 .. 128 foreground classes (ncls - 1) and
+ * (ncls - 1) * R <= 16384 -- the merge keeps the whole candidate list, next_pow2((ncls - 1) * R) entries of 8 bytes, in LDS;
+ * 30 classes x 512 rows fit, 128 x 512 do not -- (else HVR_EUNSUPPORTED); nothing is launched and nothing written on an error.
+ * hvr_multiclass_nms_workspace_bytes returns 0 for a shape outside that envelope.  R == 0 writes only the count (zero).
  * scale_factor <= 0 means rescale=False.  img_w <= 0 means no clipping.
  * ---------------------------------------------------------------------------------- */
 int hvr_det_decode(const float* logits, int ldl, int cls_off, int reg_off, int ncls, const float* rois, int R,
