@@ -136,7 +136,7 @@ def enable_training(module):
             p.requires_grad = True
     for m in module.modules():
         if isinstance(m, ResNet):
-            frozen = [m.conv1, m.bn1] + [getattr(m, 'layer%d' % i) for i in range(1, m.frozen_stages + 1)]
+            frozen = [m.conv1, m.norm1] + [getattr(m, 'layer%d' % i) for i in range(1, m.frozen_stages + 1)]
             for f in frozen:
                 for p in f.parameters():
                     p.requires_grad = False
@@ -152,10 +152,46 @@ def enable_training(module):
     return module
 
 
+GN_GROUP_WIDTHS = (2, 4, 8, 16, 32, 64)   # channels per group the group-norm kernels take (include/hvr_hip.h: hvr_gn_supported)
+
+
+def norm_kind(norm_cfg, what):
+    """norm_cfg -> ('BN', None, eps) or ('GN', num_groups, eps), as build_norm_layer reads it (norm.py:12-55); every other type is refused."""
+    cfg = norm_cfg if norm_cfg is not None else dict(type='BN')
+    kind = cfg.get('type', 'BN')
+    if kind == 'BN':
+        return 'BN', None, cfg.get('eps', 1e-5)
+    if kind != 'GN':
+        raise NotImplementedError('%s: norm_cfg type %r is not built (frozen BatchNorm \'BN\' and GroupNorm \'GN\' are)' % (what, kind))
+    assert 'num_groups' in cfg, '%s: norm_cfg type GN needs num_groups' % what
+    return 'GN', int(cfg['num_groups']), cfg.get('eps', 1e-5)
+
+
+def gn_padded(C, G, what):
+    """(channels, groups) of the map the group-norm kernels run for a GroupNorm(G, C): C rounded up to a multiple of 64 with whole groups of
+    exact zeros behind the real ones (weight rows, gamma and beta 0: such a group normalises to exact zeros), or NotImplementedError where
+    the instance set of include/hvr_hip.h has no such form."""
+    if G < 1 or C % G or C // G not in GN_GROUP_WIDTHS or C > 2048:
+        raise NotImplementedError('%s: GroupNorm with num_groups=%d on %d channels is outside the kernels\' instance set (num_groups divides the '
+                                  'channels, channels per group in %s, up to 2048 channels)' % (what, G, C, list(GN_GROUP_WIDTHS)))
+    Cp = (C + 63) // 64 * 64
+    return Cp, Cp // (C // G)
+
+
+def _pad_to(t, shape):
+    """t in the leading corner of a zero tensor of `shape`."""
+    if tuple(t.shape) == tuple(shape):
+        return t.contiguous()
+    out = torch.zeros(shape, dtype=t.dtype, device=t.device)
+    out[tuple(slice(0, n) for n in t.shape)] = t
+    return out
+
+
 class Step(collections.namedtuple('Step', 'kind projection downsample stride compact h1_in', defaults=(False, False, None, False, False))):
     """How one Bottleneck of a stage closes (ResNet.stage_route).  kind: the native entry -- 'tail', 'tail_next' (`projection`: the shortcut
-    as a second K segment, else the identity form), 'tail_next_live', 'close_sampled' (at `stride` 2 from the full-resolution input), 'conv' or
-    'gcb' (a block with a context block: the closing 1x1 without residual or ReLU, then native.context_block with both).
+    as a second K segment, else the identity form), 'tail_next_live', 'close_sampled' (at `stride` 2 from the full-resolution input), 'conv',
+    'gcb' (a block with a context block: the closing 1x1 without residual or ReLU, then native.context_block with both) or 'gn' (a block
+    under GroupNorm: every conv raw, its norm two launches behind it, the residual add and the ReLU in the last norm's apply).
     downsample: the projection shortcut is a conv of its own in front.  compact ('close_sampled' at stride 1, 'conv'): the dense close on the
     compact map that a tail_next_live block left.  h1_in: the block's conv1 output arrived from the block before."""
 
@@ -196,11 +232,29 @@ class Bottleneck(nn.Module, PackedMixin):
             raise NotImplementedError('dcn on a grouped Bottleneck (the dcn[\'groups\'] form of resnext.py:57-83) is not built')
         if groups > 1 and gen_attention is not None:
             raise NotImplementedError('gen_attention on a grouped Bottleneck is not built (the reference\'s resnext.py accepts the argument and drops it)')
+        kind, self.num_groups, eps = norm_kind(norm_cfg, 'Bottleneck')
+        self.with_gn = kind == 'GN'
+        if self.with_gn:
+            for arg, name in ((dcn, 'dcn'), (gcb, 'gcb'), (gen_attention, 'gen_attention')):
+                if arg is not None:
+                    raise NotImplementedError('%s on a Bottleneck under GroupNorm (norm_cfg type GN) is not built' % name)
+            if groups > 1:
+                raise NotImplementedError('GroupNorm (norm_cfg type GN) on a grouped Bottleneck (groups=%d) is not built' % groups)
+            # the maps the norms run on: conv1 / conv2 outputs (width channels, padded with zero groups to a multiple of 64) and conv3's
+            self.gn_width, self.gn_width_groups = gn_padded(width, self.num_groups, 'Bottleneck gn1 / gn2')
+            if gn_padded(planes * 4, self.num_groups, 'Bottleneck gn3') != (planes * 4, self.num_groups):
+                raise NotImplementedError('Bottleneck gn3: %d channels are no multiple of 64 (GroupNorm kernels)' % (planes * 4))
+            if downsample is not None and not isinstance(downsample[1], nn.GroupNorm):
+                raise NotImplementedError('a Bottleneck under GroupNorm takes a (conv, GroupNorm) projection shortcut, got %s' % type(downsample[1]).__name__)
+        self.gn_eps = eps
+        self.norm_names = tuple(('gn' if self.with_gn else 'bn') + str(i) for i in (1, 2, 3))
+
+        def norm(ch):   # norm.py: build_norm_layer
+            return nn.GroupNorm(self.num_groups, ch, eps=eps) if self.with_gn else nn.BatchNorm2d(ch, eps=eps)
         # caffe: stride on the first 1x1 (resnet.py:127-132)
         self.conv1_stride, self.conv2_stride = (1, stride) if style == 'pytorch' else (stride, 1)
-        eps = (norm_cfg or {}).get('eps', 1e-5)
         self.conv1 = nn.Conv2d(inplanes, width, 1, stride=self.conv1_stride, bias=False)
-        self.bn1 = nn.BatchNorm2d(width, eps=eps)
+        self.add_module(self.norm_names[0], norm(width))
         # resnet.py:147-186: conv2 is a (modulated) deformable 3x3 whose offsets (and mask logits) come from conv2_offset, a plain
         # biased 3x3 on the same input; fallback_on_stride keeps the plain conv where conv2 carries a stride
         self.dcn = dcn
@@ -212,9 +266,9 @@ class Bottleneck(nn.Module, PackedMixin):
             self.conv2_offset = nn.Conv2d(width, self.deformable_groups * offset_channels, 3, stride=self.conv2_stride, padding=dilation,
                                           dilation=dilation)
         self.conv2 = nn.Conv2d(width, width, 3, stride=self.conv2_stride, padding=dilation, dilation=dilation, groups=groups, bias=False)
-        self.bn2 = nn.BatchNorm2d(width, eps=eps)
+        self.add_module(self.norm_names[1], norm(width))
         self.conv3 = nn.Conv2d(width, planes * 4, 1, bias=False)
-        self.bn3 = nn.BatchNorm2d(planes * 4, eps=eps)
+        self.add_module(self.norm_names[2], norm(planes * 4))
         self.downsample = downsample
         # resnet.py:199-201,249-250: the global context block acts on bn3's output, in front of the residual add
         self.gcb, self.with_gcb = gcb, gcb is not None
@@ -228,15 +282,38 @@ class Bottleneck(nn.Module, PackedMixin):
             self.gen_attention_block = GeneralizedAttention(planes, **gen_attention)
         self._init_packed()
 
+    norm1 = property(lambda self: getattr(self, self.norm_names[0]))   # resnet.py:208-218
+    norm2 = property(lambda self: getattr(self, self.norm_names[1]))
+    norm3 = property(lambda self: getattr(self, self.norm_names[2]))
+
+    def _pack_gn(self, dtype):
+        """Under GroupNorm nothing folds: the conv weights raw (no bias), gamma and beta f32.  Where width is no multiple of 64 the maps of
+        conv1 and conv2 carry whole groups of zero channels behind the real ones (gn_padded): zero weight rows and columns, gamma = beta = 0."""
+        wp = self.gn_width
+
+        def raw(conv, cout, cin):
+            w = conv.weight.detach().float().permute(0, 2, 3, 1)
+            return native.as_operand(_pad_to(w, (cout, w.shape[1], w.shape[2], cin)), dtype)
+
+        def affine(gn, c):
+            return _pad_to(gn.weight.detach().float(), (c,)), _pad_to(gn.bias.detach().float(), (c,))
+        p = dict(c1=raw(self.conv1, wp, self.inplanes), n1=affine(self.norm1, wp), c2=raw(self.conv2, wp, wp), n2=affine(self.norm2, wp),
+                 c3=raw(self.conv3, 4 * self.planes, wp), n3=affine(self.norm3, 4 * self.planes))
+        if self.downsample is not None:
+            p['ds'], p['nd'] = raw(self.downsample[0], 4 * self.planes, self.inplanes), affine(self.downsample[1], 4 * self.planes)
+        return p
+
     def _pack(self, dtype):
-        p = dict(c1=fold_conv_bn(self.conv1, self.bn1, dtype), c3=fold_conv_bn(self.conv3, self.bn3, dtype))
+        if self.with_gn:
+            return self._pack_gn(dtype)
+        p = dict(c1=fold_conv_bn(self.conv1, self.norm1, dtype), c3=fold_conv_bn(self.conv3, self.norm3, dtype))
         if self.groups > 1:
             # bn2 folded into the grouped weight [width,3,3,width/groups]; the operand forms (grouped, block-diagonal dense) are made by the
             # route that first needs them (native.GroupedWeight)
-            wg, bg = fold_conv_bn(self.conv2, self.bn2, torch.float32)
+            wg, bg = fold_conv_bn(self.conv2, self.norm2, torch.float32)
             p['c2'] = (native.GroupedWeight(wg, dtype), bg)
         else:
-            p['c2'] = fold_conv_bn(self.conv2, self.bn2, dtype)
+            p['c2'] = fold_conv_bn(self.conv2, self.norm2, dtype)
         if self.with_dcn:
             # the offset conv: Cout padded with zero rows to a multiple the engine takes (N % 4); its output stays f32 in every mode
             wo, bo = fold_conv_bn(self.conv2_offset, None, torch.float32)
@@ -260,6 +337,8 @@ class Bottleneck(nn.Module, PackedMixin):
         stride = 1 if compact_in else self.stride
         OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
         P, C, proj = self.width, 4 * self.planes, self.downsample is not None
+        if self.with_gn:    # a group's statistics need every pixel of the conv's output: no fused close, no sampled or compact form
+            return Step('gn', downsample=proj)
         if self.with_gcb:   # the context block sits between conv3 and the residual add: no fused close, whatever fuse_next / fuse_tail say
             return Step('gcb', downsample=proj)
         # split half has no second-K-segment tail: the projection is its own conv and enters the fused closing 1x1 + next conv1 as the
@@ -278,6 +357,12 @@ class Bottleneck(nn.Module, PackedMixin):
         compact_in (a caffe-style stride-2 block): x holds only the pixels the strided 1x1 convs read, so they run at stride 1.
         A block with a generalized attention block applies it here, to conv2's output at every pixel (conv2_only: without it): every close
         that only reads h ('conv', 'tail', 'tail_next', 'gcb') stays available to it; the sampled and compact forms are not (ResNet._dead_pixels)."""
+        if self.with_gn:
+            assert h1 is None and not compact_in and conv2_stride is None and out is None, 'a block under GroupNorm has the full-resolution form only'
+            p = self.packed(x.device)
+            h = self._gn(self._gn_conv(x, p['c1'], stride=self.conv1_stride), p['n1'], self.gn_width_groups, x.dtype)
+            u = self._gn_conv(h, p['c2'], stride=self.conv2_stride, pad=self.dilation, dil=self.dilation)
+            return self._gn(u, p['n2'], self.gn_width_groups, x.dtype)
         if self.with_gen_attention and not conv2_only:
             assert conv2_stride is None, 'a block with gen_attention has no sampled form'
             return self.gen_attention_block.forward_nhwc(self.body(x, h1, compact_in, conv2_only=True), out=out)
@@ -292,6 +377,23 @@ class Bottleneck(nn.Module, PackedMixin):
             return native.conv3x3_grouped(h, p['c2'][0], p['c2'][1], True, s2, self.dilation, out=out, route=self.grouped_route)
         return native.conv2d_nhwc(h, p['c2'][0], p['c2'][1], relu=True, stride=s2, pad=self.dilation, dil=self.dilation, out=out)
 
+    @staticmethod
+    def _gn_conv(x, w, **kw):
+        """A raw conv (no bias, no activation) -> u in the format its norm reads: the compute format (one rounding of u more than the
+        reference makes, as the context block's u), split half: f32 straight from the accumulators."""
+        return native.conv2d_nhwc(x, w, None, relu=False, out_f32=x.dtype == native.SPLIT, **kw)
+
+    def _gn(self, u, affine, G, dtype, relu=True, resid=None, resid_norm=None, out=None):
+        """GroupNorm (+ r) (+ ReLU) on u -> a map in the compute format `dtype`: in place on u, or into out.  Split half has no kernel form: u
+        is f32, the result is cast (the rule the context block follows)."""
+        if dtype == native.SPLIT:
+            y = native.cast(native.group_norm(u, affine[0], affine[1], G, self.gn_eps, resid, resid_norm, relu, out=u), native.SPLIT)
+            if out is None:
+                return y
+            out.copy_(y)
+            return out
+        return native.group_norm(u, affine[0], affine[1], G, self.gn_eps, resid, resid_norm, relu, out=u if out is None else out)
+
     def _conv2(self, x, h1, compact_in, conv2_stride, out):
         return self.body(x, h1, compact_in, conv2_stride, out, conv2_only=True)
 
@@ -299,6 +401,17 @@ class Bottleneck(nn.Module, PackedMixin):
         """The plain close ('tail', 'conv' or 'gcb') -> y.  out: where y goes (a contiguous [B,OH,OW,4*planes] tensor), e.g. a frame group's slice."""
         p = self.packed(x.device)
         stride = 1 if compact_in else self.stride
+        if step.kind == 'gn':
+            # y = relu(GN3(conv3(h)) + identity) in ONE apply; a projection shortcut's conv output is normalised inside it (its statistics
+            # are one more pass, its normalised map is never written)
+            assert self.with_gn and not compact_in, step
+            G, u = self.num_groups, self._gn_conv(h, p['c3'])
+            if step.downsample:
+                resid = self._gn_conv(x, p['ds'], stride=stride)
+                rn = (native.group_norm_stats(resid, G),) + p['nd']
+            else:
+                resid, rn = native.cast(x, torch.float32) if x.dtype == native.SPLIT else x, None
+            return self._gn(u, p['n3'], G, x.dtype, True, resid, rn, out)
         if step.kind == 'gcb':
             # u = bn3(conv3(h)) as a map of its own (the pool reads every pixel of it), then relu(context_block(u) + identity) in the apply
             identity = native.conv2d_nhwc(x, p['ds'][0], p['ds'][1], relu=False, stride=stride) if step.downsample else x
@@ -360,6 +473,8 @@ class Bottleneck(nn.Module, PackedMixin):
     def forward_train_nhwc(self, x):
         """The block as an autograd graph of HIP convs (train_ops.conv_bn): frozen BatchNorm statistics and affine
         (norm_eval=True, requires_grad=False in both configs), trainable conv weights; f32, physical NHWC."""
+        if self.with_gn:
+            raise NotImplementedError('Bottlenecks under GroupNorm are inference only: group normalisation has no backward')
         if self.with_dcn:
             raise NotImplementedError('deformable convs are inference only: no backward (col2im + coordinate gradients) is implemented')
         if self.groups > 1:
@@ -369,19 +484,20 @@ class Bottleneck(nn.Module, PackedMixin):
         if self.with_gen_attention:
             raise NotImplementedError('Bottlenecks with a generalized attention block are inference only: the attention core has no backward')
         from . import train_ops as TO
-        out = TO.conv_bn(x, self.conv1, self.bn1, relu=True)
-        out = TO.conv_bn(out, self.conv2, self.bn2, relu=True)
+        out = TO.conv_bn(x, self.conv1, self.norm1, relu=True)
+        out = TO.conv_bn(out, self.conv2, self.norm2, relu=True)
         identity = x if self.downsample is None else TO.conv_bn(x, self.downsample[0], self.downsample[1])
-        return TO.conv_bn(out, self.conv3, self.bn3, resid=identity, relu=True)
+        return TO.conv_bn(out, self.conv3, self.norm3, resid=identity, relu=True)
 
 
 def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style='pytorch', norm_cfg=None, dcn=None, groups=1, base_width=4, gcb=None,
                    gen_attention=None, gen_attention_blocks=(), **_unused):
     downsample = None
-    eps = (norm_cfg or {}).get('eps', 1e-5)
+    kind, num_groups, eps = norm_kind(norm_cfg, 'make_res_layer')
     if stride != 1 or inplanes != planes * block.expansion:
-        downsample = nn.Sequential(nn.Conv2d(inplanes, planes * block.expansion, 1, stride=stride, bias=False),
-                                   nn.BatchNorm2d(planes * block.expansion, eps=eps))
+        cout = planes * block.expansion
+        downsample = nn.Sequential(nn.Conv2d(inplanes, cout, 1, stride=stride, bias=False),
+                                   nn.GroupNorm(num_groups, cout, eps=eps) if kind == 'GN' else nn.BatchNorm2d(cout, eps=eps))
     extra = {} if dcn is None else dict(dcn=dcn)
     if groups != 1:   # resnext.py:94-154
         extra.update(groups=groups, base_width=base_width)
@@ -408,7 +524,9 @@ class ResNet(nn.Module, PackedMixin):
     """Same kwargs as the reference ResNet (resnet.py:372-395); dcn / stage_with_dcn as there (deformable conv2 in the marked
     stages, inference only); gcb / stage_with_gcb as there (a global context block between bn3 and the residual add of every block of the
     marked stages, inference only); gen_attention / stage_with_gen_attention as there (a generalized attention block between conv2 and conv3
-    of the blocks named per stage, inference only); conv_cfg must be None."""
+    of the blocks named per stage, inference only); norm_cfg type 'BN' (frozen, folded into the convs) or 'GN' (dict(type='GN',
+    num_groups=32): gn1 / gn2 / gn3 as in the reference, native.group_norm behind every raw conv, inference only, not together with dcn /
+    gcb / gen_attention); conv_cfg must be None."""
     arch_settings = {d: (Bottleneck, s) for d, s in ARCH_SETTINGS.items()}
     _block_kwargs = {}   # what every block gets beyond the reference ResNet's arguments (ResNeXt: groups, base_width)
 
@@ -445,8 +563,16 @@ class ResNet(nn.Module, PackedMixin):
                 # (the reference builds the plain net then and drops the dict without a word; an argument that would be disobeyed is refused)
                 raise NotImplementedError('gcb is given but stage_with_gcb marks no stage: no context block would be built; mark a stage or pass gcb=None')
         self.gcb, self.stage_with_gcb = gcb, stage_with_gcb
-        if norm_cfg.get('type', 'BN') != 'BN':
-            raise NotImplementedError('only frozen BatchNorm is supported')
+        kind, self.num_groups, eps = norm_kind(norm_cfg, type(self).__name__)
+        self.with_gn, self.gn_eps, self.norm_cfg = kind == 'GN', eps, norm_cfg
+        if self.with_gn:
+            for arg, name in ((dcn, 'dcn'), (gcb, 'gcb'), (gen_attention, 'gen_attention')):
+                if arg is not None:
+                    raise NotImplementedError('%s together with GroupNorm (norm_cfg type GN) is not built' % name)
+            if self._block_kwargs.get('groups', 1) > 1:
+                raise NotImplementedError('GroupNorm (norm_cfg type GN) on %s with groups=%d is not built' % (type(self).__name__, self._block_kwargs['groups']))
+            if gn_padded(64, self.num_groups, 'the stem\'s gn1') != (64, self.num_groups):
+                raise NotImplementedError('the stem\'s gn1: num_groups=%d on 64 channels is outside the instance set' % self.num_groups)
         assert 1 <= num_stages <= 4 and len(strides) == len(dilations) == num_stages and max(out_indices) < num_stages
         assert in_channels == 3
         self.depth, self.num_stages, self.strides, self.dilations = depth, num_stages, strides, dilations
@@ -454,7 +580,8 @@ class ResNet(nn.Module, PackedMixin):
         self.zero_init_residual = zero_init_residual
         self.stage_blocks = stage_blocks[:num_stages]
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
-        self.bn1 = nn.BatchNorm2d(64, eps=norm_cfg.get('eps', 1e-5))
+        self.norm1_name = 'gn1' if self.with_gn else 'bn1'
+        self.add_module(self.norm1_name, nn.GroupNorm(self.num_groups, 64, eps=eps) if self.with_gn else nn.BatchNorm2d(64, eps=eps))
         self.res_layers = []
         inplanes = 64
         for i, nb in enumerate(self.stage_blocks):
@@ -474,6 +601,8 @@ class ResNet(nn.Module, PackedMixin):
         _freeze(self)
         self._init_packed()
 
+    norm1 = property(lambda self: getattr(self, self.norm1_name))   # resnet.py:465-467
+
     def init_weights(self, pretrained=None):
         """resnet.py:496-520 (pretrained checkpoints are loaded by the caller via load_state_dict)."""
         if pretrained is not None:
@@ -481,7 +610,7 @@ class ResNet(nn.Module, PackedMixin):
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
-            elif isinstance(m, nn.BatchNorm2d):
+            elif isinstance(m, (nn.BatchNorm2d, nn.GroupNorm)):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
         if self.dcn is not None:   # resnet.py:507-511: a deformable conv starts as the plain conv (zero offsets; modulated: mask 0.5)
@@ -492,13 +621,16 @@ class ResNet(nn.Module, PackedMixin):
         if self.zero_init_residual:
             for m in self.modules():
                 if isinstance(m, Bottleneck):
-                    nn.init.constant_(m.bn3.weight, 0)
+                    nn.init.constant_(m.norm3.weight, 0)
         set_compute_dtype(self, self.compute_dtype)
 
     def _pack(self, dtype):
-        w, b = fold_conv_bn(self.conv1, self.bn1, torch.float32)  # [64,7,7,3]
+        w, b = fold_conv_bn(self.conv1, None if self.with_gn else self.norm1, torch.float32)  # [64,7,7,3]
         wp = torch.zeros((64, STEM_KP), dtype=torch.float32, device=w.device)
         wp[:, :147] = w.reshape(64, 147)
+        if self.with_gn:   # the raw weight for the patch-matrix GEMM (the fused stem kernel folds a BatchNorm: not used), gamma and beta f32
+            return dict(stem=(native.as_operand(wp, dtype), None),
+                        gn=(self.norm1.weight.detach().float().contiguous(), self.norm1.bias.detach().float().contiguous()))
         # fused bf16 stem: [n][ky][kx*4 + c], zero weight for the pad channel (c = 3) and the pad tap (kx = 7)
         wf = torch.zeros((64, 7, 8, 4), dtype=torch.float32, device=w.device)
         wf[:, :, :7, :3] = w
@@ -580,6 +712,8 @@ class ResNet(nn.Module, PackedMixin):
         (resnet.py:127-132,283-296): three quarters of its pixels are dead, and its last block computes the live quarter only
         (Bottleneck.close_sampled).  Few-row split-K (native.fewrow_split) picks its K slices by the row count, so the
         compact 3x3 would sum in another order than the full one: full resolution there."""
+        if self.with_gn:   # a group's statistics need every pixel: the stages of a GroupNorm net run at full resolution
+            return False
         if not self.skip_dead_pixels or i + 1 >= len(self.res_layers) or i in self.out_indices or native.fewrow_enabled():
             return False
         blocks, nxt = getattr(self, self.res_layers[i]), getattr(self, self.res_layers[i + 1])[0]
@@ -596,6 +730,12 @@ class ResNet(nn.Module, PackedMixin):
         """conv1 7x7/2 + bn1 + relu + maxpool 3x3/2 of x [B,3,H,W] -> physical NHWC in the compute dtype.  forward_train_nhwc never reaches
         the split-half branch of the generic route (training runs f32 or bf16)."""
         dt = self.compute_dtype
+        if self.with_gn:
+            # conv1 raw by the patch-matrix GEMM -> u (split half: f32), gn1 + ReLU in place, the pool
+            cols, OH, OW = native.im2col_stem(x.contiguous().float(), dt, STEM_KP)
+            u = native.gemm(cols, p['stem'][0], None, relu=False, out_f32=dt == native.SPLIT).view(x.shape[0], OH, OW, 64)
+            y = native.group_norm(u, p['gn'][0], p['gn'][1], self.num_groups, self.gn_eps, relu=True, out=u)
+            return native.cast(native.maxpool3x3s2_nhwc(y), dt)
         if dt in native.FUSED_DTYPES and self.fused_stem:
             return native.stem_fused(x.contiguous().float(), p['fused'], p['fused_bias'])
         # generic route (f32 / split-half modes): patch matrix + GEMM + pooling
@@ -643,6 +783,8 @@ class ResNet(nn.Module, PackedMixin):
         -> the last out_indices map, physical NHWC."""
         if self.gen_attention is not None:
             raise NotImplementedError('a ResNet with generalized attention blocks is inference only: the attention core has no backward')
+        if self.with_gn:
+            raise NotImplementedError('a ResNet under GroupNorm is inference only: group normalisation has no backward')
         with torch.no_grad():
             y = self._stem(x, self.packed(x.device))
             for i, name in enumerate(self.res_layers):
@@ -668,6 +810,11 @@ class ResLayer(nn.Module, PackedMixin):
                  norm_eval=True, with_cp=False, external_conv=False, dcn=None):
         super(ResLayer, self).__init__()
         self.dcn = dcn
+        self.with_gn = norm_kind(norm_cfg, type(self).__name__)[0] == 'GN'
+        if self.with_gn and dcn is not None:
+            raise NotImplementedError('dcn together with GroupNorm (norm_cfg type GN) is not built')
+        if self.with_gn and self._block_kwargs.get('groups', 1) > 1:
+            raise NotImplementedError('GroupNorm (norm_cfg type GN) on %s with groups=%d is not built' % (type(self).__name__, self._block_kwargs['groups']))
         self.norm_eval, self.norm_cfg, self.stage, self.external_conv = norm_eval, norm_cfg, stage, external_conv
         self.fp16_enabled = False
         stage_block = ARCH_SETTINGS[depth][stage]
@@ -693,7 +840,7 @@ class ResLayer(nn.Module, PackedMixin):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
                 if m.bias is not None:
                     nn.init.constant_(m.bias, 0)
-            elif isinstance(m, nn.BatchNorm2d):
+            elif isinstance(m, (nn.BatchNorm2d, nn.GroupNorm)):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
         set_compute_dtype(self, self.compute_dtype)
@@ -716,6 +863,8 @@ class ResLayer(nn.Module, PackedMixin):
 
     def forward_train_nhwc(self, y):
         """res5 + the external 1x1 conv as an autograd graph of HIP convs (f32, physical NHWC in and out)."""
+        if self.with_gn:
+            raise NotImplementedError('a ResLayer under GroupNorm is inference only: group normalisation has no backward')
         from . import train_ops as TO
         for blk in getattr(self, 'layer{}'.format(self.stage + 1)):
             y = blk.forward_train_nhwc(y)

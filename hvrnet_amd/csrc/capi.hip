@@ -100,6 +100,10 @@ void gcb_split(int B, int P, int* S, int* chunk);
 hipError_t run_gcb_pool(const void*, const float*, float*, int, int, int, int, hipStream_t);
 hipError_t run_gcb_transform(const float*, int, int, int, int, const float* const*, const float* const*, float*, float*, hipStream_t);
 hipError_t run_gcb_apply(const void*, const float*, const float*, const void*, void*, int, int, int, int, int, hipStream_t);
+void gn_split(int B, int P, int* S, int* chunk);
+hipError_t run_gn_stats(const void*, float*, int, int, int, int, int, hipStream_t);
+hipError_t run_gn_apply(const void*, const float*, const float*, const float*, float, const void*, const float*, const float*, const float*, void*, int,
+                        int, int, int, int, int, hipStream_t);
 int gen_attn_query_tile();
 int gen_attn_key_block();
 int gen_attn_max_pos();
@@ -788,6 +792,62 @@ int hvr_gcb_apply(const void* u, const float* m, const float* t, const void* res
     if (a < b + bytes && b < a + bytes) return fail(HVR_EINVAL, "hvr_gcb_apply: y overlaps an input without being it");
   }
   return check_launch(run_gcb_apply(u, m, t, resid, y, B, P, C, relu ? 1 : 0, dtype, (hipStream_t)stream), "hvr_gcb_apply");
+}
+
+// ---- group normalisation (gn.hip)
+static bool gn_instance(int C, int G) {
+  if (C < 64 || C > 2048 || C % 64 || G < 1 || C % G) return false;
+  const int cg = C / G;
+  return cg == 2 || cg == 4 || cg == 8 || cg == 16 || cg == 32 || cg == 64;
+}
+static int gn_shape(const char* what, int B, int P, int C, int G, int dtype) {
+  if (!valid_dtype(dtype)) return fail(HVR_EINVAL, "%s: bad dtype %d", what, dtype);
+  if (dtype == HVR_F16S) return fail(HVR_EUNSUPPORTED, "%s: no split-half instance (normalise the f32 form)", what);
+  if (B <= 0 || P <= 0 || C <= 0 || G <= 0) return fail(HVR_EINVAL, "%s: empty map B=%d P=%d C=%d G=%d", what, B, P, C, G);
+  if (C % 64 || C > 2048) return fail(HVR_EUNSUPPORTED, "%s: C=%d is no multiple of 64 from 64 to 2048", what, C);
+  if (C % G) return fail(HVR_EUNSUPPORTED, "%s: G=%d does not divide C=%d", what, G, C);
+  if (!gn_instance(C, G)) return fail(HVR_EUNSUPPORTED, "%s: Cg=%d channels per group (C=%d, G=%d) is not one of 2, 4, 8, 16, 32, 64", what, C / G, C, G);
+  if (B > 65535) return fail(HVR_EUNSUPPORTED, "%s: B=%d frames (up to 65535)", what, B);
+  if ((long)P * (C / G) > (1L << 24)) return fail(HVR_EUNSUPPORTED, "%s: %ld values per group and frame (up to 2^24: the counts are f32)", what, (long)P * (C / G));
+  return HVR_OK;
+}
+int hvr_gn_supported(int C, int G, int dtype) { return gn_instance(C, G) && (dtype == HVR_F32 || dtype == HVR_BF16 || dtype == HVR_F16); }
+int hvr_gn_splits(int B, int P, int C) {
+  if (B <= 0 || P <= 0 || C <= 0) return 0;
+  int S, chunk;
+  gn_split(B, P, &S, &chunk);
+  return S;
+}
+size_t hvr_gn_workspace_bytes(int B, int P, int C, int G) {
+  if (G <= 0) return 0;
+  return align256((size_t)B * hvr_gn_splits(B, P, C) * G * 4 * sizeof(float));
+}
+int hvr_gn_stats(const void* u, void* ws, size_t ws_bytes, int B, int P, int C, int G, int dtype, void* stream) {
+  if (int rc = gn_shape("hvr_gn_stats", B, P, C, G, dtype)) return rc;
+  if (!u || !ws || !aligned16(u) || !aligned16(ws)) return fail(HVR_EINVAL, "hvr_gn_stats: u and ws must be 16-byte aligned device pointers");
+  if (ws_bytes < hvr_gn_workspace_bytes(B, P, C, G))
+    return fail(HVR_EWORKSPACE, "hvr_gn_stats: workspace of %zu bytes, %zu needed", ws_bytes, hvr_gn_workspace_bytes(B, P, C, G));
+  return check_launch(run_gn_stats(u, (float*)ws, B, P, C, G, dtype, (hipStream_t)stream), "hvr_gn_stats");
+}
+int hvr_gn_apply(const void* u, const void* ws, const float* gamma, const float* beta, float eps, const void* resid, const void* ws_r,
+                 const float* gamma_r, const float* beta_r, void* y, int B, int P, int C, int G, int relu, int dtype, void* stream) {
+  if (int rc = gn_shape("hvr_gn_apply", B, P, C, G, dtype)) return rc;
+  if (!(eps > 0.f)) return fail(HVR_EINVAL, "hvr_gn_apply: eps=%g must be positive", (double)eps);
+  if (!u || !y || !ws || !gamma || !beta || !aligned16(u) || !aligned16(y) || !aligned16(ws) || (resid && !aligned16(resid)) || (ws_r && !aligned16(ws_r)))
+    return fail(HVR_EINVAL, "hvr_gn_apply: u, ws, resid, ws_r and y must be 16-byte aligned device pointers, gamma and beta given");
+  if ((ws_r != nullptr) != (gamma_r != nullptr) || (ws_r != nullptr) != (beta_r != nullptr) || (ws_r && !resid))
+    return fail(HVR_EINVAL, "hvr_gn_apply: a normalised residual takes resid, ws_r, gamma_r and beta_r together");
+  // y may BE u or resid (same address); any other overlap would let one lane read what another has written
+  const size_t bytes = (size_t)B * P * C * elem_size(dtype);
+  const void* ins[2] = {u, resid};
+  for (const void* x : ins) {
+    if (!x || x == y) continue;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(y);
+    if (a < b + bytes && b < a + bytes) return fail(HVR_EINVAL, "hvr_gn_apply: y overlaps an input without being it");
+  }
+  return check_launch(run_gn_apply(u, (const float*)ws, gamma, beta, eps, resid, (const float*)ws_r, gamma_r, beta_r, y, B, P, C, G, relu ? 1 : 0, dtype,
+                                   (hipStream_t)stream),
+                      "hvr_gn_apply");
 }
 
 // ---- generalized attention core (gen_attn.hip)

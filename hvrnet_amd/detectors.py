@@ -229,6 +229,10 @@ class _WindowDetector(TwoStageDetector):
         if getattr(self.backbone, 'gen_attention', None) is not None:
             # (HNMBRCNN.forward_train would run such a backbone frozen, under no_grad; the block is inference only everywhere, as stated)
             raise NotImplementedError('a detector whose backbone holds generalized attention blocks is inference only: the attention core has no backward')
+        for part in (self.backbone, getattr(self, 'shared_head', None)):
+            if getattr(part, 'with_gn', False):
+                raise NotImplementedError('a detector whose %s runs under GroupNorm is inference only: group normalisation has no backward'
+                                          % type(part).__name__)
         layer = self.bbox_roi_extractor.roi_layers[0]
         if not isinstance(layer, ops.RoIAlign):
             raise NotImplementedError('training runs through RoIAlign only: roi_layer %s is inference only (it has no backward)'

@@ -212,6 +212,11 @@ SYMBOLS = {
     'hvr_gcb_pool': (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     'hvr_gcb_transform': (_i, [_vp, _sz, _i, _i, _i, _i, ctypes.POINTER(GcbMlp), ctypes.POINTER(GcbMlp), _vp, _vp, _vp]),
     'hvr_gcb_apply': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'hvr_gn_supported': (_i, [_i, _i, _i]),
+    'hvr_gn_splits': (_i, [_i, _i, _i]),
+    'hvr_gn_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'hvr_gn_stats': (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    'hvr_gn_apply': (_i, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'hvr_gen_attn_supported': (_i, [_i, _i, _i, _i, _i]),
     'hvr_gen_attn_query_tile': (_i, []),
     'hvr_gen_attn_key_block': (_i, []),
@@ -1817,6 +1822,88 @@ def context_block(u, packed, resid=None, relu=False, out=None):
     B, P, C = _gcb_map(u, 'context_block')
     m, t = gcb_transform(gcb_pool(u, packed.get('wm')), P, packed.get('mul'), packed.get('add'))
     return gcb_apply(u, m, t, resid, relu, out)
+
+
+# ---- group normalisation (csrc/gn.hip; the rule: include/hvr_hip.h)
+def group_norm_supported(C, G, dtype):
+    """True when the group-norm kernels take maps of C channels in G groups in the compute format `dtype` (C a multiple of 64 from 64 to
+    2048, G divides C, C / G in {2, 4, 8, 16, 32, 64}; split half runs the f32 kernels, cast in and out by the caller).  Every other
+    shape is refused with HvrError: there is no second path."""
+    return bool(lib().hvr_gn_supported(int(C), int(G), DTYPE_CODES[torch.float32 if dtype == SPLIT else dtype]))
+
+
+def group_norm_splits(B, P, C):
+    """The runs the statistics pass cuts a frame's P pixels into: a function of the shape only."""
+    return int(lib().hvr_gn_splits(int(B), int(P), int(C)))
+
+
+def _gn_map(u, what):
+    if u.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise HvrError('%s: a %s map (float32 / bfloat16 / float16; a split-half map is normalised in its float32 form)' % (what, u.dtype))
+    if u.dim() != 4 or not u.is_contiguous():
+        raise HvrError('%s: the map must be a contiguous physical NHWC tensor, got shape %s strides %s' % (what, tuple(u.shape), u.stride()))
+    B, H, W, C = u.shape
+    return B, H * W, C
+
+
+def _gn_ws(ws, B, P, C, G, what):
+    S = group_norm_splits(B, P, C)
+    if ws.dtype != torch.float32 or tuple(ws.shape) != (B, S, G, 4) or not ws.is_contiguous():
+        raise HvrError('%s %s %s is not group_norm_stats\' of %d frames of %d pixels in %d groups: float32 %s'
+                       % (what, ws.dtype, tuple(ws.shape), B, P, G, (B, S, G, 4)))
+    return ws
+
+
+def group_norm_stats(u, G):
+    """One pass over u [B,H,W,C] (bf16 / half / f32): per frame, pixel run and group the centred partial (count, mean, M2, 0) -> ws f32
+    [B,S,G,4], S = group_norm_splits(B, H * W, C), which group_norm_apply merges.  A fresh tensor of torch's allocator (a block holds two
+    of them at a time: its conv3's and its shortcut's), so the call can be captured in a graph."""
+    _need_cuda(u)
+    B, P, C = _gn_map(u, 'group_norm_stats')
+    G = int(G)
+    S = group_norm_splits(B, P, C)
+    nbytes = lib().hvr_gn_workspace_bytes(B, P, C, max(G, 1))
+    buf = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=u.device)
+    with _span('gn_stats', float(B * P * C * u.element_size())):
+        _check(lib().hvr_gn_stats(_ptr(u), _ptr(buf), nbytes, B, P, C, G, _dt(u), _stream()), 'hvr_gn_stats')
+    return buf[:B * S * G * 16].view(torch.float32).view(B, S, G, 4)
+
+
+def group_norm_apply(u, ws, gamma, beta, eps, G, resid=None, resid_norm=None, relu=False, out=None):
+    """y = act((u - mean[n,g(c)]) * rstd[n,g(c)] * gamma[c] + beta[c] (+ r)) in f32, rounded once into u's format, mean and rstd merged
+    from ws = group_norm_stats(u, G).  gamma / beta f32 [C].  r: nothing, resid (a map like u), or -- resid_norm = (ws_r, gamma_r,
+    beta_r), ws_r = group_norm_stats(resid, G) -- resid normalised in the same pass.  out: a contiguous tensor like u; it may BE u (or
+    resid)."""
+    _need_cuda(u, ws, gamma, beta, resid, out)
+    B, P, C = _gn_map(u, 'group_norm_apply')
+    G = int(G)
+    _gn_ws(ws, B, P, C, G, 'group_norm_apply: ws')
+    _gcb_f32(gamma, (C,), 'group_norm_apply: gamma'), _gcb_f32(beta, (C,), 'group_norm_apply: beta')
+    ws_r = gamma_r = beta_r = None
+    if resid_norm is not None:
+        if resid is None:
+            raise HvrError('group_norm_apply: resid_norm without resid')
+        ws_r, gamma_r, beta_r = resid_norm
+        _need_cuda(ws_r, gamma_r, beta_r)
+        _gn_ws(ws_r, B, P, C, G, 'group_norm_apply: resid_norm ws')
+        _gcb_f32(gamma_r, (C,), 'group_norm_apply: resid_norm gamma'), _gcb_f32(beta_r, (C,), 'group_norm_apply: resid_norm beta')
+    for x, what in ((resid, 'resid'), (out, 'out')):
+        if x is not None and (x.dtype != u.dtype or tuple(x.shape) != tuple(u.shape) or not x.is_contiguous()):
+            raise HvrError('group_norm_apply: %s is %s %s, the map %s %s (same format, same shape, contiguous)'
+                           % (what, x.dtype, tuple(x.shape), u.dtype, tuple(u.shape)))
+    out = torch.empty_like(u) if out is None else out
+    moved = (2 + (resid is not None)) * B * P * C * u.element_size() + (1 + (ws_r is not None)) * ws.numel() * 4
+    with _span('gn_apply', float(moved)):
+        _check(lib().hvr_gn_apply(_ptr(u), _ptr(ws), _ptr(gamma), _ptr(beta), float(eps), _ptr(resid), _ptr(ws_r), _ptr(gamma_r), _ptr(beta_r),
+                                  _ptr(out), B, P, C, G, int(bool(relu)), _dt(u), _stream()), 'hvr_gn_apply')
+    return out
+
+
+def group_norm(u, gamma, beta, G, eps, resid=None, resid_norm=None, relu=False, out=None):
+    """torch.nn.GroupNorm(G, C, eps) on u [B,H,W,C] (bf16 / half / f32) with the residual add and the ReLU of a block's close: statistics
+    plus apply, two launches.  resid_norm = (the shortcut's group_norm_stats, gamma_r, beta_r).  Arguments as group_norm_apply."""
+    _need_cuda(u)
+    return group_norm_apply(u, group_norm_stats(u, G), gamma, beta, eps, G, resid, resid_norm, relu, out)
 
 
 # ---- generalized attention core (csrc/gen_attn.hip; the rule: include/hvr_hip.h)

@@ -49,6 +49,21 @@ def _bn(g, sd, prefix, c, gamma_scale=1.0):
     sd[prefix + '.num_batches_tracked'] = torch.zeros((), dtype=torch.long)
 
 
+def _gn(g, sd, prefix, c, gamma_scale=1.0):
+    """Keys of an nn.GroupNorm (no running statistics): gamma ~ U(0.5, 1.5), beta ~ 0.1 N."""
+    sd[prefix + '.weight'] = (torch.rand(c, generator=g) + 0.5) * gamma_scale
+    sd[prefix + '.bias'] = torch.randn(c, generator=g) * 0.1
+
+
+def _norm(g, sd, prefix, c, norm, gamma_scale=1.0):
+    """The norm layer behind a conv under the reference's name: prefix names the BatchNorm ('....bn1'); a GroupNorm is 'gn' + the same
+    postfix (norm.py: abbreviation + postfix), a module inside an nn.Sequential ('downsample.1') keeps its index."""
+    if norm == 'GN':
+        head, _, last = prefix.rpartition('.')
+        return _gn(g, sd, head + '.' + ('gn' + last[2:] if last.startswith('bn') else last), c, gamma_scale)
+    return _bn(g, sd, prefix, c, gamma_scale)
+
+
 def _gcb(g, sd, prefix, c, ratio, pooling_type='att', fusion_types=('channel_add', )):
     """Keys of a ContextBlock (context_block.py:31-51).  The reference zeroes the last conv of each branch, which makes a fresh block the
     identity (channel_add) or a constant 1/2 (channel_mul): here it gets values, so that the block shows in the output."""
@@ -97,21 +112,22 @@ def _gen_attention(g, sd, prefix, c, num_heads=9, position_embedding_dim=-1, att
         sd[prefix + '.geom_bias'] = (torch.rand(oc, generator=g) * 2.0 - 1.0) * stdv
 
 
-def _res_layer(g, sd, prefix, inplanes, planes, blocks, groups=1, base_width=4, gcb=None, gen_attention=None, gen_attention_blocks=()):
+def _res_layer(g, sd, prefix, inplanes, planes, blocks, groups=1, base_width=4, gcb=None, gen_attention=None, gen_attention_blocks=(),
+               norm='BN'):
     width = planes if groups == 1 else int(math.floor(planes * (base_width / 64))) * groups   # resnext.py:21-24
     for i in range(blocks):
         p = '%s.%d' % (prefix, i)
         cin = inplanes if i == 0 else planes * 4
         sd[p + '.conv1.weight'] = _conv(g, width, cin, 1)
-        _bn(g, sd, p + '.bn1', width)
+        _norm(g, sd, p + '.bn1', width, norm)
         sd[p + '.conv2.weight'] = _conv(g, width, width // groups, 3) * math.sqrt(groups)   # (fan_out counts one group's inputs: keep the output's scale)
-        _bn(g, sd, p + '.bn2', width)
+        _norm(g, sd, p + '.bn2', width, norm)
         sd[p + '.conv3.weight'] = _conv(g, planes * 4, width, 1)
         # a live but damped residual branch keeps 33 stacked blocks from blowing up
-        _bn(g, sd, p + '.bn3', planes * 4, gamma_scale=0.25)
+        _norm(g, sd, p + '.bn3', planes * 4, norm, gamma_scale=0.25)
         if i == 0:
             sd[p + '.downsample.0.weight'] = _conv(g, planes * 4, cin, 1)
-            _bn(g, sd, p + '.downsample.1', planes * 4)
+            _norm(g, sd, p + '.downsample.1', planes * 4, norm)
         if gcb is not None:
             _gcb(g, sd, p + '.context_block', planes * 4, **gcb)
         if gen_attention is not None and i in gen_attention_blocks:
@@ -145,16 +161,20 @@ def _linear(g, sd, prefix, cout, cin, gain, conv=False):
 
 
 def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024, roi_feat=256 * 49, groups=1, base_width=4, arch='resnet',
-                     gcb=None, stage_with_gcb=(False, True, True), gen_attention=None, stage_with_gen_attention=((), (), ())):
+                     gcb=None, stage_with_gcb=(False, True, True), gen_attention=None, stage_with_gen_attention=((), (), ()), norm='BN'):
     """Full detector state dict (f32, CPU) with the reference's key names.  groups / base_width: a ResNeXt backbone + ResXLayer.
     arch='res2net': a Res2Net backbone (101 layers, 26w x 4s, deep stem) + Res2Layer; the heads' keys are the same.
     gcb: dict(ratio=..., pooling_type=..., fusion_types=...) adds the context-block keys to the backbone stages marked in stage_with_gcb
     (ResNet / ResNeXt), with non-zero last convs; None (the default) leaves every key and value as before.
     gen_attention: the dict ResNet takes adds the keys of a generalized attention block to the blocks stage_with_gen_attention names per
-    stage (ResNet), with non-zero gamma and biases; None (the default) leaves every key and value as before."""
+    stage (ResNet), with non-zero gamma and biases; None (the default) leaves every key and value as before.
+    norm='GN': the backbone and res5 of norm_cfg=dict(type='GN', ...) -- gn1 / gn2 / gn3 and downsample.1 hold a GroupNorm's weight and bias only
+    (plain ResNet); 'BN' (the default) leaves every key and value as before."""
     assert arch in ('resnet', 'res2net'), arch
     assert gcb is None or arch == 'resnet', 'Res2Net takes no context blocks'
     assert gen_attention is None or (arch == 'resnet' and groups == 1), 'only ResNet takes generalized attention blocks'
+    assert norm in ('BN', 'GN'), norm
+    assert norm == 'BN' or (arch == 'resnet' and groups == 1 and gcb is None and gen_attention is None), 'only the plain ResNet takes GroupNorm'
     g = torch.Generator().manual_seed(seed)
     sd = {}
     blocks = STAGE_BLOCKS[depth]
@@ -172,14 +192,14 @@ def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024,
         _res2_layer(g, sd, 'shared_head.layer4', 1024, 512, blocks[3])
     else:
         sd['backbone.conv1.weight'] = _conv(g, 64, 3, 7)
-        _bn(g, sd, 'backbone.bn1', 64)
+        _norm(g, sd, 'backbone.bn1', 64, norm)
         inplanes = 64
         for i in range(3):
             _res_layer(g, sd, 'backbone.layer%d' % (i + 1), inplanes, 64 * 2 ** i, blocks[i], groups, base_width,
                        gcb if gcb is not None and stage_with_gcb[i] else None, gen_attention,
-                       tuple(stage_with_gen_attention[i]) if gen_attention is not None and i < len(stage_with_gen_attention) else ())
+                       tuple(stage_with_gen_attention[i]) if gen_attention is not None and i < len(stage_with_gen_attention) else (), norm)
             inplanes = 64 * 2 ** i * 4
-        _res_layer(g, sd, 'shared_head.layer4', 1024, 512, blocks[3], groups, base_width)
+        _res_layer(g, sd, 'shared_head.layer4', 1024, 512, blocks[3], groups, base_width, norm=norm)
     sd['shared_head.new_layer_1.conv.weight'] = _conv(g, 256, 2048, 1) * NEW_LAYER_GAIN
     sd['shared_head.new_layer_1.conv.bias'] = torch.randn(256, generator=g) * 0.01
     # RPN (12 anchors)

@@ -270,6 +270,44 @@ int hvr_gcb_apply(const void* u, const float* m, const float* t, const void* res
                   void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Group normalisation (torch.nn.GroupNorm), forward only.  Replaces the norm layers that build_norm_layer makes for
+ * norm_cfg = dict(type='GN', num_groups=G) (mmdet/models/utils/norm.py) behind every conv of a Bottleneck, and the residual add + ReLU
+ * that close the block (resnet.py:249-264).  A GroupNorm has no running statistics: it does not fold into the conv, every map is reduced
+ * per frame and group and then rescaled.  u [B][P][C] is a physical NHWC map (P = H * W pixels per frame) in `dtype` = HVR_F32 /
+ * HVR_BF16 / HVR_F16 (HVR_F16S: HVR_EUNSUPPORTED; run the f32 form); G groups of Cg = C / G consecutive channels; gamma[C], beta[C] f32;
+ * eps > 0.  The instance set (hvr_gn_supported answers 1 / 0 for C, G and dtype; anything else is refused before any launch, there is
+ * no other path): C a multiple of 64 from 64 to 2048, G divides C, Cg in {2, 4, 8, 16, 32, 64}; any P >= 1 with P * Cg <= 2^24 (the
+ * counts are exact f32 integers), any B from 1 to 65535.  The rule, per frame n and group g, over the N = P * Cg values of channels
+ * [g * Cg, (g + 1) * Cg), all in f32:
+ *   mean = sum u / N            var = sum (u - mean)^2 / N   (the BIASED variance)            rstd = 1 / sqrt(var + eps)
+ *   a[n][c] = rstd[n][g(c)] * gamma[c]
+ *   y = act((u - mean[n][g(c)]) * a[n][c] + beta[c] (+ r))       the product first, then beta, then r; act = ReLU when relu != 0
+ * and each element is rounded ONCE into `dtype`.  The apply is the centred form: u * m + t with t = beta - mean * m would lose
+ * |mean| * rstd * 2^-24 where a group's spread is small against its mean.  r is nothing (resid NULL), the map resid (same format and
+ * shape as u), or -- ws_r, gamma_r, beta_r given -- resid normalised in the same pass, r = (resid - mean_r) * a_r + beta_r with its
+ * own G-group statistics: the projection shortcut (conv, GroupNorm) of a block, whose normalised map is never written.
+ * hvr_gn_stats: ONE pass.  A frame's pixels are cut into S = hvr_gn_splits(B, P, C) runs (a function of the shape only) and every run
+ *  writes one f32 partial (count, mean - K, M2, K) per group to ws [B][S][G][4]: M2 = sum (u - mean)^2 over the run's values of the
+ * group, K the group's PIVOT, u[n][0][g * Cg] (its first channel at the frame's first pixel).  Every value enters as u - K, an exact
+ * subtraction where the group's spread is small against its mean, so no partial mean carries the mean's magnitude, and the apply
+ * forms u - mean as (u - K) - (mean - K).  Partials are centred at EVERY level -- a 16-byte piece (its values of one group: the mean, then the squared distances to it), the
+ * lane (a piece per pixel it visits), the wave (xor shuffles, the lower lane first), the workgroup (LDS, wave order), the runs (run
+ * order, in the apply) -- and merge by Chan's formula
+ *   d = mean_b - mean_a        mean = mean_a + d * n_b / n        M2 = M2_a + M2_b + d^2 * n_a * n_b / n        n = n_a + n_b
+ * never through a sum of squares.  The merge order is fixed by the shape; no float atomics: two runs of a call give the same bits.
+ * hvr_gn_apply: every workgroup merges the S partials of its frame (and those of ws_r) into mean and rstd, then streams 16 bytes per
+ * lane.  A lane reads its pieces of u and resid before it writes the same pieces of y: y may be u or resid itself (same address), no
+ * other overlap.  There is no third launch.  ws: hvr_gn_workspace_bytes(B, P, C, G) bytes, 16-byte aligned, written by hvr_gn_stats
+ * and read by hvr_gn_apply on the same stream.  No host synchronisation, no allocation.
+ * ---------------------------------------------------------------------------------- */
+int hvr_gn_supported(int C, int G, int dtype);
+int hvr_gn_splits(int B, int P, int C);
+size_t hvr_gn_workspace_bytes(int B, int P, int C, int G);
+int hvr_gn_stats(const void* u, void* ws, size_t ws_bytes, int B, int P, int C, int G, int dtype, void* stream);
+int hvr_gn_apply(const void* u, const void* ws, const float* gamma, const float* beta, float eps, const void* resid, const void* ws_r,
+                 const float* gamma_r, const float* beta_r, void* y, int B, int P, int C, int G, int relu, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Generalized (empirical) attention core, forward only.  Replaces the energy, softmax and weighted sum of
  * mmdet/models/plugins/generalized_attention.py:240-368 (spatial_range = -1, q_stride = 1); the projections in front and the closing
  * conv behind it are hvr_conv2d_nhwc calls.  q [B][H*W][heads*d], k and v [B][Hk*Wk][heads*d] are physical NHWC maps in `dtype` =
