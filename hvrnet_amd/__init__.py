@@ -1,7 +1,7 @@
 """hvrnet_amd -- MI355X-native HVRNet video-detection forward path.
 
 Importing the package registers the hot-path components under the reference's names
-(ResNet, ResNeXt, Res2Net, ResLayer, ResXLayer, Res2Layer, RPNHead, SingleRoIExtractor, SelsaBBoxHead, HRNMPBBoxHead, SelsaRCNN, HNMBRCNN).
+(ResNet, ResNeXt, Res2Net, ResLayer, ResXLayer, Res2Layer, RPNHead, GARPNHead, SingleRoIExtractor, SelsaBBoxHead, HRNMPBBoxHead, SelsaRCNN, HNMBRCNN).
 """
 __version__ = '0.1.0'
 
@@ -13,7 +13,8 @@ from .box_ops import (bbox_flip, bbox_mapping, bbox_mapping_back, merge_aug_bbox
                       merge_aug_scores)
 from .config import Config, hvr_config, selsa_config  # noqa: F401
 from .detectors import HNMBRCNN, SelsaRCNN  # noqa: F401
-from .ops import ContextBlock, GeneralizedAttention, seq_nms, soft_nms  # noqa: F401
+from .ga_rpn_head import GARPNHead  # noqa: F401
+from .ops import ContextBlock, GeneralizedAttention, MaskedConv2d, masked_conv2d, seq_nms, soft_nms  # noqa: F401
 from .pipelines import FrameIngest, FrameIngestAug  # noqa: F401
 from .registry import build_detector  # noqa: F401
 from .roi_extractor import SingleRoIExtractor  # noqa: F401

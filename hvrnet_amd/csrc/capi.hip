@@ -12,6 +12,7 @@
 #include "common.h"
 #include "gemm_params.h"
 #include "relation_bt.h"
+#include "ga_rpn.h"
 
 namespace hvr {
 hipError_t run_transpose_pad(const void*, void*, int, int, long, long, int, hipStream_t);
@@ -109,6 +110,13 @@ int gen_attn_key_block();
 int gen_attn_max_pos();
 hipError_t run_gen_attn(const void*, const void*, const void*, const float*, const void*, const void*, const float*, const float*, void*, int, int, int,
                         int, int, int, int, int, int, hipStream_t);
+hipError_t run_ga_mask_offsets(const float*, long, float, unsigned char*, const float*, long, const float*, float*, long, int, long, hipStream_t);
+int masked_conv_max_cout();
+hipError_t run_masked_conv(const void*, const void*, const float*, const unsigned char*, float*, int, int, int, int, int, int, int, long, int,
+                           hipStream_t);
+hipError_t run_ga_select(const float*, const float*, const float*, const unsigned char*, float*, int*, int*, int*, const GaParams&, hipStream_t);
+hipError_t run_ga_gather(const float*, const long long*, const int*, const int*, const int*, const int*, int, int, int, int, float*, int*,
+                         hipStream_t);
 }  // namespace hvr
 
 using namespace hvr;
@@ -1761,6 +1769,105 @@ int hvr_rpn_proposals(const hvr_rpn_desc* d, void* ws, size_t ws_bytes, void* st
   if (rc) return rc;
   return check_launch(run_rpn_gather(props, keep, n_keep, d->T, npre, d->nms_post, d->max_num, presorted, d->proposals, d->counts, s),
                       "rpn: gather");
+}
+
+// ---- Guided Anchoring RPN (ga_rpn.hip) ----
+int hvr_ga_mask_offsets(const float* loc, int64_t loc_pitch, float loc_filter_thr, uint8_t* keep, const float* shape, int64_t shape_pitch,
+                        const float* w_off, float* om, int64_t ldo, int nch, int64_t pixels, void* stream) {
+  if (!keep && !om) return fail(HVR_EINVAL, "hvr_ga_mask_offsets: neither a mask nor an offset output");
+  if (pixels <= 0) return fail(HVR_EINVAL, "hvr_ga_mask_offsets: %ld pixels", (long)pixels);
+  if (keep && (!loc || loc_pitch < 1)) return fail(HVR_EINVAL, "hvr_ga_mask_offsets: the mask needs loc and loc_pitch >= 1");
+  if (om && (!shape || !w_off || shape_pitch < 2 || nch <= 0 || ldo < nch))
+    return fail(HVR_EINVAL, "hvr_ga_mask_offsets: the offsets need shape (pitch >= 2), w_off, nch=%d >= 1 and ldo=%ld >= nch", nch, (long)ldo);
+  if ((reinterpret_cast<uintptr_t>(loc) & 3) || (reinterpret_cast<uintptr_t>(shape) & 3) || (reinterpret_cast<uintptr_t>(w_off) & 3) ||
+      (reinterpret_cast<uintptr_t>(om) & 3))
+    return fail(HVR_EINVAL, "hvr_ga_mask_offsets: misaligned pointer");
+  if (pixels > (1L << 40) / (om ? nch : 1)) return fail(HVR_EUNSUPPORTED, "hvr_ga_mask_offsets: too many outputs");
+  return check_launch(run_ga_mask_offsets(loc, (long)loc_pitch, loc_filter_thr, keep, shape, (long)shape_pitch, w_off, om, (long)ldo, om ? nch : 1,
+                                          (long)pixels, (hipStream_t)stream),
+                      "hvr_ga_mask_offsets");
+}
+
+int hvr_masked_conv_max_cout(void) { return masked_conv_max_cout(); }
+
+int hvr_masked_conv_fwd(const void* x, const void* w, const float* bias, const uint8_t* keep, float* out, int B, int H, int W, int Cin, int Cout,
+                        int KH, int KW, int pad, int64_t ldo, int dtype, void* stream) {
+  if (!valid_dtype(dtype)) return fail(HVR_EINVAL, "hvr_masked_conv_fwd: bad dtype %d", dtype);
+  if (dtype == HVR_F16S) return fail(HVR_EUNSUPPORTED, "hvr_masked_conv_fwd: no split-half instance (run the f32 form)");
+  if (!x || !w || !keep || !out) return fail(HVR_EINVAL, "hvr_masked_conv_fwd: null pointer");
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0)
+    return fail(HVR_EINVAL, "hvr_masked_conv_fwd: bad shape B=%d H=%d W=%d Cin=%d Cout=%d k=%dx%d", B, H, W, Cin, Cout, KH, KW);
+  if (KH != KW || (KH & 1) == 0 || pad != (KH - 1) / 2)
+    return fail(HVR_EINVAL, "hvr_masked_conv_fwd: kernel %dx%d pad %d is not odd, square and padded to the input size", KH, KW, pad);
+  if (Cin % (dtype == HVR_F32 ? 4 : 8)) return fail(HVR_EINVAL, "hvr_masked_conv_fwd: Cin=%d is not a whole number of 16-byte chunks", Cin);
+  if (ldo < Cout) return fail(HVR_EINVAL, "hvr_masked_conv_fwd: ldo=%ld is below Cout=%d", (long)ldo, Cout);
+  if (!aligned16(x) || !aligned16(w) || (reinterpret_cast<uintptr_t>(out) & 3) || (reinterpret_cast<uintptr_t>(bias) & 3))
+    return fail(HVR_EINVAL, "hvr_masked_conv_fwd: x and w must be 16-byte, out and bias 4-byte aligned");
+  if (Cout > masked_conv_max_cout())
+    return fail(HVR_EUNSUPPORTED, "hvr_masked_conv_fwd: Cout=%d is above the %d outputs of the skinny kernel (run the dense conv and zero the unkept pixels)",
+                Cout, masked_conv_max_cout());
+  if (KH > 15 || (long)B * H * W > 0x7fffffffL) return fail(HVR_EUNSUPPORTED, "hvr_masked_conv_fwd: kernel above 15x15 or 2^31 pixels");
+  return check_launch(run_masked_conv(x, w, bias, keep, out, B, H, W, Cin, Cout, KH, pad, (long)ldo, dtype, (hipStream_t)stream), "hvr_masked_conv_fwd");
+}
+
+static inline int ga_npre(int H, int W, int nms_pre) {
+  const long n = (long)H * W;
+  return (nms_pre > 0 && n > nms_pre) ? nms_pre : (int)n;
+}
+
+size_t hvr_ga_rpn_workspace_bytes(int T, int H, int W, int nms_pre) {
+  if (T <= 0 || H <= 0 || W <= 0 || (long)H * W > 8192) return 0;
+  const int npre = ga_npre(H, W, nms_pre);
+  return align256((size_t)T * npre * 5 * 4) + align256((size_t)T * npre * 8) + align256((size_t)T * npre * 4) + 3 * align256((size_t)T * 4) + nms_workspace_bytes(T, npre) + 256;
+}
+
+int hvr_ga_rpn_proposals(const hvr_ga_rpn_desc* d, void* ws, size_t ws_bytes, void* stream) {
+  if (!d || !ws) return fail(HVR_EINVAL, "hvr_ga_rpn_proposals: null pointer");
+  if (d->T <= 0 || d->H <= 0 || d->W <= 0) return fail(HVR_EINVAL, "hvr_ga_rpn_proposals needs T, H, W >= 1, got %d, %d, %d", d->T, d->H, d->W);
+  if (d->nms_post <= 0) return fail(HVR_EINVAL, "hvr_ga_rpn_proposals needs nms_post > 0");
+  if (d->max_num <= 0) return fail(HVR_EINVAL, "hvr_ga_rpn_proposals needs max_num > 0");
+  if (!d->cls || !d->reg || !d->shape || !d->keep || !d->proposals || !d->counts || !d->base_square || !d->anchoring_means ||
+      !d->anchoring_stds || !d->target_means || !d->target_stds)
+    return fail(HVR_EINVAL, "hvr_ga_rpn_proposals: null pointer in the descriptor");
+  if ((long)d->H * d->W > 8192) return fail(HVR_EUNSUPPORTED, "hvr_ga_rpn_proposals: a map of %d x %d is above 8192 pixels", d->H, d->W);
+  if (d->nms_post > 4096) return fail(HVR_EUNSUPPORTED, "hvr_ga_rpn_proposals: nms_post above 4096");
+  if (!(d->wh_ratio_clip > 0.f) || !std::isfinite(d->wh_ratio_clip))
+    return fail(HVR_EINVAL, "hvr_ga_rpn_proposals needs a finite wh_ratio_clip > 0, got %g", (double)d->wh_ratio_clip);
+  GaParams gp;
+  gp.T = d->T; gp.H = d->H; gp.W = d->W; gp.nms_pre = d->nms_pre; gp.stride = d->anchor_stride;
+  gp.npre = ga_npre(d->H, d->W, d->nms_pre);
+  gp.cls_pitch = d->cls_pitch > 0 ? d->cls_pitch : 1;
+  gp.reg_pitch = d->reg_pitch > 0 ? d->reg_pitch : 4;
+  gp.shape_pitch = d->shape_pitch > 0 ? d->shape_pitch : 2;
+  if (gp.reg_pitch < 4 || gp.shape_pitch < 2) return fail(HVR_EINVAL, "hvr_ga_rpn_proposals: bad pixel pitch");
+  if ((reinterpret_cast<uintptr_t>(d->cls) & 3) || (reinterpret_cast<uintptr_t>(d->reg) & 3) || (reinterpret_cast<uintptr_t>(d->shape) & 3))
+    return fail(HVR_EINVAL, "hvr_ga_rpn_proposals: misaligned map");
+  if (ws_bytes < hvr_ga_rpn_workspace_bytes(d->T, d->H, d->W, d->nms_pre)) return fail(HVR_EWORKSPACE, "ga rpn workspace too small");
+  for (int i = 0; i < 4; ++i) {
+    gp.square[i] = d->base_square[i];
+    gp.am[i] = d->anchoring_means[i]; gp.as[i] = d->anchoring_stds[i];
+    gp.tm[i] = d->target_means[i];    gp.ts[i] = d->target_stds[i];
+  }
+  gp.a_ratio = std::fabs(std::log(1e-6f));
+  gp.t_ratio = std::fabs(std::log(d->wh_ratio_clip));
+  gp.img_h = d->img_h; gp.img_w = d->img_w;
+  const int npre = gp.npre;
+  char* w = (char*)ws;
+  float* props = (float*)w;          w += align256((size_t)d->T * npre * 5 * 4);
+  long long* keep = (long long*)w;   w += align256((size_t)d->T * npre * 8);
+  int* n_keep = (int*)w;             w += align256((size_t)d->T * 4);
+  int* ncand = (int*)w;              w += align256((size_t)d->T * 4);
+  int* topk = (int*)w;               w += align256((size_t)d->T * 4);
+  int* pix = (int*)w;                w += align256((size_t)d->T * npre * 4);
+  hipStream_t s = (hipStream_t)stream;
+  int rc = check_launch(run_ga_select(d->cls, d->reg, d->shape, d->keep, props, pix, ncand, topk, gp, s), "ga rpn: select");
+  if (rc) return rc;
+  // Every survivor is needed: whether a frame's "first nms_post" are the first in score order (its top nms_pre were taken) or in
+  // row-major order (they were not) depends on its kept count, which only the device knows -- no cap on the NMS.
+  rc = check_launch(run_nms_batched(props, d->T, npre, d->nms_thr, 1, 1, 0, keep, n_keep, w, s), "ga rpn: nms");
+  if (rc) return rc;
+  return check_launch(run_ga_gather(props, keep, n_keep, pix, ncand, topk, d->T, npre, d->nms_post, d->max_num, d->proposals, d->counts, s),
+                      "ga rpn: gather");
 }
 
 // ---- RCNN read-out ----

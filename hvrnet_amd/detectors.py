@@ -151,6 +151,12 @@ class TwoStageDetector(BaseDetector):
         return self.rpn_head.get_bboxes(*(rpn_outs + (img_meta, rpn_test_cfg)))
 
 
+def _need_trainable_rpn(head):
+    """The training entry points take an RPN whose losses are on the HIP path; an inference-only head (GARPNHead) says so by name."""
+    if getattr(head, 'inference_only', False):
+        raise NotImplementedError('%s is inference only: training through it is not on the HIP path' % type(head).__name__)
+
+
 def _sampled_rois(results):
     """bbox2roi of the frames' sampled boxes (transforms.py:114-136): [sum n_i, 5] = (frame index, box).  The frame-index column comes from
     one repeat_interleave when every frame kept the same number of boxes (the sampler's `num`: the usual case), the boxes from one cat."""
@@ -297,7 +303,7 @@ class _WindowDetector(TwoStageDetector):
                 with torch.cuda.stream(side):
                     side.wait_event(ready)
                     rpn_outs = self.rpn_head([xc])
-                    props, counts = self.rpn_head.get_bboxes_batched(rpn_outs[0], rpn_outs[1], img_meta, self.test_cfg.rpn)
+                    props, counts = self.rpn_head.get_bboxes_batched(*rpn_outs, img_meta, self.test_cfg.rpn)
                     done = torch.cuda.Event()
                     done.record(side)
                 feats = [self.shared_head(xc)] if self.feat_from_shared_head else [xc]
@@ -306,7 +312,7 @@ class _WindowDetector(TwoStageDetector):
                 counts.record_stream(main)
             else:   # one chain (HVR_RPN_SIDE=0): no fork for a captured graph's replay to spread over further hardware queues
                 rpn_outs = self.rpn_head([xc])
-                props, counts = self.rpn_head.get_bboxes_batched(rpn_outs[0], rpn_outs[1], img_meta, self.test_cfg.rpn)
+                props, counts = self.rpn_head.get_bboxes_batched(*rpn_outs, img_meta, self.test_cfg.rpn)
                 feats = [self.shared_head(xc)] if self.feat_from_shared_head else [xc]
             T, mx = props.shape[0], props.shape[1]
             counts_dev = counts if speculate else None
@@ -560,7 +566,7 @@ class _WindowDetector(TwoStageDetector):
         props, counts = [None] * A, [None] * A
         for g, m in zip(groups, maps):
             rpn_outs = self.rpn_head([m])
-            p, c = self.rpn_head.get_bboxes_batched(rpn_outs[0], rpn_outs[1], [mt for a in g for mt in img_metas[a]], self.test_cfg.rpn)
+            p, c = self.rpn_head.get_bboxes_batched(*rpn_outs, [mt for a in g for mt in img_metas[a]], self.test_cfg.rpn)
             for i, a in enumerate(g):
                 props[a], counts[a] = p[i * T:(i + 1) * T], c[i * T:(i + 1) * T]
         return torch.stack(props, 0), torch.stack(counts, 0)
@@ -756,6 +762,7 @@ class SelsaRCNN(_WindowDetector):
         c4 = self.backbone.forward_train_nhwc(img)
         losses = dict()
         if self.with_rpn:
+            _need_trainable_rpn(self.rpn_head)
             A = self.rpn_head.num_anchors
             o = self.rpn_head.forward_train_fused(c4)
             rl = self.rpn_head.loss_train(o[key], gt_bboxes[key], img_meta[key], self.train_cfg.rpn, keys=keys.get('rpn'),
@@ -923,6 +930,7 @@ class HNMBRCNN(_WindowDetector):
         proposal_cfg = self.train_cfg.get('rpn_proposal', self.test_cfg.rpn)
         c4k = torch.cat([c4.permute(0, 2, 3, 1)[v * F_:(v + 1) * F_] for v in chosen], 0)          # the chosen videos' frames
         metas_k = [m for v in chosen for m in img_meta[v * F_:(v + 1) * F_]]
+        _need_trainable_rpn(self.rpn_head)
         with torch.no_grad():
             rpn_outs = self.rpn_head([c4k.permute(0, 3, 1, 2)])
             if len({tuple(m['img_shape'][:2]) for m in metas_k}) == 1:

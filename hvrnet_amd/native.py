@@ -132,6 +132,18 @@ class RpnDesc(ctypes.Structure):
                 ('cls_pitch', ctypes.c_int32), ('reg_pitch', ctypes.c_int32)]
 
 
+class GaRpnDesc(ctypes.Structure):           # hvr_ga_rpn_desc
+    _fields_ = [('cls', ctypes.c_void_p), ('reg', ctypes.c_void_p), ('shape', ctypes.c_void_p), ('keep', ctypes.c_void_p),
+                ('T', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('anchor_stride', ctypes.c_int32),
+                ('cls_pitch', ctypes.c_int32), ('reg_pitch', ctypes.c_int32), ('shape_pitch', ctypes.c_int32),
+                ('base_square', ctypes.c_void_p), ('anchoring_means', ctypes.c_void_p), ('anchoring_stds', ctypes.c_void_p),
+                ('target_means', ctypes.c_void_p), ('target_stds', ctypes.c_void_p),
+                ('img_h', ctypes.c_float), ('img_w', ctypes.c_float), ('wh_ratio_clip', ctypes.c_float),
+                ('nms_pre', ctypes.c_int32), ('nms_post', ctypes.c_int32), ('max_num', ctypes.c_int32),
+                ('nms_thr', ctypes.c_float),
+                ('proposals', ctypes.c_void_p), ('counts', ctypes.c_void_p)]
+
+
 # every symbol include/hvr_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _f, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
 SYMBOLS = {
@@ -227,6 +239,11 @@ SYMBOLS = {
     'hvr_rpn_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'hvr_rpn_proposals': (_i, [ctypes.POINTER(RpnDesc), _vp, _sz, _vp]),
     'hvr_rpn_wide_frames': (_i, [_i]),
+    'hvr_ga_mask_offsets': (_i, [_vp, _i64, _f, _vp, _vp, _i64, _vp, _vp, _i64, _i, _i64, _vp]),
+    'hvr_masked_conv_max_cout': (_i, []),
+    'hvr_masked_conv_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i, _vp]),
+    'hvr_ga_rpn_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'hvr_ga_rpn_proposals': (_i, [ctypes.POINTER(GaRpnDesc), _vp, _sz, _vp]),
     'hvr_det_decode': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp]),
     'hvr_multiclass_nms_workspace_bytes': (_sz, [_i, _i]),
     'hvr_multiclass_nms': (_i, [_vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -2065,6 +2082,115 @@ def rpn_proposals(cls, reg, base_anchors, anchor_stride, means, stds, img_shape,
     ws = _workspace(lib().hvr_rpn_workspace_bytes(T, H, W, A, int(nms_pre)), cls.device, 'rpn')
     with _span('rpn_proposals', float(cls.numel() * 4 + reg.numel() * 4)):
         _check(lib().hvr_rpn_proposals(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), 'hvr_rpn_proposals')
+    return props, counts
+
+
+def _pixel_slice(t, ch, what):
+    """A [T,H,W,ch] f32 map with unit channel stride whose pixels lie at one pitch (a channel slice of a wider contiguous conv output
+    keeps that output's pitch) -> the pitch in floats."""
+    T, H, W, C = t.shape
+    assert t.dtype == torch.float32 and C == ch, (what, tuple(t.shape), t.dtype)
+    p = t.stride(2)
+    assert (C == 1 or t.stride(3) == 1) and p >= C and t.stride(1) == W * p and t.stride(0) == H * W * p, \
+        (what, tuple(t.shape), t.stride())
+    return p
+
+
+def ga_mask_offsets(loc=None, loc_filter_thr=0.01, shape=None, w_off=None, ldo=None, keep=None, om=None):
+    """The location mask and / or the offsets of GA-RPN's feature adaption in one launch (hvr_ga_mask_offsets).
+    loc [T,H,W,1] f32 logits -> keep [T,H,W] uint8 = (sigmoid(loc) >= loc_filter_thr);
+    shape [T,H,W,2] f32, w_off [nch,2] f32 (conv_offset.weight) -> om [T,H,W,ldo] f32 (ldo >= nch, default nch; columns nch.. are
+    left as they are), the layout deform_im2col reads.  loc / shape may be channel slices of one conv output.  -> (keep, om),
+    None for the half that was not asked for."""
+    assert loc is not None or shape is not None
+    _need_cuda(loc, shape, w_off)
+    ref = loc if loc is not None else shape
+    T, H, W = ref.shape[:3]
+    lp = sp = 1
+    if loc is not None:
+        lp = _pixel_slice(loc, 1, 'loc')
+        keep = _out(keep, (T, H, W), torch.uint8, loc.device)
+    nch = 1
+    if shape is not None:
+        sp = _pixel_slice(shape, 2, 'shape')
+        assert tuple(shape.shape[:3]) == (T, H, W) and w_off is not None and w_off.dtype == torch.float32 and w_off.is_contiguous() \
+            and w_off.dim() == 2 and w_off.shape[1] == 2, 'w_off is the [nch, 2] f32 weight of the 1x1 offset conv'
+        nch = w_off.shape[0]
+        ldo = nch if ldo is None else int(ldo)
+        om = _out(om, (T, H, W, ldo), torch.float32, shape.device)
+    with _span('ga_mask_offsets', float(T * H * W * (4 + 8 + 1 + 4 * nch))):
+        _check(lib().hvr_ga_mask_offsets(_ptr(loc), lp, float(loc_filter_thr), _ptr(keep) if loc is not None else None, _ptr(shape), sp,
+                                         _ptr(w_off), _ptr(om) if shape is not None else None, ldo or 0, nch, T * H * W, _stream()),
+               'hvr_ga_mask_offsets')
+    return (keep if loc is not None else None), (om if shape is not None else None)
+
+
+def ga_loc_mask(loc, loc_filter_thr, out=None):
+    """keep [T,H,W] uint8 = (sigmoid(loc [T,H,W,1] f32) >= loc_filter_thr)."""
+    return ga_mask_offsets(loc=loc, loc_filter_thr=loc_filter_thr, keep=out)[0]
+
+
+def ga_offsets(shape, w_off, ldo=None, out=None):
+    """om [T,H,W,ldo] f32 = the 1x1, 2-channel, bias-free offset conv of shape [T,H,W,2] f32 with w_off [nch,2]."""
+    return ga_mask_offsets(shape=shape, w_off=w_off, ldo=ldo, om=out)[1]
+
+
+def masked_conv_max_cout():
+    """The most output channels masked_conv2d_nhwc has a kernel for."""
+    return int(lib().hvr_masked_conv_max_cout())
+
+
+def masked_conv2d_nhwc(x, w, bias, keep, pad=0, out=None):
+    """Conv at the kept pixels only (hvr_masked_conv_fwd): x [B,H,W,Cin] physical NHWC (bf16 / f16 / f32), w [Cout,KH,KW,Cin] of the
+    same dtype, bias [Cout] f32 or None, keep [B,H,W] uint8 (one mask per frame) -> out f32: bias + conv at kept pixels, exactly 0 at
+    the others.  out: a [B,H,W,ldo] f32 tensor, ldo >= Cout, whose first Cout columns are written (default: a fresh [B,H,W,Cout]).
+    Cout above masked_conv_max_cout() or split-half operands raise HvrError (HVR_EUNSUPPORTED)."""
+    _need_cuda(x, w, bias, keep)
+    B, H, W, Cin = x.shape
+    Cout, KH, KW, _ = w.shape
+    assert x.is_contiguous() and w.is_contiguous() and w.dtype == x.dtype and w.shape[3] == Cin, (tuple(x.shape), tuple(w.shape), x.dtype, w.dtype)
+    assert keep.dtype == torch.uint8 and keep.is_contiguous() and tuple(keep.shape) == (B, H, W), (tuple(keep.shape), keep.dtype)
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == Cout)
+    if out is None:
+        out = torch.empty((B, H, W, Cout), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape[:3]) == (B, H, W) and out.shape[3] >= Cout, tuple(out.shape)
+    kept_bytes = float(B * H * W * (1 + 4 * Cout) + Cout * KH * KW * Cin * x.element_size())
+    with _span('masked_conv', kept_bytes):
+        _check(lib().hvr_masked_conv_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(keep), _ptr(out), B, H, W, Cin, Cout, KH, KW, int(pad),
+                                         out.shape[3], _dt(x), _stream()), 'hvr_masked_conv_fwd')
+    return out
+
+
+def ga_rpn_proposals(cls, reg, shape, keep, base_square, anchor_stride, anchoring_means, anchoring_stds, target_means, target_stds,
+                     img_shape, nms_pre, nms_post, max_num, nms_thr, wh_ratio_clip=16 / 1000):
+    """Guided anchors + proposal read-out (hvr_ga_rpn_proposals): cls [T,H,W,1], reg [T,H,W,4], shape [T,H,W,2] f32 (physical NHWC; may
+    be channel slices of wider contiguous conv outputs), keep [T,H,W] uint8 from ga_mask_offsets, base_square [4] (the grid anchor of
+    AnchorGenerator(base_size, [octave_base_scale], [1.0])) -> (proposals [T,max_num,5] in score order, counts [T] int32)."""
+    _need_cuda(cls, reg, shape, keep)
+    T, H, W = cls.shape[:3]
+    cp, rp, sp = _pixel_slice(cls, 1, 'cls'), _pixel_slice(reg, 4, 'reg'), _pixel_slice(shape, 2, 'shape')
+    assert tuple(reg.shape[:3]) == (T, H, W) and tuple(shape.shape[:3]) == (T, H, W)
+    assert keep.dtype == torch.uint8 and keep.is_contiguous() and tuple(keep.shape) == (T, H, W), (tuple(keep.shape), keep.dtype)
+    props = torch.zeros((T, max_num, 5), dtype=torch.float32, device=cls.device)
+    counts = torch.zeros(T, dtype=torch.int32, device=cls.device)
+
+    def f4(v):
+        v = v.reshape(-1).tolist() if hasattr(v, 'reshape') else list(v)
+        assert len(v) == 4
+        return (ctypes.c_float * 4)(*[float(e) for e in v])
+    hold = [f4(base_square), f4(anchoring_means), f4(anchoring_stds), f4(target_means), f4(target_stds)]
+    hp = [ctypes.cast(h, ctypes.c_void_p) for h in hold]
+    d = GaRpnDesc(cls=cls.data_ptr(), reg=reg.data_ptr(), shape=shape.data_ptr(), keep=keep.data_ptr(), T=T, H=H, W=W,
+                  anchor_stride=int(anchor_stride), cls_pitch=cp, reg_pitch=rp, shape_pitch=sp, base_square=hp[0], anchoring_means=hp[1],
+                  anchoring_stds=hp[2], target_means=hp[3], target_stds=hp[4], img_h=float(img_shape[0]), img_w=float(img_shape[1]),
+                  wh_ratio_clip=float(wh_ratio_clip), nms_pre=int(nms_pre), nms_post=int(nms_post), max_num=int(max_num),
+                  nms_thr=float(nms_thr), proposals=props.data_ptr(), counts=counts.data_ptr())
+    nbytes = lib().hvr_ga_rpn_workspace_bytes(T, H, W, int(nms_pre))
+    if not nbytes:
+        raise HvrError('ga_rpn_proposals: a %d x %d map is above the 8192 pixels hvr_ga_rpn_proposals selects from' % (H, W))
+    ws = _workspace(nbytes, cls.device, 'ga_rpn')
+    with _span('ga_rpn_proposals', float(T * H * W * (4 * 7 + 1))):
+        _check(lib().hvr_ga_rpn_proposals(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), 'hvr_ga_rpn_proposals')
     return props, counts
 
 

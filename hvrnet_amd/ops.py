@@ -13,6 +13,8 @@ signatures and error behaviour:
   deform_roi_pooling(data, rois, offset, spatial_scale, out_size, out_channels, no_trans, group_size=1, part_size=None,
                      sample_per_part=4, trans_std=.0)                      dcn/deform_pool.py:10-79 (inference only)
   DeformRoIPooling / DeformRoIPoolingPack / ModulatedDeformRoIPoolingPack   dcn/deform_pool.py:82-252 (inference only)
+  masked_conv2d(features, mask, weight, bias, padding=0, stride=1)          masked_conv/masked_conv.py:15-61 (inference only)
+  MaskedConv2d(in_channels, out_channels, kernel_size, ...)                masked_conv/masked_conv.py:64-89
 plus `relation(q, k, v, scale)`: the relation core as an autograd Function with a HIP backward (training path).
 CPU tensors raise NotImplementedError exactly like the reference's RoIAlign (roi_align.py:27-28);
 NMS follows the reference's CPU semantics (`IoU >= thr` suppresses, nms_cpu.cpp:55).
@@ -526,6 +528,58 @@ class GeneralizedAttention(nn.Module, PackedMixin):
             raise NotImplementedError('GeneralizedAttention runs on the GPU only (no CPU fallback)')
         from .backbone import as_logical, as_nhwc
         return as_logical(self.forward_nhwc(as_nhwc(x, self.compute_dtype)))   # (in the compute format, as Bottleneck.forward)
+
+
+def masked_conv2d(features, mask, weight, bias, padding=0, stride=1, dtype=None):
+    """MaskedConv2dFunction.forward (masked_conv.py:15-53), forward only: features [B,C,H,W], mask [B,H,W] (or [1,H,W] for one frame, as
+    the reference asserts; > 0 keeps), weight [Cout,Cin,k,k], bias [Cout] or None -> [B,Cout,H,W] f32 (physically NHWC): bias + conv at
+    the kept pixels, exactly 0 at the others.  One mask per frame (the reference takes batch 1).  dtype: the operand format
+    (default: bf16 / f16 / f32 features keep theirs).  Up to native.masked_conv_max_cout() outputs run hvr_masked_conv_fwd, which never
+    reads the unkept rows; more outputs take the dense conv and zero the unkept pixels."""
+    pad_h, pad_w = _pair(padding)
+    stride_h, stride_w = _pair(stride)
+    if stride_h != 1 or stride_w != 1:
+        raise ValueError('Stride could not only be 1 in masked_conv2d currently.')
+    if not features.is_cuda:
+        raise NotImplementedError('masked_conv2d runs on the GPU only (no CPU fallback)')
+    assert mask.dim() == 3 and features.dim() == 4 and mask.size(0) == features.size(0) and features.size()[2:] == mask.size()[1:]
+    Cout, Cin, KH, KW = weight.shape
+    if KH != KW or KH % 2 == 0 or pad_h != pad_w or pad_h != (KH - 1) // 2:
+        raise NotImplementedError('masked_conv2d: odd square kernels padded to the input size only')
+    dtype = dtype or (features.dtype if features.dtype in (torch.bfloat16, torch.float16, torch.float32) else torch.float32)
+    from .backbone import as_nhwc, as_logical
+    keep = (mask > 0).to(torch.uint8).contiguous()
+    w = weight.detach().float().permute(0, 2, 3, 1).contiguous()
+    b = bias.detach().float().contiguous() if bias is not None else None
+    if Cout <= native.masked_conv_max_cout():
+        op = torch.float32 if dtype == native.SPLIT else dtype     # (no split-half kernel: the f32 form)
+        x = as_nhwc(features, op)
+        return as_logical(native.masked_conv2d_nhwc(x, w.to(op), b, keep, pad=pad_h))
+    x = as_nhwc(features, dtype)
+    wp, bp = _pad_rows(w.reshape(Cout, -1), b if b is not None else torch.zeros(Cout, device=w.device))
+    y = native.conv2d_nhwc(x, native.as_operand(wp.view(-1, KH, KW, Cin), dtype), bp, relu=False, pad=pad_h, out_f32=True)[..., :Cout]
+    return as_logical(torch.where(keep.unsqueeze(-1) != 0, y, torch.zeros((), dtype=y.dtype, device=y.device)))   # (not y * keep: 0 * inf is NaN, an unkept pixel is exactly 0)
+
+
+class MaskedConv2d(nn.Conv2d):
+    """masked_conv.py:64-89: an nn.Conv2d whose forward takes a mask.  mask=None is the plain conv (through conv2d_nhwc, like every conv
+    here); with a mask the conv is evaluated at the kept pixels only and the others are exactly 0."""
+
+    def forward(self, input, mask=None):
+        if not input.is_cuda:
+            raise NotImplementedError('MaskedConv2d runs on the GPU only (no CPU fallback)')
+        if mask is None:
+            if _pair(self.stride) != (1, 1) or _pair(self.dilation) != (1, 1) or self.groups != 1:
+                raise NotImplementedError('MaskedConv2d without a mask: stride 1, no dilation, one group')
+            from .backbone import as_nhwc, as_logical
+            dtype = input.dtype if input.dtype in (torch.bfloat16, torch.float16, torch.float32) else torch.float32
+            Cout, Cin, KH, KW = self.weight.shape
+            b = self.bias.detach().float() if self.bias is not None else torch.zeros(Cout, device=input.device)
+            wp, bp = _pad_rows(self.weight.detach().float().permute(0, 2, 3, 1).reshape(Cout, -1), b)
+            y = native.conv2d_nhwc(as_nhwc(input, dtype), native.as_operand(wp.view(-1, KH, KW, Cin), dtype), bp, relu=False,
+                                   pad=_pair(self.padding)[0], out_f32=True)
+            return as_logical(y[..., :Cout])
+        return masked_conv2d(input, mask, self.weight, self.bias, self.padding)
 
 
 class RelationFunction(Function):

@@ -9,7 +9,7 @@ own modules) see bit-identical tensors.
 State-dict keys and shapes are the reference's checkpoint contract:
   backbone.*      mmdet/models/backbones/resnet.py:456-466,269-329 (R101, 3 stages, caffe)
   shared_head.*   mmdet/models/shared_heads/res_layer.py:37-52
-  rpn_head.*      mmdet/models/anchor_heads/rpn_head.py:18-23
+  rpn_head.*      mmdet/models/anchor_heads/rpn_head.py:18-23 (synth_ga_rpn_state_dict: ga_rpn_head.py:19-22, guided_anchor_head.py:172-185)
   bbox_head.*     mmdet/models/bbox_heads/selsa_bbox_head.py:45-89, hrnmp_bbox_head.py:121-189
 
 The reference's own init (`zero_init_residual=True`, resnet.py:513-518; N(0, 0.01) head linears)
@@ -34,6 +34,14 @@ HEAD_REG_GAIN = 3.5
 RPN_CONV_GAIN = 1.0
 RPN_CLS_GAIN = 0.3
 RPN_REG_GAIN = 0.07
+# GA-RPN (synth_ga_rpn_state_dict): on the synthetic frames the C4 map is ~unit scale, so the 3x3 conv's output has a std of about
+# 0.01 * sqrt(9 C) * gain.  The location logits are centred on logit(loc_filter_thr) so that about half the pixels are kept; the
+# shape deltas stay within a few units, far inside the +-13.8 (= |log 1e-6|) clip after the anchoring stds (0.07 / 0.14).
+GA_CONV_GAIN = 3.0     # rpn_conv with zero-sum kernels (see synth_ga_rpn_state_dict): contrast is a fraction of the level
+GA_LOC_GAIN = 3.0
+GA_SHAPE_GAIN = 3.0
+GA_OFFSET_STD = 0.1     # feature_adaption.conv_offset: the reference's own init
+GA_ADAPT_GAIN = 1.0
 
 
 def _conv(g, cout, cin, k):
@@ -222,6 +230,31 @@ def synth_state_dict(head='hvr', seed=0, depth=101, num_classes=31, fc_dim=1024,
     if head == 'hvr':
         _linear(g, sd, 'bbox_head.fc_cls_2', num_classes, fc_dim, HEAD_CLS_GAIN)
         _linear(g, sd, 'bbox_head.fc_reg_2', 4, fc_dim, HEAD_REG_GAIN)
+    return sd
+
+
+def synth_ga_rpn_state_dict(channels=1024, deformable_groups=4, loc_filter_thr=0.01, seed=0, prefix='rpn_head.'):
+    """Seeded GARPNHead weights (f32, CPU) under the reference's key names (ga_rpn_head.py:19-22, guided_anchor_head.py:172-185,
+    :38-46), in_channels == feat_channels == channels.  A generator of its own: synth_state_dict's keys and values do not change.
+    Replace the `rpn_head.*` entries of a detector state dict with these to run a GA-RPN detector."""
+    g = torch.Generator().manual_seed(seed * 7919 + 26)
+    sd = {}
+    # C4 is a post-ReLU map with a large common level, and so is the 3x3 conv's output under zero-mean random weights: a random 1x1
+    # head on it sees one offset shared by every pixel, larger than the variation between pixels, and the location mask comes out
+    # all-kept or all-dropped whatever the gains.  So every 3x3 kernel here sums to zero over its taps (it answers to the map's spatial
+    # contrast, its output channels share one distribution) and the location weights sum to zero over the channels: the location logit
+    # then spreads evenly around its bias, which sits on the threshold.
+    w = torch.randn((channels, channels, 3, 3), generator=g)
+    sd[prefix + 'rpn_conv.weight'] = (w - w.mean(dim=(2, 3), keepdim=True)) * (0.01 * GA_CONV_GAIN)
+    sd[prefix + 'rpn_conv.bias'] = torch.zeros(channels)
+    _linear(g, sd, prefix + 'conv_loc', 1, channels, GA_LOC_GAIN, conv=True)
+    sd[prefix + 'conv_loc.weight'] -= sd[prefix + 'conv_loc.weight'].mean()
+    sd[prefix + 'conv_loc.bias'] = torch.full((1,), math.log(loc_filter_thr / (1.0 - loc_filter_thr)))   # half the pixels pass the filter
+    _linear(g, sd, prefix + 'conv_shape', 2, channels, GA_SHAPE_GAIN, conv=True)
+    sd[prefix + 'feature_adaption.conv_offset.weight'] = torch.randn((deformable_groups * 18, 2, 1, 1), generator=g) * GA_OFFSET_STD
+    sd[prefix + 'feature_adaption.conv_adaption.weight'] = torch.randn((channels, channels, 3, 3), generator=g) * (0.01 * GA_ADAPT_GAIN)
+    _linear(g, sd, prefix + 'conv_cls', 1, channels, RPN_CLS_GAIN, conv=True)
+    _linear(g, sd, prefix + 'conv_reg', 4, channels, RPN_REG_GAIN, conv=True)
     return sd
 
 

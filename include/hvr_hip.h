@@ -674,6 +674,77 @@ int hvr_rpn_proposals(const hvr_rpn_desc* d, void* ws, size_t ws_bytes, void* st
 int hvr_rpn_wide_frames(int frames);
 
 /* ------------------------------------------------------------------------------------
+ * Guided Anchoring RPN (GA-RPN), inference only, one level.  Replaces the inference path of GuidedAnchorHead / GARPNHead
+ * (mmdet/models/anchor_heads/guided_anchor_head.py:197-208, :271-362; ga_rpn_head.py:60-127) and MaskedConv2dFunction.forward
+ * (mmdet/ops/masked_conv/masked_conv.py:15-53).  Every step is f32 and every operation of the mask, offset and box rules is
+ * rounded on its own (no fused multiply-add); expf is the precise one, add and divide are correctly rounded.
+ *
+ * hvr_ga_mask_offsets: the location mask and the offset conv (feature_adaption.conv_offset) in one launch.
+ *   loc    [T][H][W] f32 logits, one per pixel, at pixel pitch loc_pitch (>= 1) -- a channel slice of a wider conv output is fine
+ *   keep   [T][H][W] uint8:  s = 1 / (1 + expf(-loc));  keep = (s >= loc_filter_thr) ? 1 : 0        (guided_anchor_head.py:203, :343-345)
+ *   shape  [T][H][W][2] f32 at pixel pitch shape_pitch (>= 2)
+ *   w_off  [nch][2] f32, the 1x1 offset conv's weight (no bias), nch = deformable_groups * 2 * KH * KW
+ *   om     [T][H][W][ldo] f32, ldo >= nch:  om[c] = w_off[c][0] * shape[0] + w_off[c][1] * shape[1]   (two products, one add)
+ *          -- the layout hvr_deform_im2col reads; columns nch .. ldo are not written
+ * keep == NULL computes only the offsets, om == NULL only the mask (both NULL: HVR_EINVAL).  The masked conv and the proposal
+ * entry below both READ this one keep map, so they cannot disagree about a pixel.
+ *
+ * hvr_masked_conv_fwd: conv evaluated at the kept pixels only.
+ *   x    [B][H][W][Cin]       physical NHWC, HVR_BF16 / HVR_F16 / HVR_F32 (HVR_F16S: HVR_EUNSUPPORTED; run the f32 form)
+ *   w    [Cout][KH][KW][Cin]  the packed conv layout, same dtype;  bias [Cout] f32 or NULL
+ *   keep [B][H][W] uint8      one mask PER FRAME (the reference asserts batch 1 and takes frame 0's mask: this is the per-frame
+ *                             generalisation, equal to the reference at B = 1)
+ *   out  [B][H][W][ldo] f32, ldo >= Cout; columns Cout .. ldo are not written
+ *   keep != 0:  out[co] = bias[co] + sum over (kh, kw, ci) of x[b][y - pad + kh][x - pad + kw][ci] * w[co][kh][kw][ci]
+ *               (taps outside the map contribute nothing), accumulated in f32 in a fixed order, rounded once
+ *   keep == 0:  out[co] = 0 exactly, for all Cout channels (NOT the bias: new_zeros + scatter, masked_conv.py:37-52); the rows
+ *               of x under an unkept pixel are not read
+ * Stride 1, KH == KW odd, pad == (KH - 1) / 2 (else HVR_EINVAL); Cin a multiple of 8 (f32: 4), x and w 16-byte aligned.
+ * Cout <= hvr_masked_conv_max_cout() (8): a skinny product with one wave per pixel; above it HVR_EUNSUPPORTED (run the dense
+ * conv and zero the unkept pixels).  No atomics: the same bits on every call.
+ *
+ * hvr_ga_rpn_proposals: guided anchors + proposal read-out for T frames.  Per frame, with n = H * W pixels in row-major order:
+ *   1. candidates = the pixels with keep == 1, in row-major order
+ *   2. square  = base_square + (x * stride, y * stride, x * stride, y * stride); base_square is the grid anchor of
+ *                AnchorGenerator(base_size, [octave_base_scale], [1.0]) (host [4] f32)
+ *      anchor  = delta2bbox(square, (0, 0, shape[0], shape[1]), anchoring_means, anchoring_stds, wh_ratio_clip = 1e-6), no
+ *                max_shape -- the means are added to dx and dy too
+ *   3. score   = 1 / (1 + expf(-cls))
+ *   4. nms_pre > 0 and more than nms_pre candidates: the top nms_pre by score (equal scores: lower pixel index first)
+ *   5. box     = delta2bbox(anchor, reg, target_means, target_stds, wh_ratio_clip) clipped to [0, img_w - 1] x [0, img_h - 1]
+ *   6. NMS at nms_thr with the IoU >= thr rule of hvr_rpn_proposals; of the survivors the first nms_post IN THE ORDER OF THE
+ *      CANDIDATE LIST -- score order when step 4 took a top-k, row-major pixel order when it did not (the reference's CPU NMS returns
+ *      the survivors by ascending input index; hvr_rpn_proposals reads it the same way) -- then the top max_num of those by score
+ *   delta2bbox(a, d, m, s, clip): d = d * s + m; dw, dh clamped to +-|log(clip)|; px = (a.x1 + a.x2) * 0.5, pw = a.x2 - a.x1 + 1;
+ *      gw = pw * expf(dw); gx = px + pw * dx; x1 = gx - gw * 0.5 + 0.5; x2 = gx + gw * 0.5 - 0.5; y alike
+ *   cls [T][H][W] (pitch cls_pitch), reg [T][H][W][4] (reg_pitch), shape [T][H][W][2] (shape_pitch): f32, may be channel slices
+ *   of fused conv outputs (pitch 0 = dense: 1 / 4 / 2); keep [T][H][W] uint8 from hvr_ga_mask_offsets.
+ *   proposals [T][max_num][5] f32 in score order, counts [T] int32 (rows beyond counts[t] are untouched).
+ * A frame with no kept pixel gives counts[t] = 0 (the reference `continue`s past the level and then fails in torch.cat).
+ * One form: one workgroup per frame selects, the mask + sweep NMS kernels of hvr_nms suppress (no survivor cap: step 6).  H * W <= 8192 (the C4 map of a
+ * 1000 x 600 frame, 38 x 63, has 2 394), nms_post <= 4096, else HVR_EUNSUPPORTED; T >= 1, nms_post > 0, max_num > 0, a finite
+ * wh_ratio_clip > 0, else HVR_EINVAL.  Nothing synchronises with the host, nothing allocates: the whole head can be captured in a graph.
+ * ---------------------------------------------------------------------------------- */
+int hvr_ga_mask_offsets(const float* loc, int64_t loc_pitch, float loc_filter_thr, uint8_t* keep, const float* shape, int64_t shape_pitch,
+                        const float* w_off, float* om, int64_t ldo, int nch, int64_t pixels, void* stream);
+int hvr_masked_conv_max_cout(void);
+int hvr_masked_conv_fwd(const void* x, const void* w, const float* bias, const uint8_t* keep, float* out, int B, int H, int W, int Cin,
+                        int Cout, int KH, int KW, int pad, int64_t ldo, int dtype, void* stream);
+typedef struct hvr_ga_rpn_desc {
+  const float* cls; const float* reg; const float* shape; const uint8_t* keep;
+  int32_t T, H, W, anchor_stride;
+  int32_t cls_pitch, reg_pitch, shape_pitch;   /* floats per pixel of each map (0 = 1 / 4 / 2) */
+  const float* base_square;                    /* host [4] */
+  const float* anchoring_means; const float* anchoring_stds; const float* target_means; const float* target_stds;  /* host [4] */
+  float img_h, img_w, wh_ratio_clip;           /* wh_ratio_clip of step 5 (16 / 1000); step 2 always uses 1e-6 */
+  int32_t nms_pre, nms_post, max_num;
+  float nms_thr;
+  float* proposals; int32_t* counts;
+} hvr_ga_rpn_desc;
+size_t hvr_ga_rpn_workspace_bytes(int T, int H, int W, int nms_pre);
+int hvr_ga_rpn_proposals(const hvr_ga_rpn_desc* d, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * RCNN detection read-out for one key frame.  Replaces BBoxHead.get_det_bboxes
  * (mmdet/models/bbox_heads/bbox_head.py:132-169; hrnmp_bbox_head.py:1009-1052 per branch):
  *   hvr_det_decode:     softmax over classes + delta2bbox + clip (+ / scale_factor)
