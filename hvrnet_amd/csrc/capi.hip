@@ -13,6 +13,7 @@
 #include "gemm_params.h"
 #include "relation_bt.h"
 #include "ga_rpn.h"
+#include "nms_dev.h"
 
 namespace hvr {
 hipError_t run_transpose_pad(const void*, void*, int, int, long, long, int, hipStream_t);
@@ -71,26 +72,21 @@ hipError_t run_deform_im2col(const void*, const float*, void*, int, int, int, in
                              hipStream_t);
 hipError_t run_deform_roi_pool(const void*, const float*, const float*, const float*, void*, int, int, int, int, int, int, int, int, int, int, int,
                                float, float, long, long, int, hipStream_t);
-size_t nms_workspace_bytes(int P, int n);
-hipError_t run_nms_batched(const float*, int, int, float, int, int, int, long long*, int*, void*, hipStream_t, int band = 0,
+hipError_t run_nms_batched(const float*, int, int, float, int, int, int, long long*, int*, const NmsWs&, hipStream_t, int band = 0,
                            int* band_done = nullptr);
 hipError_t run_rpn_select(const void*, const void*, long, long, float*, const RpnParams&, int, hipStream_t);
-hipError_t run_rpn_select_wide(const void*, const void*, long, long, float*, const RpnParams&, void*, hipStream_t);
-size_t rpn_wide_workspace_bytes(int T, long n_anchor);
+hipError_t run_rpn_select_wide(const void*, const void*, long, long, float*, const RpnParams&, const RpnWideWs&, hipStream_t);
 int rpn_wide_max_frames(int set);
-int* rpn_wide_done_flags(void* wws, int T);
 hipError_t run_rpn_gather(const float*, const long long*, const int*, int, int, int, int, int, float*, int*, hipStream_t);
-hipError_t run_multiclass_nms(const float*, const float*, int, int, float, float, int, float*, long long*, int*, void*,
+hipError_t run_multiclass_nms(const float*, const float*, int, int, float, float, int, float*, long long*, int*, const McNmsWs&,
                               hipStream_t);
 size_t multiclass_nms_workspace_bytes(int R, int ncls);
 int multiclass_nms_max_candidates();
 hipError_t run_soft_nms(const float*, int, float, int, float, float, float*, long long*, int*, hipStream_t);
 hipError_t run_multiclass_soft_nms(const float*, const float*, int, int, int, float, float, int, float, float, int, float*, long long*, int*,
-                                   void*, hipStream_t);
-size_t multiclass_soft_nms_workspace_bytes(int P, int R, int ncls);
+                                   const McSoftNmsWs&, hipStream_t);
 hipError_t run_seq_nms(const float*, const float*, int, const int*, int, int, int, float, float, float, int, int, float*, long long*, int*, int*,
-                       int*, float*, int*, int, void*, int, hipStream_t);
-size_t seq_nms_workspace_bytes(int P, int F, int R, int ncls, int tubes);
+                       int*, float*, int*, int, const SeqNmsWs&, int, hipStream_t);
 hipError_t run_stem_fused(const float*, const void*, const float*, void*, int, int, int, int, hipStream_t);
 hipError_t run_gconv3x3(const void*, const void*, void*, const float*, int, int, int, int, int, int, int, int, int, hipStream_t);
 hipError_t run_res2_conv3x3(const void*, long, const void*, long, void*, long, const void*, const float*, int, int, int, int, int, int, int, int,
@@ -137,7 +133,6 @@ static int check_launch(hipError_t e, const char* what) {
   if (e == hipErrorInvalidValue) return fail(HVR_EUNSUPPORTED, "%s: shape outside the implemented envelope", what);
   return fail(HVR_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
 }
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline int elem_size(int dtype) { return (dtype == HVR_BF16 || dtype == HVR_F16) ? 2 : 4; }   // (split half: 4 bytes per logical element)
 static inline int kstep_elems(int dtype) { return (dtype == HVR_F32 || dtype == HVR_F16S) ? 32 : 64; }
 static inline bool valid_dtype(int dtype) { return dtype >= HVR_F32 && dtype <= HVR_F16S; }
@@ -226,46 +221,92 @@ static int gemm_params(const hvr_gemm_desc* d, GemmParams& p) {
   return 0;
 }
 
-size_t hvr_gemm_fewrow_workspace_bytes(const hvr_gemm_desc* d) {
-  GemmParams p;
-  if (gemm_params(d, p)) return 0;
-  const int s = fewrow_slices(p);
-  return s > 1 ? (size_t)s * p.M * p.N * 4 : 0;
+// ---- what runs for a product: ONE plan per entry, read by its launch and by every query about it ----
+enum Route {
+  kRouteNone = 0,    // no kernel takes the descriptor (the launch says why)
+  kRoutePanel,       // row panel (expand.hip)
+  kRoutePanelSplit,  // row panel on split-half operands (expand_split.hip)
+  kRouteConv3x3C64,  // the 64-channel 3x3 (conv3x3.hip)
+  kRouteBigTile,     // 288 x 256 tiles (bigtile.hip)
+  kRouteTwoLevel,    // tile engine, two-level accumulation (EPI_LINEAR2)
+  kRoutePc,          // producer / consumer tiles (pc_gemm.hip), pc_bn columns
+  kRouteKpar,        // few rows: K sliced across the waves of a workgroup (kpar.hip)
+  kRouteSplitK,      // few rows: `slices` K slices across workgroups + a reduce launch
+  kRouteTile,        // tile engine
+};
+struct ProductPlan {
+  GemmParams p;   // as the route's launcher takes it
+  int route;
+  int slices;     // > 1: the few-row rule offers the product this many K slices (taken when the caller hands the scratch for them)
+  int pc_bn;
+};
+static size_t fewrow_bytes(const ProductPlan& r) { return r.slices > 1 ? (size_t)r.slices * r.p.M * r.p.N * 4 : 0; }
+// The few-row step, the last before the tile engine: (a caller that hands a few-row workspace asked for the few-row forms: K sliced
+// across the waves of a workgroup where the shape allows -- no partials, one launch -- else across workgroups + a reduce launch).
+// have_ws: the size queries plan as if the scratch were there.
+static void plan_fewrow(ProductPlan& r, bool have_ws, const void* ws, size_t ws_bytes) {
+  r.slices = fewrow_slices(r.p);
+  if (r.slices > 1 && (have_ws || (ws && aligned16(ws) && ws_bytes >= fewrow_bytes(r))))
+    r.route = (fewrow_mode() == 1 && kpar_supported(r.p)) ? kRouteKpar : kRouteSplitK;
 }
 
-int hvr_gemm(const hvr_gemm_desc* d, void* stream) {
-  GemmParams p;
+static int gemm_plan(const hvr_gemm_desc* d, bool have_ws, ProductPlan& r) {
+  GemmParams& p = r.p;
   const int rc = gemm_params(d, p);
   if (rc) return rc;
+  r.route = kRouteTile; r.slices = 1; r.pc_bn = 128;
   int hint = d->tile_hint;
   if (hint == kBigForce) {
-    if (!bigtile_supported(p, true)) return fail(HVR_EUNSUPPORTED, "the big-tile kernel takes bf16 products with N %% 256 == 0 and K %% 64 == 0");
-    return check_launch(run_bigtile(p, (hipStream_t)stream), "hvr_gemm(big tile)");
+    r.route = bigtile_supported(p, true) ? kRouteBigTile : kRouteNone;
+    return 0;
   }
   if (hint == kBigHint || hint == 0) {  // the 288 x 256 shape where it applies (kBigHint: a throughput caller), else as with hint 0
     const bool thr = hint == kBigHint;
     p.tile_hint = hint = 0;
-    if (bigtile_supported(p, thr)) return check_launch(run_bigtile(p, (hipStream_t)stream), "hvr_gemm(big tile)");
+    if (bigtile_supported(p, thr)) { r.route = kRouteBigTile; return 0; }
   }
   if (d->tile_hint == kPcHint128 || d->tile_hint == kPcHint256) {
-    if (!pc_supported(p, EPI_LINEAR)) return fail(HVR_EUNSUPPORTED, "the producer / consumer tile kernel takes aligned bf16 operands with N %% 8 == 0");
-    return check_launch(run_pc(p, EPI_LINEAR, d->tile_hint == kPcHint256 ? 256 : 128, (hipStream_t)stream), "hvr_gemm (pc)");
+    r.pc_bn = d->tile_hint == kPcHint256 ? 256 : 128;
+    r.route = pc_supported(p, EPI_LINEAR) ? kRoutePc : kRouteNone;
+    return 0;
   }
   // Long-K products whose 144 x 128 tile grid is one round of the chip (fc_new_1: 4500 x 1024 x 12544 -> 256 tiles of 196
   // K-steps): the producer / consumer kernel, 1.00-1.03 PF/s against the tile engine's 0.90 (tools/pc_bench.py).  Shorter K
   // loops do not amortise its one-wave-per-SIMD compute stream's prologue; there the tile engine stays ahead.
   if (hint == 0 && d->K >= 8192 && pc_supported(p, EPI_LINEAR)) {
     const long tiles = (long)((d->M + 143) / 144) * ((d->N + 127) / 128);
-    if (tiles > 192 && tiles <= 256) return check_launch(run_pc(p, EPI_LINEAR, 128, (hipStream_t)stream), "hvr_gemm (pc)");
+    if (tiles > 192 && tiles <= 256) { r.route = kRoutePc; return 0; }
   }
-  const int slices = fewrow_slices(p);
-  if (slices > 1 && d->ws && aligned16(d->ws) && d->ws_bytes >= (size_t)slices * p.M * p.N * 4) {
-    // (a caller that hands a few-row workspace asked for the few-row forms: K sliced across the waves of a workgroup where the
-    // shape allows -- no partials, one launch -- else across workgroups + a reduce launch)
-    if (fewrow_mode() == 1 && kpar_supported(p)) return check_launch(run_kpar(p, (hipStream_t)stream), "hvr_gemm(K-parallel waves)");
-    return check_launch(run_fewrow_split(p, slices, d->ws, (hipStream_t)stream), "hvr_gemm(split-K)");
+  plan_fewrow(r, have_ws, d->ws, d->ws_bytes);
+  return 0;
+}
+
+size_t hvr_gemm_fewrow_workspace_bytes(const hvr_gemm_desc* d) {
+  ProductPlan r;
+  if (gemm_plan(d, true, r)) return 0;
+  // Query and launch disagree under kBigHint: the launch clears the hint before the few-row rule sees it and would take the few-row
+  // forms if handed a workspace; this query has always applied the rule to the caller's hint, which refuses any hint but 0.  No
+  // caller plans with it; the answer stays as it was.
+  if (d->tile_hint == kBigHint) return 0;
+  return fewrow_bytes(r);
+}
+
+int hvr_gemm(const hvr_gemm_desc* d, void* stream) {
+  ProductPlan r;
+  const int rc = gemm_plan(d, false, r);
+  if (rc) return rc;
+  const GemmParams& p = r.p;
+  hipStream_t s = (hipStream_t)stream;
+  switch (r.route) {
+    case kRouteBigTile: return check_launch(run_bigtile(p, s), "hvr_gemm(big tile)");
+    case kRoutePc: return check_launch(run_pc(p, EPI_LINEAR, r.pc_bn, s), "hvr_gemm (pc)");
+    case kRouteKpar: return check_launch(run_kpar(p, s), "hvr_gemm(K-parallel waves)");
+    case kRouteSplitK: return check_launch(run_fewrow_split(p, r.slices, d->ws, s), "hvr_gemm(split-K)");
+    case kRouteTile: return check_launch(run_tile_op(p, EPI_LINEAR, s), "hvr_gemm");
+    default:
+      if (d->tile_hint == kBigForce) return fail(HVR_EUNSUPPORTED, "the big-tile kernel takes bf16 products with N %% 256 == 0 and K %% 64 == 0");
+      return fail(HVR_EUNSUPPORTED, "the producer / consumer tile kernel takes aligned bf16 operands with N %% 8 == 0");
   }
-  return check_launch(run_tile_op(p, EPI_LINEAR, (hipStream_t)stream), "hvr_gemm");
 }
 
 // slices for a GEMM whose output has too few tiles to fill the chip and whose K loop is long (weight gradients)
@@ -373,8 +414,10 @@ static int expand_enabled() {   // HVR_EXPAND=0: the automatic choice of the row
   return on;
 }
 
-// descriptor -> kernel parameters + the path it takes (0 tile engine, 1 expand.hip); a negative return is the error
-static int conv_params(const hvr_conv_desc* d, GemmParams& p, int& path) {
+// descriptor -> kernel parameters + what runs; a negative return is the error
+static int conv_plan(const hvr_conv_desc* d, bool have_ws, ProductPlan& r) {
+  GemmParams& p = r.p;
+  r.route = kRouteTile; r.slices = 1; r.pc_bn = 0;
   if (!d) return fail(HVR_EINVAL, "null descriptor");
   const int OH = (d->H + 2 * d->pad - d->dil * (d->KH - 1) - 1) / d->stride + 1;
   const int OW = (d->W + 2 * d->pad - d->dil * (d->KW - 1) - 1) / d->stride + 1;
@@ -403,8 +446,9 @@ static int conv_params(const hvr_conv_desc* d, GemmParams& p, int& path) {
   if (pointwise) p.zero = d->zero;  // (expand.hip reads it in place of a missing shift)
   // the expand convs of a Bottleneck (1x1, K <= 256, + residual) are HBM-bound: row-panel kernel (expand.hip)
   const int use_expand = expand_enabled();
-  if (p.tile_hint == kBigForce) {
-    path = 0;
+  const int hint = d->tile_hint;
+  if (hint == kBigForce) {
+    r.route = bigtile_supported(p, true) ? kRouteBigTile : kRouteNone;
     return 0;
   }
   const bool hint0 = p.tile_hint == 0 || p.tile_hint == kBigHint;  // (the big-tile hint leaves the dedicated kernels their shapes)
@@ -417,51 +461,72 @@ static int conv_params(const hvr_conv_desc* d, GemmParams& p, int& path) {
     // batch of clips -- 60 frames: 178 - 198 against 155 - 167 us, profiles/r06_expand_ablation_raw.txt / r06_l3_fused.txt)
     if (big_first && p.resid && p.K == 256 && p.dtype != DT_F16S && p.M >= 65536 && expand_supported(p)) big_first = false;
   }
-  path = (pointwise && (expand_supported(p) || expand_split_supported(p)) &&
-          (p.tile_hint == kExpandHint || (hint0 && use_expand && p.resid && p.N >= 2 * p.K && !big_first))) ? 1 : 0;
-  if (p.tile_hint == kExpandHint) p.tile_hint = 0;
+  const bool panel = pointwise && (expand_supported(p) || expand_split_supported(p)) &&
+                     (hint == kExpandHint || (hint0 && use_expand && p.resid && p.N >= 2 * p.K && !big_first));
+  if (hint == kExpandHint) p.tile_hint = 0;
   // layer 1's 3x3 (64 -> 64): persistent kernel with the weights resident in the LDS (conv3x3.hip)
   static const int use_c3 = std::getenv("HVR_CONV3") ? std::atoi(std::getenv("HVR_CONV3")) : 1;
-  if (path == 0 && hint0 && use_c3 && conv3x3_c64_supported(p)) path = 2;
-  if (path != 0 && p.tile_hint == kBigHint) p.tile_hint = 0;
+  if (panel || (hint0 && use_c3 && conv3x3_c64_supported(p))) {
+    r.route = !panel ? kRouteConv3x3C64 : p.dtype == DT_F16S ? kRoutePanelSplit : kRoutePanel;
+    if (hint == kBigHint) p.tile_hint = 0;
+    return 0;
+  }
+  if (hint == kTwoLevelHint) {
+    // two-level accumulation (gemm_params.h: EPI_LINEAR2) where the format carries the f32 tolerance; any other format runs as with hint 0
+    p.tile_hint = 0;
+    if (two_level_supported(p)) { r.route = kRouteTwoLevel; return 0; }
+  }
+  if (hint == kBigHint || hint == 0 || hint == kTwoLevelHint) {
+    p.tile_hint = 0;
+    if (bigtile_supported(p, hint == kBigHint)) { r.route = kRouteBigTile; return 0; }
+  }
+  plan_fewrow(r, have_ws, d->ws, d->ws_bytes);
   return 0;
 }
 
+// Where query and launch disagree (no caller plans with these hints -- ResNet.stage_route uses 0 and kBigHint; the answers stay as
+// they were):
+//  - hvr_conv2d_path has always answered 0 under kBigForce and kTwoLevelHint, where the launch runs the big tiles (kBigForce: or
+//    fails) or, under kTwoLevelHint, the two-level form, else the big tiles where they apply;
+//  - hvr_conv2d_splitk_workspace_bytes has always applied the few-row rule to the caller's hint, which refuses kBigHint and
+//    kTwoLevelHint; the launch clears those hints first and would take the few-row forms if handed a workspace.
+int hvr_conv2d_path(const hvr_conv_desc* d) {
+  ProductPlan r;
+  const int rc = conv_plan(d, false, r);
+  if (rc) return rc;
+  if (d->tile_hint == kBigForce || d->tile_hint == kTwoLevelHint) return 0;
+  switch (r.route) {
+    case kRoutePanel: case kRoutePanelSplit: return 1;
+    case kRouteConv3x3C64: return 2;
+    case kRouteBigTile: return 3;
+    default: return 0;
+  }
+}
+
 size_t hvr_conv2d_splitk_workspace_bytes(const hvr_conv_desc* d) {
-  GemmParams p;
-  int path = 0;
-  if (conv_params(d, p, path)) return 0;
-  const int s = (path == 0 ? fewrow_slices(p) : 1);
-  return s > 1 ? (size_t)s * p.M * p.N * 4 : 0;
+  ProductPlan r;
+  if (conv_plan(d, true, r)) return 0;
+  if (d->tile_hint == kBigHint || d->tile_hint == kTwoLevelHint) return 0;
+  return fewrow_bytes(r);
 }
 
 int hvr_conv2d_nhwc(const hvr_conv_desc* d, void* stream) {
-  GemmParams p;
-  int path = 0;
-  const int rc = conv_params(d, p, path);
+  ProductPlan r;
+  const int rc = conv_plan(d, false, r);
   if (rc) return rc;
-  if (path == 1) return check_launch(p.dtype == DT_F16S ? run_expand_split(p, (hipStream_t)stream) : run_expand(p, (hipStream_t)stream), "hvr_conv2d_nhwc(expand)");
-  if (path == 2) return check_launch(run_conv3x3_c64(p, (hipStream_t)stream), "hvr_conv2d_nhwc(conv3x3_c64)");
-  if (path == 0 && d->tile_hint == kBigForce) {
-    if (!bigtile_supported(p, true)) return fail(HVR_EUNSUPPORTED, "the big-tile kernel takes bf16 convs with Cout %% 256 == 0 and Cin %% 64 == 0");
-    return check_launch(run_bigtile(p, (hipStream_t)stream), "hvr_conv2d_nhwc(big tile)");
+  const GemmParams& p = r.p;
+  hipStream_t s = (hipStream_t)stream;
+  switch (r.route) {
+    case kRoutePanel: return check_launch(run_expand(p, s), "hvr_conv2d_nhwc(expand)");
+    case kRoutePanelSplit: return check_launch(run_expand_split(p, s), "hvr_conv2d_nhwc(expand)");
+    case kRouteConv3x3C64: return check_launch(run_conv3x3_c64(p, s), "hvr_conv2d_nhwc(conv3x3_c64)");
+    case kRouteBigTile: return check_launch(run_bigtile(p, s), "hvr_conv2d_nhwc(big tile)");
+    case kRouteTwoLevel: return check_launch(run_tile_op(p, EPI_LINEAR2, s), "hvr_conv2d_nhwc(two-level)");
+    case kRouteKpar: return check_launch(run_kpar(p, s), "hvr_conv2d_nhwc(K-parallel waves)");
+    case kRouteSplitK: return check_launch(run_fewrow_split(p, r.slices, d->ws, s), "hvr_conv2d_nhwc(split-K)");
+    case kRouteTile: return check_launch(run_tile_op(p, EPI_LINEAR, s), "hvr_conv2d_nhwc");
+    default: return fail(HVR_EUNSUPPORTED, "the big-tile kernel takes bf16 convs with Cout %% 256 == 0 and Cin %% 64 == 0");
   }
-  if (path == 0 && d->tile_hint == kTwoLevelHint) {
-    // two-level accumulation (gemm_params.h: EPI_LINEAR2) where the format carries the f32 tolerance; any other format runs as with hint 0
-    p.tile_hint = 0;
-    if (two_level_supported(p)) return check_launch(run_tile_op(p, EPI_LINEAR2, (hipStream_t)stream), "hvr_conv2d_nhwc(two-level)");
-  }
-  if (path == 0 && (d->tile_hint == kBigHint || d->tile_hint == 0 || d->tile_hint == kTwoLevelHint)) {
-    p.tile_hint = 0;
-    if (bigtile_supported(p, d->tile_hint == kBigHint)) return check_launch(run_bigtile(p, (hipStream_t)stream), "hvr_conv2d_nhwc(big tile)");
-  }
-  const int slices = (path == 0 ? fewrow_slices(p) : 1);
-  if (slices > 1 && d->ws && aligned16(d->ws) && d->ws_bytes >= (size_t)slices * p.M * p.N * 4) {
-    if (fewrow_mode() == 1 && kpar_supported(p)) return check_launch(run_kpar(p, (hipStream_t)stream), "hvr_conv2d_nhwc(K-parallel waves)");
-    const hipError_t e = run_fewrow_split(p, slices, d->ws, (hipStream_t)stream);
-    return check_launch(e, "hvr_conv2d_nhwc(split-K)");
-  }
-  return check_launch(run_tile_op(p, EPI_LINEAR, (hipStream_t)stream), "hvr_conv2d_nhwc");
 }
 
 static int tail_params(const hvr_tail_desc* d, GemmParams& p) {
@@ -488,25 +553,30 @@ static bool tail_on_tile_engine(const GemmParams& p) {
          (long)p.M * (p.K - p.K1) * 2 < (1L << 31);
 }
 
+static int tail_route(const GemmParams& p) {
+  if (expand_supported(p)) return kRoutePanel;
+  if (!tail_on_tile_engine(p)) return kRouteNone;
+  // the 288 x 256 tiles take the second K segment too (same MFMA order: bit-identical).  Round 3 measured them slightly behind the tile
+  // engine here; with persistent workgroups (round 6) they are ahead: res5's 512 + 1024 -> 2048 tail 973 -> 857 us for four clips (230 ->
+  // 200 for one), layer 3's 256 + 512 -> 1024 311 -> 256 (72 -> 69)
+  return bigtile_supported(p, false) ? kRouteBigTile : kRouteTile;
+}
+
 int hvr_bottleneck_tail_supported(const hvr_tail_desc* d) {
   GemmParams p;
-  if (tail_params(d, p)) return 0;
-  return (expand_supported(p) || tail_on_tile_engine(p)) ? 1 : 0;
+  return !tail_params(d, p) && tail_route(p) != kRouteNone;
 }
 
 int hvr_bottleneck_tail(const hvr_tail_desc* d, void* stream) {
   GemmParams p;
   const int rc = tail_params(d, p);
   if (rc) return rc;
-  if (expand_supported(p)) return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_tail");
-  if (tail_on_tile_engine(p)) {
-    // the 288 x 256 tiles take the second K segment too (same MFMA order: bit-identical).  Round 3 measured them slightly behind the tile
-    // engine here; with persistent workgroups (round 6) they are ahead: res5's 512 + 1024 -> 2048 tail 973 -> 857 us for four clips (230 ->
-    // 200 for one), layer 3's 256 + 512 -> 1024 311 -> 256 (72 -> 69)
-    if (bigtile_supported(p, false)) return check_launch(run_bigtile(p, (hipStream_t)stream), "hvr_bottleneck_tail(big tile)");
-    return check_launch(run_tile_op(p, EPI_LINEAR, (hipStream_t)stream), "hvr_bottleneck_tail(tile engine)");
+  switch (tail_route(p)) {
+    case kRoutePanel: return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_tail");
+    case kRouteBigTile: return check_launch(run_bigtile(p, (hipStream_t)stream), "hvr_bottleneck_tail(big tile)");
+    case kRouteTile: return check_launch(run_tile_op(p, EPI_LINEAR, (hipStream_t)stream), "hvr_bottleneck_tail(tile engine)");
+    default: return fail(HVR_EUNSUPPORTED, "no fused tail kernel for C1=%d C2=%d Cout=%d", d->C1, d->C2, d->Cout);
   }
-  return fail(HVR_EUNSUPPORTED, "no fused tail kernel for C1=%d C2=%d Cout=%d", d->C1, d->C2, d->Cout);
 }
 
 // closing 1x1 (+ projection shortcut or identity residual) + the next block's reducing 1x1 (expand.hip, NX > 0)
@@ -536,20 +606,24 @@ static int tail_next_params(const hvr_tail_next_desc* d, GemmParams& p) {
   return 0;
 }
 
+static int tail_next_route(const GemmParams& p) {
+  return expand_split_next_supported(p) ? kRoutePanelSplit : expand_next_supported(p) ? kRoutePanel : kRouteNone;
+}
+
 int hvr_bottleneck_tail_next_supported(const hvr_tail_next_desc* d) {
   GemmParams p;
-  if (tail_next_params(d, p)) return 0;
-  return (expand_next_supported(p) || expand_split_next_supported(p)) ? 1 : 0;
+  return !tail_next_params(d, p) && tail_next_route(p) != kRouteNone;
 }
 
 int hvr_bottleneck_tail_next(const hvr_tail_next_desc* d, void* stream) {
   GemmParams p;
   const int rc = tail_next_params(d, p);
   if (rc) return rc;
-  if (expand_split_next_supported(p)) return check_launch(run_expand_split(p, (hipStream_t)stream), "hvr_bottleneck_tail_next(split half)");
-  if (!expand_next_supported(p))
-    return fail(HVR_EUNSUPPORTED, "no fused tail + next conv kernel for C1=%d C2=%d Cout=%d Cn=%d", d->tail.C1, d->tail.C2, d->tail.Cout, d->Cn);
-  return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_tail_next");
+  switch (tail_next_route(p)) {
+    case kRoutePanelSplit: return check_launch(run_expand_split(p, (hipStream_t)stream), "hvr_bottleneck_tail_next(split half)");
+    case kRoutePanel: return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_tail_next");
+    default: return fail(HVR_EUNSUPPORTED, "no fused tail + next conv kernel for C1=%d C2=%d Cout=%d Cn=%d", d->tail.C1, d->tail.C2, d->tail.Cout, d->Cn);
+  }
 }
 
 // the identity form with only the pixels (s oy, s ox) of y written, as a compact map (expand.hip / expand_split.hip, LIVE)
@@ -564,20 +638,25 @@ static int tail_next_live_params(const hvr_tail_next_live_desc* d, GemmParams& p
   return 0;
 }
 
+static int tail_next_live_route(const GemmParams& p) {
+  return expand_split_next_live_supported(p) ? kRoutePanelSplit : expand_next_live_supported(p) ? kRoutePanel : kRouteNone;
+}
+
 int hvr_bottleneck_tail_next_live_supported(const hvr_tail_next_live_desc* d) {
   GemmParams p;
-  if (tail_next_live_params(d, p)) return 0;
-  return (expand_next_live_supported(p) || expand_split_next_live_supported(p)) ? 1 : 0;
+  return !tail_next_live_params(d, p) && tail_next_live_route(p) != kRouteNone;
 }
 
 int hvr_bottleneck_tail_next_live(const hvr_tail_next_live_desc* d, void* stream) {
   GemmParams p;
   const int rc = tail_next_live_params(d, p);
   if (rc) return rc;
-  if (expand_split_next_live_supported(p)) return check_launch(run_expand_split(p, (hipStream_t)stream), "hvr_bottleneck_tail_next_live(split half)");
-  if (!expand_next_live_supported(p))
-    return fail(HVR_EUNSUPPORTED, "no live-store tail + next conv kernel for C1=%d Cout=%d Cn=%d dtype=%d", d->next.tail.C1, d->next.tail.Cout, d->next.Cn, d->next.tail.dtype);
-  return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_tail_next_live");
+  switch (tail_next_live_route(p)) {
+    case kRoutePanelSplit: return check_launch(run_expand_split(p, (hipStream_t)stream), "hvr_bottleneck_tail_next_live(split half)");
+    case kRoutePanel: return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_tail_next_live");
+    default:
+      return fail(HVR_EUNSUPPORTED, "no live-store tail + next conv kernel for C1=%d Cout=%d Cn=%d dtype=%d", d->next.tail.C1, d->next.tail.Cout, d->next.Cn, d->next.tail.dtype);
+  }
 }
 
 // closing 1x1 of a stage's last block on the pixels the next stage's stride-2 1x1 convs read: compact h and y, the residual sampled from the
@@ -601,22 +680,26 @@ static int close_sampled_params(const hvr_close_sampled_desc* d, GemmParams& p) 
   return 0;
 }
 
+// the row-panel kernels only, and only where hvr_conv2d_nhwc takes them for the same product at full resolution (same sums, bit for bit)
+static int close_sampled_route(const GemmParams& p) {
+  if (!expand_enabled() || p.N < 2 * p.K) return kRouteNone;
+  return expand_split_supported(p) ? kRoutePanelSplit : expand_supported(p) ? kRoutePanel : kRouteNone;
+}
+
 int hvr_bottleneck_close_sampled_supported(const hvr_close_sampled_desc* d) {
   GemmParams p;
-  if (close_sampled_params(d, p)) return 0;
-  // the row-panel kernels only, and only where hvr_conv2d_nhwc takes them for the same product at full resolution (same sums, bit for bit)
-  return (expand_enabled() && p.N >= 2 * p.K && (expand_supported(p) || expand_split_supported(p))) ? 1 : 0;
+  return !close_sampled_params(d, p) && close_sampled_route(p) != kRouteNone;
 }
 
 int hvr_bottleneck_close_sampled(const hvr_close_sampled_desc* d, void* stream) {
   GemmParams p;
   const int rc = close_sampled_params(d, p);
   if (rc) return rc;
-  if (expand_enabled() && p.N >= 2 * p.K) {
-    if (expand_split_supported(p)) return check_launch(run_expand_split(p, (hipStream_t)stream), "hvr_bottleneck_close_sampled(split half)");
-    if (expand_supported(p)) return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_close_sampled");
+  switch (close_sampled_route(p)) {
+    case kRoutePanelSplit: return check_launch(run_expand_split(p, (hipStream_t)stream), "hvr_bottleneck_close_sampled(split half)");
+    case kRoutePanel: return check_launch(run_expand(p, (hipStream_t)stream), "hvr_bottleneck_close_sampled");
+    default: return fail(HVR_EUNSUPPORTED, "no sampled-residual closing kernel for C1=%d Cout=%d dtype=%d (%d output pixels)", d->C1, d->Cout, d->dtype, p.M);
   }
-  return fail(HVR_EUNSUPPORTED, "no sampled-residual closing kernel for C1=%d Cout=%d dtype=%d (%d output pixels)", d->C1, d->Cout, d->dtype, p.M);
 }
 
 // the instance set of gconv3x3.hip (include/hvr_hip.h states it); 0 or the error
@@ -895,18 +978,6 @@ int hvr_stem3x3s2_first(const float* img, const float* w, const float* bias, voi
   return check_launch(run_stem3x3s2_first(img, w, bias, y, B, H, W, ldy, dtype, (hipStream_t)stream), "hvr_stem3x3s2_first");
 }
 
-int hvr_conv2d_path(const hvr_conv_desc* d) {
-  GemmParams p;
-  int path = 0;
-  const int rc = conv_params(d, p, path);
-  if (rc) return rc;
-  if (path == 0 && (d->tile_hint == 0 || d->tile_hint == kBigHint)) {
-    p.tile_hint = 0;
-    if (bigtile_supported(p, d->tile_hint == kBigHint)) return 3;
-  }
-  return path;
-}
-
 int hvr_im2col_stem(const float* img, void* cols, int B, int H, int W, int KP, int dtype, void* stream) {
   if (!img || !cols || B <= 0) return fail(HVR_EINVAL, "bad stem arguments");
   if (dtype == HVR_F16S && (KP % 32 || !aligned128(cols))) return fail(HVR_EINVAL, "split-half patch rows: KP %% 32 == 0, 128-byte aligned");
@@ -1054,12 +1125,41 @@ static int relation_split_tail(void* P, void* Vt, float* mstat, float* lstat, co
   return check_launch(run_tile_op(p, EPI_APPLY, s), "relation: apply (split half)");
 }
 
-size_t hvr_relation_workspace_bytes(int Mq, int Mk, int D, int dtype) {
+// P~ [Mq][ldp], V^T [D][ldp], the block maxima and sums [Mq][ntile] and, with apply_slices(...) > 1, the slices' f32 partial outputs [slices][Mq][D]
+struct RelationWs { void *P, *Vt; float *mstat, *lstat, *partial; size_t bytes; };
+static RelationWs relation_ws(void* base, int Mq, int Mk, int D, int dtype) {
   const long ldp = rel_ldp(Mk), nt = ldp / 128;
   const size_t es = elem_size(dtype);
   const int slices = apply_slices(Mq, Mk, D);
-  return align256((size_t)Mq * ldp * es) + align256((size_t)D * ldp * es) + 2 * align256((size_t)Mq * nt * 4) +
-         (slices > 1 ? align256((size_t)slices * Mq * D * 4) : 0);
+  Carver c(base);
+  RelationWs L;
+  L.P = c.take<char>((size_t)Mq * ldp * es);
+  L.Vt = c.take<char>((size_t)D * ldp * es);
+  L.mstat = c.take<float>((size_t)Mq * nt);
+  L.lstat = c.take<float>((size_t)Mq * nt);
+  L.partial = c.take<float>(slices > 1 ? (size_t)slices * Mq * D : 0);
+  L.bytes = c.off;
+  return L;
+}
+
+size_t hvr_relation_workspace_bytes(int Mq, int Mk, int D, int dtype) { return relation_ws(nullptr, Mq, Mk, D, dtype).bytes; }
+
+// one group's score tiles on the persistent big-tile kernel (relation_bt.hip); `groups` > 1: group g's operands gs_* elements behind
+// group 0's, its workspace `per` bytes behind
+static ScoresBTParams scores_bt_params(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const RelationWs& w, int Mq,
+                                       int Mk, int D, float scale, int dtype, int groups = 1, int64_t gsq = 0, int64_t gsk = 0, int64_t gsv = 0,
+                                       size_t per = 0, int int_max = 0) {
+  const long ldp = rel_ldp(Mk);
+  const long es = elem_size(dtype);
+  ScoresBTParams b;
+  b.Q = (const bf16_t*)Q; b.K = (const bf16_t*)K; b.P = (bf16_t*)w.P; b.mstat = w.mstat; b.lstat = w.lstat;
+  b.V = (const bf16_t*)V; b.Vt = (bf16_t*)w.Vt; b.Mq = Mq; b.Mk = Mk; b.D = D; b.ntile = (int)(ldp / 128);
+  b.ldq = ldq; b.ldk = ldk; b.ldv = ldv; b.ldp = ldp; b.sl2 = scale * 1.4426950408889634f;
+  b.f16 = dtype == HVR_F16S ? 2 : dtype == HVR_F16;
+  b.groups = groups; b.gs_q = gsq; b.gs_k = gsk; b.gs_v = gsv;
+  b.gs_p = b.gs_vt = (long)(per / es); b.gs_stat = (long)(per / 4);
+  b.int_max = int_max;
+  return b;
 }
 
 int hvr_relation_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, void* O,
@@ -1072,13 +1172,9 @@ int hvr_relation_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
     return fail(HVR_EWORKSPACE, "relation workspace %zu < %zu", ws_bytes, hvr_relation_workspace_bytes(Mq, Mk, D, dtype));
   const long ldp = rel_ldp(Mk);
   const int nt = (int)(ldp / 128);
-  const size_t es = elem_size(dtype);
-  char* w = (char*)ws;
-  void* P = w;                w += align256((size_t)Mq * ldp * es);
-  void* Vt = w;               w += align256((size_t)D * ldp * es);
-  float* mstat = (float*)w;   w += align256((size_t)Mq * nt * 4);
-  float* lstat = (float*)w;   w += align256((size_t)Mq * nt * 4);
-  float* partial = (float*)w;  // apply_slices(...) > 1: the slices' f32 partial outputs
+  const RelationWs L = relation_ws(ws, Mq, Mk, D, dtype);
+  void *P = L.P, *Vt = L.Vt;
+  float *mstat = L.mstat, *lstat = L.lstat, *partial = L.partial;
   hipStream_t s = (hipStream_t)stream;
 
   GemmParams p;
@@ -1091,12 +1187,7 @@ int hvr_relation_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
     if (split_normalizes(Mq) && (rc = normalize_blocks_ok(Mk, "split-half relation"))) return rc;
     const bool bt = staging && scores_bt_supported(Mq, Mk, D, ldq, ldk, ldv, ldp, Q, K, V, P, Vt, 1, true);
     if (bt) {   // (V^T is written by the same launch)
-      ScoresBTParams b;
-      b.Q = (const bf16_t*)Q; b.K = (const bf16_t*)K; b.P = (bf16_t*)P; b.mstat = mstat; b.lstat = lstat;
-      b.V = (const bf16_t*)V; b.Vt = (bf16_t*)Vt; b.Mq = Mq; b.Mk = Mk; b.D = D; b.ntile = nt;
-      b.ldq = ldq; b.ldk = ldk; b.ldv = ldv; b.ldp = ldp; b.sl2 = scale * 1.4426950408889634f; b.f16 = 2;
-      b.groups = 1; b.gs_q = b.gs_k = b.gs_v = b.gs_p = b.gs_vt = b.gs_stat = 0; b.int_max = 0;
-      rc = check_launch(run_scores_bt(b, s), "relation: scores (split half, big tile)");
+      rc = check_launch(run_scores_bt(scores_bt_params(Q, ldq, K, ldk, V, ldv, L, Mq, Mk, D, scale, dtype), s), "relation: scores (split half, big tile)");
     } else {
       rc = fill_linear(p, Q, K, P, Mq, (Mk + 3) / 4 * 4, D, ldq, ldk, ldp, dtype, staging);
       if (rc) return rc;
@@ -1116,12 +1207,7 @@ int hvr_relation_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
   const bool bt = two_byte && staging && scores_bt_supported(Mq, Mk, D, ldq, ldk, ldv, ldp, Q, K, V, P, Vt);
   if (bt) {
     // window-sized problems: one 336 x 256 score tile per CU, V^T written by the same launch (relation_bt.hip)
-    ScoresBTParams b;
-    b.Q = (const bf16_t*)Q; b.K = (const bf16_t*)K; b.P = (bf16_t*)P; b.mstat = mstat; b.lstat = lstat;
-    b.V = (const bf16_t*)V; b.Vt = (bf16_t*)Vt; b.Mq = Mq; b.Mk = Mk; b.D = D; b.ntile = nt;
-    b.ldq = ldq; b.ldk = ldk; b.ldv = ldv; b.ldp = ldp; b.sl2 = scale * 1.4426950408889634f; b.f16 = dtype == HVR_F16;
-    b.groups = 1; b.gs_q = b.gs_k = b.gs_v = b.gs_p = b.gs_vt = b.gs_stat = 0; b.int_max = 0;
-    rc = check_launch(run_scores_bt(b, s), "relation: scores (big tile)");
+    rc = check_launch(run_scores_bt(scores_bt_params(Q, ldq, K, ldk, V, ldv, L, Mq, Mk, D, scale, dtype), s), "relation: scores (big tile)");
     if (rc) return rc;
   } else {
     // few query rows (the key stage, 300 x 4 500: 108 score tiles on 256 CUs): V^T is written by workgroups of the SCORES launch that sit
@@ -1181,12 +1267,9 @@ int hvr_relation_fwd_grouped(const void* Q, int64_t ldq, int64_t gsq, const void
   const int nt = (int)(ldp / 128);
   const bool two_byte = dtype == HVR_BF16 || dtype == HVR_F16;
   // group 0's workspace laid out as hvr_relation_fwd lays out its own; group g's `per` bytes further
-  char* w = (char*)ws;
-  void* P = w;                w += align256((size_t)Mq * ldp * es);
-  void* Vt = w;               w += align256((size_t)D * ldp * es);
-  float* mstat = (float*)w;   w += align256((size_t)Mq * nt * 4);
-  float* lstat = (float*)w;   w += align256((size_t)Mq * nt * 4);
-  float* partial = (float*)w;
+  const RelationWs L = relation_ws(ws, Mq, Mk, D, dtype);
+  void *P = L.P, *Vt = L.Vt;
+  float *mstat = L.mstat, *lstat = L.lstat, *partial = L.partial;
   const bool split = dtype == HVR_F16S;
   const bool strides_ok = split ? (gsq % 32 == 0 && gsk % 32 == 0 && gsv % 32 == 0 && gso % 32 == 0)
                                 : (two_byte && gsq % 8 == 0 && gsk % 8 == 0 && gsv % 8 == 0 && gso % 8 == 0);
@@ -1277,12 +1360,7 @@ int hvr_relation_fwd_grouped(const void* Q, int64_t ldq, int64_t gsq, const void
   // exact: every group's result is hvr_relation_fwd's bit for bit (one scores launch over all groups, its arithmetic per tile
   // unchanged; the apply pass per group) -- what the batched head's equality tests run
   const bool bt_apply = !exact && mode >= 2 && (two_byte || split) && apply_bt_supported(Mq, Mk, D, ldp, ldo, P, Vt, O, groups, split);
-  ScoresBTParams b;
-  b.Q = (const bf16_t*)Q; b.K = (const bf16_t*)K; b.P = (bf16_t*)P; b.mstat = mstat; b.lstat = lstat;
-  b.V = (const bf16_t*)V; b.Vt = (bf16_t*)Vt; b.Mq = Mq; b.Mk = Mk; b.D = D; b.ntile = nt;
-  b.ldq = ldq; b.ldk = ldk; b.ldv = ldv; b.ldp = ldp; b.sl2 = scale * 1.4426950408889634f; b.f16 = split ? 2 : dtype == HVR_F16;
-  b.groups = groups; b.gs_q = gsq; b.gs_k = gsk; b.gs_v = gsv; b.gs_p = (long)(per / es); b.gs_vt = (long)(per / es); b.gs_stat = (long)(per / 4);
-  b.int_max = bt_apply ? 1 : 0;
+  const ScoresBTParams b = scores_bt_params(Q, ldq, K, ldk, V, ldv, L, Mq, Mk, D, scale, dtype, groups, gsq, gsk, gsv, per, bt_apply ? 1 : 0);
   int rc = check_launch(run_scores_bt(b, s), "relation (grouped): scores");
   if (rc) return rc;
   if (bt_apply) {
@@ -1293,27 +1371,30 @@ int hvr_relation_fwd_grouped(const void* Q, int64_t ldq, int64_t gsq, const void
     return check_launch(run_apply_bt(a, s), "relation (grouped): apply");
   }
   for (int g = 0; g < groups; ++g) {
-    char* wg = (char*)ws + (size_t)g * per;
+    const RelationWs G = relation_ws((char*)ws + (size_t)g * per, Mq, Mk, D, dtype);
     if (split) {   // one persistent scores launch over all groups (V^T included); the normalising sweep and the product per group
-      rc = relation_split_tail(wg + ((char*)P - (char*)ws), wg + ((char*)Vt - (char*)ws), (float*)(wg + ((char*)mstat - (char*)ws)),
-                               (float*)(wg + ((char*)lstat - (char*)ws)), nullptr, ldv,
-                               (char*)O + (size_t)g * gso * es, ldo, Mq, Mk, D, ldp, nt, staging, s);
+      rc = relation_split_tail(G.P, G.Vt, G.mstat, G.lstat, nullptr, ldv, (char*)O + (size_t)g * gso * es, ldo, Mq, Mk, D, ldp, nt, staging, s);
       if (rc) return rc;
       continue;
     }
-    rc = relation_apply_pass(wg + ((char*)P - (char*)ws), wg + ((char*)Vt - (char*)ws), (float*)(wg + ((char*)mstat - (char*)ws)),
-                             (float*)(wg + ((char*)lstat - (char*)ws)), (float*)(wg + ((char*)partial - (char*)ws)),
-                             (char*)O + (size_t)g * gso * es, ldo, Mq, Mk, D, ldp, nt, dtype, staging, s);
+    rc = relation_apply_pass(G.P, G.Vt, G.mstat, G.lstat, G.partial, (char*)O + (size_t)g * gso * es, ldo, Mq, Mk, D, ldp, nt, dtype, staging, s);
     if (rc) return rc;
   }
   return HVR_OK;
 }
 
 // ---- relation backward (attention backward of one stage) ----
-size_t hvr_relation_probs_workspace_bytes(int Mq, int Mk) {
+struct RelationProbsWs { float *mstat, *lstat; size_t bytes; };   // [Mq][ntile] each
+static RelationProbsWs relation_probs_ws(void* base, int Mq, int Mk) {
   const long nt = rel_ldp(Mk) / 128;
-  return 2 * align256((size_t)Mq * nt * 4);
+  Carver c(base);
+  RelationProbsWs L;
+  L.mstat = c.take<float>((size_t)Mq * nt);
+  L.lstat = c.take<float>((size_t)Mq * nt);
+  L.bytes = c.off;
+  return L;
 }
+size_t hvr_relation_probs_workspace_bytes(int Mq, int Mk) { return relation_probs_ws(nullptr, Mq, Mk).bytes; }
 
 int hvr_relation_probs(const void* Q, int64_t ldq, const void* K, int64_t ldk, void* P, int64_t ldp, int Mq, int Mk, int D,
                        float scale, int dtype, int staging, void* ws, size_t ws_bytes, void* stream) {
@@ -1324,8 +1405,8 @@ int hvr_relation_probs(const void* Q, int64_t ldq, const void* K, int64_t ldk, v
   if (int rc = normalize_blocks_ok(Mk, "relation probs")) return rc;
   if (ws_bytes < hvr_relation_probs_workspace_bytes(Mq, Mk)) return fail(HVR_EWORKSPACE, "relation probs workspace too small");
   const int nt = (int)(ldp / 128);
-  float* mstat = (float*)ws;
-  float* lstat = (float*)((char*)ws + align256((size_t)Mq * nt * 4));
+  const RelationProbsWs L = relation_probs_ws(ws, Mq, Mk);
+  float *mstat = L.mstat, *lstat = L.lstat;
   hipStream_t s = (hipStream_t)stream;
   GemmParams p;
   int rc = fill_linear(p, Q, K, P, Mq, (Mk + 3) / 4 * 4, D, ldq, ldk, ldp, dtype, staging);
@@ -1680,7 +1761,7 @@ int hvr_deform_roi_pool_fwd(const void* feat, const float* rois, const float* tr
 }
 
 // ---- NMS ----
-size_t hvr_nms_workspace_bytes(int n) { return nms_workspace_bytes(1, n) + 256; }
+size_t hvr_nms_workspace_bytes(int n) { return nms_ws(nullptr, 1, n).bytes + 256; }
 
 int hvr_nms(const float* dets, int n, float thr, int ge_semantics, int64_t* keep, int32_t* n_keep, void* ws,
             size_t ws_bytes, void* stream) {
@@ -1692,7 +1773,7 @@ int hvr_nms(const float* dets, int n, float thr, int ge_semantics, int64_t* keep
   if (!dets || !keep || !ws) return fail(HVR_EINVAL, "null pointer");
   if (n < 0 || n > 8192) return fail(HVR_EUNSUPPORTED, "hvr_nms supports 0 <= n <= 8192, got %d", n);
   if (ws_bytes < hvr_nms_workspace_bytes(n)) return fail(HVR_EWORKSPACE, "nms workspace too small");
-  return check_launch(run_nms_batched(dets, 1, n, thr, ge_semantics, 0, 0, (long long*)keep, n_keep, ws, (hipStream_t)stream),
+  return check_launch(run_nms_batched(dets, 1, n, thr, ge_semantics, 0, 0, (long long*)keep, n_keep, nms_ws(ws, 1, n), (hipStream_t)stream),
                       "hvr_nms");
 }
 
@@ -1707,7 +1788,7 @@ int hvr_nms_first(const float* dets, int n, float thr, int ge_semantics, int max
   if (!dets || !keep || !ws) return fail(HVR_EINVAL, "null pointer");
   if (n < 0 || n > 8192) return fail(HVR_EUNSUPPORTED, "hvr_nms_first supports 0 <= n <= 8192, got %d", n);
   if (ws_bytes < hvr_nms_workspace_bytes(n)) return fail(HVR_EWORKSPACE, "nms workspace too small");
-  return check_launch(run_nms_batched(dets, 1, n, thr, ge_semantics, 0, max_keep, (long long*)keep, n_keep, ws, (hipStream_t)stream),
+  return check_launch(run_nms_batched(dets, 1, n, thr, ge_semantics, 0, max_keep, (long long*)keep, n_keep, nms_ws(ws, 1, n), (hipStream_t)stream),
                       "hvr_nms_first");
 }
 
@@ -1717,10 +1798,24 @@ static inline int rpn_npre(int H, int W, int A, int nms_pre) {
   return (nms_pre > 0 && n > nms_pre) ? nms_pre : (int)n;
 }
 
+// props [T][npre][5], keep [T][npre], n_keep [T], the NMS's buffers, the chip-wide select's (few frames)
+struct RpnWs { float* props; long long* keep; int* n_keep; NmsWs nms; RpnWideWs wide; size_t bytes; };
+static RpnWs rpn_ws(void* base, int T, int npre, long n_anchor) {
+  Carver c(base);
+  RpnWs L;
+  L.props = c.take<float>((size_t)T * npre * 5);
+  L.keep = c.take<long long>((size_t)T * npre);
+  L.n_keep = c.take<int>((size_t)T);
+  L.nms = nms_ws(c.here(), T, npre);
+  c.skip(L.nms.bytes);
+  L.wide = rpn_wide_ws(c.here(), T, n_anchor);
+  c.skip(L.wide.bytes + 256);
+  L.bytes = c.off;
+  return L;
+}
+
 size_t hvr_rpn_workspace_bytes(int T, int H, int W, int A, int nms_pre) {
-  const int npre = rpn_npre(H, W, A, nms_pre);
-  return align256((size_t)T * npre * 5 * 4) + align256((size_t)T * npre * 8) + align256((size_t)T * 4) +
-         nms_workspace_bytes(T, npre) + rpn_wide_workspace_bytes(T, (long)H * W * A) + 256;
+  return rpn_ws(nullptr, T, rpn_npre(H, W, A, nms_pre), (long)H * W * A).bytes;
 }
 
 int hvr_rpn_wide_frames(int frames) { return rpn_wide_max_frames(frames); }
@@ -1747,27 +1842,23 @@ int hvr_rpn_proposals(const hvr_rpn_desc* d, void* ws, size_t ws_bytes, void* st
   rp.max_ratio = std::fabs(std::log(d->wh_ratio_clip));
   for (int a = 0; a < d->A; ++a)
     for (int i = 0; i < 4; ++i) rp.base[a][i] = d->base_anchors[a * 4 + i];
-  char* w = (char*)ws;
-  float* props = (float*)w;          w += align256((size_t)d->T * npre * 5 * 4);
-  long long* keep = (long long*)w;   w += align256((size_t)d->T * npre * 8);
-  int* n_keep = (int*)w;             w += align256((size_t)d->T * 4);
+  const RpnWs L = rpn_ws(ws, d->T, npre, n_anchor);
   hipStream_t s = (hipStream_t)stream;
   const int presorted = n_anchor > npre ? 1 : 0;
   // few frames (stream mode: one): the chip-wide kernels -- the same proposals, bit for bit (nms.hip, "the chip-wide form")
   const bool wide = presorted && d->T <= rpn_wide_max_frames(-1) && d->nms_post > 0 && d->nms_post <= 1024;
-  void* wws = w + nms_workspace_bytes(d->T, npre);
   int rc;
   if (wide)
-    rc = check_launch(run_rpn_select_wide(d->cls, d->reg, (long)d->H * d->W * rp.cls_pitch, (long)d->H * d->W * rp.reg_pitch, props, rp, wws, s), "rpn: select (chip-wide)");
+    rc = check_launch(run_rpn_select_wide(d->cls, d->reg, (long)d->H * d->W * rp.cls_pitch, (long)d->H * d->W * rp.reg_pitch, L.props, rp, L.wide, s), "rpn: select (chip-wide)");
   else
-    rc = check_launch(run_rpn_select(d->cls, d->reg, (long)d->H * d->W * rp.cls_pitch, (long)d->H * d->W * rp.reg_pitch, props, rp, HVR_F32, s), "rpn: select");
+    rc = check_launch(run_rpn_select(d->cls, d->reg, (long)d->H * d->W * rp.cls_pitch, (long)d->H * d->W * rp.reg_pitch, L.props, rp, HVR_F32, s), "rpn: select");
   if (rc) return rc;
   // with score-sorted input the first nms_post survivors are known after nms_post keeps
-  rc = check_launch(run_nms_batched(props, d->T, npre, d->nms_thr, 1, presorted, presorted ? d->nms_post : 0, keep, n_keep, w, s,
-                                    wide ? 4096 : 0, wide ? rpn_wide_done_flags(wws, d->T) : nullptr),
+  rc = check_launch(run_nms_batched(L.props, d->T, npre, d->nms_thr, 1, presorted, presorted ? d->nms_post : 0, L.keep, L.n_keep, L.nms, s,
+                                    wide ? 4096 : 0, wide ? L.wide.done : nullptr),
                     "rpn: nms");
   if (rc) return rc;
-  return check_launch(run_rpn_gather(props, keep, n_keep, d->T, npre, d->nms_post, d->max_num, presorted, d->proposals, d->counts, s),
+  return check_launch(run_rpn_gather(L.props, L.keep, L.n_keep, d->T, npre, d->nms_post, d->max_num, presorted, d->proposals, d->counts, s),
                       "rpn: gather");
 }
 
@@ -1815,10 +1906,26 @@ static inline int ga_npre(int H, int W, int nms_pre) {
   return (nms_pre > 0 && n > nms_pre) ? nms_pre : (int)n;
 }
 
+// props [T][npre][5], keep [T][npre], n_keep / ncand / topk [T] each, pix [T][npre], the NMS's buffers
+struct GaRpnWs { float* props; long long* keep; int *n_keep, *ncand, *topk, *pix; NmsWs nms; size_t bytes; };
+static GaRpnWs ga_rpn_ws(void* base, int T, int npre) {
+  Carver c(base);
+  GaRpnWs L;
+  L.props = c.take<float>((size_t)T * npre * 5);
+  L.keep = c.take<long long>((size_t)T * npre);
+  L.n_keep = c.take<int>((size_t)T);
+  L.ncand = c.take<int>((size_t)T);
+  L.topk = c.take<int>((size_t)T);
+  L.pix = c.take<int>((size_t)T * npre);
+  L.nms = nms_ws(c.here(), T, npre);
+  c.skip(L.nms.bytes + 256);
+  L.bytes = c.off;
+  return L;
+}
+
 size_t hvr_ga_rpn_workspace_bytes(int T, int H, int W, int nms_pre) {
   if (T <= 0 || H <= 0 || W <= 0 || (long)H * W > 8192) return 0;
-  const int npre = ga_npre(H, W, nms_pre);
-  return align256((size_t)T * npre * 5 * 4) + align256((size_t)T * npre * 8) + align256((size_t)T * npre * 4) + 3 * align256((size_t)T * 4) + nms_workspace_bytes(T, npre) + 256;
+  return ga_rpn_ws(nullptr, T, ga_npre(H, W, nms_pre)).bytes;
 }
 
 int hvr_ga_rpn_proposals(const hvr_ga_rpn_desc* d, void* ws, size_t ws_bytes, void* stream) {
@@ -1852,21 +1959,15 @@ int hvr_ga_rpn_proposals(const hvr_ga_rpn_desc* d, void* ws, size_t ws_bytes, vo
   gp.t_ratio = std::fabs(std::log(d->wh_ratio_clip));
   gp.img_h = d->img_h; gp.img_w = d->img_w;
   const int npre = gp.npre;
-  char* w = (char*)ws;
-  float* props = (float*)w;          w += align256((size_t)d->T * npre * 5 * 4);
-  long long* keep = (long long*)w;   w += align256((size_t)d->T * npre * 8);
-  int* n_keep = (int*)w;             w += align256((size_t)d->T * 4);
-  int* ncand = (int*)w;              w += align256((size_t)d->T * 4);
-  int* topk = (int*)w;               w += align256((size_t)d->T * 4);
-  int* pix = (int*)w;                w += align256((size_t)d->T * npre * 4);
+  const GaRpnWs L = ga_rpn_ws(ws, d->T, npre);
   hipStream_t s = (hipStream_t)stream;
-  int rc = check_launch(run_ga_select(d->cls, d->reg, d->shape, d->keep, props, pix, ncand, topk, gp, s), "ga rpn: select");
+  int rc = check_launch(run_ga_select(d->cls, d->reg, d->shape, d->keep, L.props, L.pix, L.ncand, L.topk, gp, s), "ga rpn: select");
   if (rc) return rc;
   // Every survivor is needed: whether a frame's "first nms_post" are the first in score order (its top nms_pre were taken) or in
   // row-major order (they were not) depends on its kept count, which only the device knows -- no cap on the NMS.
-  rc = check_launch(run_nms_batched(props, d->T, npre, d->nms_thr, 1, 1, 0, keep, n_keep, w, s), "ga rpn: nms");
+  rc = check_launch(run_nms_batched(L.props, d->T, npre, d->nms_thr, 1, 1, 0, L.keep, L.n_keep, L.nms, s), "ga rpn: nms");
   if (rc) return rc;
-  return check_launch(run_ga_gather(props, keep, n_keep, pix, ncand, topk, d->T, npre, d->nms_post, d->max_num, d->proposals, d->counts, s),
+  return check_launch(run_ga_gather(L.props, L.keep, L.n_keep, L.pix, L.ncand, L.topk, d->T, npre, d->nms_post, d->max_num, d->proposals, d->counts, s),
                       "ga rpn: gather");
 }
 
@@ -1900,7 +2001,7 @@ int hvr_multiclass_nms(const float* boxes, const float* scores, int R, int ncls,
   if (!boxes || !scores || !dets || !labels || !ws) return fail(HVR_EINVAL, "null pointer");
   if (ws_bytes < hvr_multiclass_nms_workspace_bytes(R, ncls)) return fail(HVR_EWORKSPACE, "multiclass nms workspace too small");
   return check_launch(run_multiclass_nms(boxes, scores, R, ncls, score_thr, iou_thr, max_num, dets, (long long*)labels, n_out,
-                                         ws, (hipStream_t)stream),
+                                         mc_nms_ws(ws, R, ncls), (hipStream_t)stream),
                       "hvr_multiclass_nms");
 }
 
@@ -1924,7 +2025,7 @@ int hvr_soft_nms(const float* dets, int n, float iou_thr, int method, float sigm
 }
 
 size_t hvr_multiclass_soft_nms_workspace_bytes(int P, int R, int ncls) {
-  return multiclass_soft_nms_workspace_bytes(P > 0 ? P : 1, R > 0 ? R : 1, ncls > 1 ? ncls : 2);
+  return mc_soft_nms_ws(nullptr, P > 0 ? P : 1, R > 0 ? R : 1, ncls > 1 ? ncls : 2).bytes;
 }
 
 int hvr_multiclass_soft_nms(const float* boxes, const float* scores, int P, int R, int ncls, float score_thr, float iou_thr, int method,
@@ -1943,17 +2044,17 @@ int hvr_multiclass_soft_nms(const float* boxes, const float* scores, int P, int 
   if (max_num <= 0) return fail(HVR_EINVAL, "hvr_multiclass_soft_nms needs max_num > 0");
   if (ws_bytes < hvr_multiclass_soft_nms_workspace_bytes(P, R, ncls)) return fail(HVR_EWORKSPACE, "multiclass soft nms workspace too small");
   return check_launch(run_multiclass_soft_nms(boxes, scores, P, R, ncls, score_thr, iou_thr, method, sigma, min_score, max_num, dets,
-                                              (long long*)labels, n_out, ws, (hipStream_t)stream),
+                                              (long long*)labels, n_out, mc_soft_nms_ws(ws, P, R, ncls), (hipStream_t)stream),
                       "hvr_multiclass_soft_nms");
 }
 
 // ---- Seq-NMS read-out of a whole video (seqnms.hip) ----
 size_t hvr_seq_nms_workspace_bytes(int F, int R, int ncls) {
-  return seq_nms_workspace_bytes(1, F > 0 ? F : 1, R > 0 ? R : 1, ncls > 1 ? ncls : 2, 0);
+  return seq_nms_ws(nullptr, 1, F > 0 ? F : 1, R > 0 ? R : 1, ncls > 1 ? ncls : 2, false).bytes;
 }
 
 size_t hvr_seq_nms_batched_workspace_bytes(int P, int Ftot, int R, int ncls, int tubes) {
-  return seq_nms_workspace_bytes(P > 0 ? P : 1, Ftot > 0 ? Ftot : 1, R > 0 ? R : 1, ncls > 1 ? ncls : 2, tubes != 0);
+  return seq_nms_ws(nullptr, P > 0 ? P : 1, Ftot > 0 ? Ftot : 1, R > 0 ? R : 1, ncls > 1 ? ncls : 2, tubes != 0).bytes;
 }
 
 int hvr_seq_nms(const float* boxes, const float* scores, int F, int R, int ncls, float score_thr, float link_thr, float nms_thr,
@@ -1983,7 +2084,8 @@ int hvr_seq_nms_phases(const float* boxes, const float* scores, int F, int R, in
   if (!aligned16(boxes) || !aligned16(ws)) return fail(HVR_EINVAL, "hvr_seq_nms: boxes and workspace must be 16-byte aligned");
   if (ws_bytes < hvr_seq_nms_workspace_bytes(F, R, ncls)) return fail(HVR_EWORKSPACE, "seq nms workspace too small");
   return check_launch(run_seq_nms(boxes, scores, 1, nullptr, F, R, ncls, score_thr, link_thr, nms_thr, rescore == 2, max_num, dets,
-                                  (long long*)labels, n_out, nullptr, nullptr, nullptr, nullptr, 0, ws, phases, (hipStream_t)stream),
+                                  (long long*)labels, n_out, nullptr, nullptr, nullptr, nullptr, 0, seq_nms_ws(ws, 1, F, R, ncls, false), phases,
+                                  (hipStream_t)stream),
                       "hvr_seq_nms");
 }
 
@@ -2015,7 +2117,8 @@ int hvr_seq_nms_batched(const float* boxes, const float* scores, int P, const in
     return fail(HVR_EINVAL, "hvr_seq_nms_batched: boxes, workspace and the tube table must be 16-byte aligned");
   if (ws_bytes < hvr_seq_nms_batched_workspace_bytes(P, Ftot, R, ncls, want != 0)) return fail(HVR_EWORKSPACE, "seq nms workspace too small");
   return check_launch(run_seq_nms(boxes, scores, P, frame_start, Ftot, R, ncls, score_thr, link_thr, nms_thr, rescore == 2, max_num, dets,
-                                  (long long*)labels, n_out, tube_ids, tubes, tube_scores, tube_start, max_tubes, ws, 7, (hipStream_t)stream),
+                                  (long long*)labels, n_out, tube_ids, tubes, tube_scores, tube_start, max_tubes,
+                                  seq_nms_ws(ws, P, Ftot, R, ncls, want != 0), 7, (hipStream_t)stream),
                       "hvr_seq_nms_batched");
 }
 

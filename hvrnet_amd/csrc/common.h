@@ -186,6 +186,22 @@ template <typename F> inline void per_device_once(std::atomic<unsigned>& done, F
   if (slot) done.fetch_or(1u << d, std::memory_order_release);
 }
 
+// A device workspace is a run of 256-byte aligned sub-buffers.  Each layout is ONE function of (base, shape) that walks a Carver:
+// with the caller's base it hands out the typed pointers, with a null base every pointer is null and `off` is the size query.
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* b) : base((char*)b) {}
+  template <typename T> T* take(size_t count) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += align256(count * sizeof(T));
+    return p;
+  }
+  void skip(size_t bytes) { off += bytes; }   // slack the sizes have always carried (captured graphs and the workspace cache hold them)
+  void* here() const { return base ? base + off : nullptr; }   // base of a nested layout: lay it out there, then skip its bytes
+};
+
 // compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{})
 template <typename F, int... Is>
 __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) {

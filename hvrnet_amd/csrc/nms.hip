@@ -795,7 +795,7 @@ __global__ __launch_bounds__(1024) void mc_nms_merge_kernel(const float* __restr
 //   nms_band_sweep    one workgroup per frame, a pipeline of eight waves over the 64-box chunks (see the kernel); stops at
 //                     max_keep survivors.  A frame whose max_keep-th survivor lies behind box R0 is handed to
 //                     nms_greedy_kernel (skip flag clear).
-constexpr int WBINS = 4096, WSEL_THREADS = 256, WSEL_PER_WG = 1024;
+constexpr int WSEL_THREADS = 256, WSEL_PER_WG = 1024;   // (WBINS: nms_dev.h, with the workspace layout)
 
 // Histogram bin of a score key (float_key of a sigmoid: a float in [0, 1]), monotone non-decreasing in the key -- all the counting
 // sort needs.  The key's top bits alone would give [0.5, 1) eight bins (one exponent), and that is where the nms_pre best scores
@@ -1153,27 +1153,15 @@ __global__ __launch_bounds__(64 * SWEEP_WAVES) void nms_band_sweep_kernel(const 
 }
 
 // ---------------- launchers ----------------
-size_t nms_workspace_bytes(int P, int n) {
-  const size_t nb = (n + 63) / 64;
-  size_t b = 0;
-  b += ((size_t)P * n * sizeof(int) + 255) & ~(size_t)255;                    // order
-  b += ((size_t)P * n * sizeof(float4) + 255) & ~(size_t)255;                 // sorted boxes
-  b += ((size_t)P * nb * 64 * nb * sizeof(unsigned long long) + 255) & ~(size_t)255;  // mask (whole 64-box chunks: the band form)
-  return b;
-}
-
 // band > 0 (score-sorted input, a survivor cap): mask of the first `band` boxes chip-wide + a one-wave sweep per problem; the greedy
 // kernel then only runs the problems the sweep could not finish inside the band (done flags, `band_done` [P])
 hipError_t run_nms_batched(const float* dets, int P, int n, float thr, int ge, int presorted, int max_keep,
-                           long long* keep, int* n_keep, void* ws, hipStream_t s, int band, int* band_done) {
+                           long long* keep, int* n_keep, const NmsWs& ws, hipStream_t s, int band, int* band_done) {
   if (n <= 0 || P <= 0) return hipSuccess;
   if (n > 8192) return hipErrorInvalidValue;
-  char* w = (char*)ws;
-  int* order = (int*)w;
-  w += ((size_t)P * n * sizeof(int) + 255) & ~(size_t)255;
-  float4* boxes4 = (float4*)w;
-  w += ((size_t)P * n * sizeof(float4) + 255) & ~(size_t)255;
-  unsigned long long* mask = (unsigned long long*)w;
+  int* order = ws.order;
+  float4* boxes4 = ws.boxes4;
+  unsigned long long* mask = ws.mask;
   int np2 = 1;
   while (np2 < n) np2 <<= 1;
   const int nb = (n + 63) / 64;
@@ -1226,11 +1214,6 @@ hipError_t run_rpn_select(const void* cls, const void* reg, long cls_stride, lon
   return hipGetLastError();
 }
 
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t rpn_wide_workspace_bytes(int T, long n_anchor) {
-  return al256((size_t)T * WBINS * 4 * 2) + al256((size_t)T * WBINS * 4) + al256((size_t)T * 16) + al256((size_t)T * 4) +
-         al256((size_t)T * n_anchor * 8);
-}
 // calls with at most this many frames take the chip-wide kernels (HVR_RPN_WIDE=<frames>, 0 = never)
 int rpn_wide_max_frames(int set) {
   // process-wide (include/hvr_hip.h says so): an atomic, so that a thread changing it never tears a concurrent call's read; a call
@@ -1241,9 +1224,6 @@ int rpn_wide_max_frames(int set) {
   }());
   return set >= 0 ? v.exchange(set, std::memory_order_relaxed) : v.load(std::memory_order_relaxed);
 }
-int* rpn_wide_done_flags(void* wws, int T) {
-  return (int*)((char*)wws + al256((size_t)T * WBINS * 4 * 2) + al256((size_t)T * WBINS * 4) + al256((size_t)T * 16));
-}
 
 __global__ void rpn_wide_zero_kernel(int* __restrict__ p, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1251,16 +1231,10 @@ __global__ void rpn_wide_zero_kernel(int* __restrict__ p, int n) {
 }
 
 hipError_t run_rpn_select_wide(const void* cls, const void* reg, long cls_stride, long reg_stride, float* out, const RpnParams& rp,
-                               void* wws, hipStream_t s) {
+                               const RpnWideWs& ws, hipStream_t s) {
   const int T = rp.T, n = rp.n_anchor;
-  char* w = (char*)wws;
-  int* hist0 = (int*)w;                    // [T][WBINS]
-  int* gcount = hist0 + (size_t)T * WBINS; // [T][WBINS]  (zeroed with hist0)
-  w += al256((size_t)T * WBINS * 4 * 2);
-  int* binstart = (int*)w;  w += al256((size_t)T * WBINS * 4);
-  int* meta = (int*)w;      w += al256((size_t)T * 16);
-  w += al256((size_t)T * 4);               // done flags (rpn_wide_done_flags)
-  unsigned long long* cand = (unsigned long long*)w;
+  int *hist0 = ws.hist0, *gcount = ws.gcount, *binstart = ws.binstart, *meta = ws.meta;
+  unsigned long long* cand = ws.cand;
   // (a kernel, not hipMemsetAsync: a captured graph whose chain holds a memset node, replayed again behind an ordinary launch on the
   // same stream while its previous replay is still in flight, took a GPU memory fault on ROCm 7.2 -- profiles/r04_graph_memset_fault.txt)
   hipLaunchKernelGGL(rpn_wide_zero_kernel, dim3((T * WBINS * 2 + 255) / 256), dim3(256), 0, s, hist0, T * WBINS * 2);
@@ -1284,34 +1258,27 @@ hipError_t run_rpn_gather(const float* props, const long long* keep, const int* 
   return hipGetLastError();
 }
 
-// The merge kernel keeps the whole candidate list, next_pow2((ncls - 1) * R) entries of 8 bytes, in LDS: the longest list it can hold.
-// One statement of the limit for the launcher, the workspace query and the entry point's refusal (capi.hip).
-constexpr size_t MC_MERGE_LDS_CAP = 160 * 1024 - 3072;
+// The longest candidate list the merge kernels hold in LDS (nms_dev.h: mc_merge_lds) -- for the workspace query and the entry point's
+// refusal (capi.hip)
 int multiclass_nms_max_candidates() {
   int p = 1;
-  while ((size_t)p * 2 * 8 <= MC_MERGE_LDS_CAP) p <<= 1;
+  while (mc_merge_lds(2 * p, 2 * p).fits) p <<= 1;
   return p;   // 16384: 30 classes x 512 rows fit, 128 x 512 do not
 }
 
 hipError_t run_multiclass_nms(const float* boxes, const float* scores, int R, int ncls, float score_thr, float iou_thr,
-                              int max_num, float* dets, long long* labels, int* n_out, void* ws, hipStream_t s) {
+                              int max_num, float* dets, long long* labels, int* n_out, const McNmsWs& ws, hipStream_t s) {
   if (R > MC_MAX_R || ncls < 2 || ncls - 1 > 128 || R <= 0 || max_num <= 0) return hipErrorInvalidValue;
-  if ((long)(ncls - 1) * R > multiclass_nms_max_candidates()) return hipErrorInvalidValue;   // (before anything is launched)
-  unsigned char* keepflag = (unsigned char*)ws;
-  int* kcount = (int*)((char*)ws + (((size_t)(ncls - 1) * R + 255) & ~(size_t)255));
+  const McMergeLds m = mc_merge_lds((ncls - 1) * R, max_num);
+  if (!m.fits) return hipErrorInvalidValue;   // (before anything is launched)
+  unsigned char* keepflag = ws.keepflag;
+  int* kcount = ws.kcount;
   hipLaunchKernelGGL(mc_nms_class_kernel, dim3(ncls - 1), dim3(1024), 0, s, boxes, scores, R, ncls, score_thr, iou_thr, keepflag, kcount);
-  int np2 = 1;
-  while (np2 < (ncls - 1) * R) np2 <<= 1;
-  // the select stage (radix-select the max_num-th score, sort only the entries above it) needs a second LDS list of
-  // next_pow2(max_num) entries; when that does not fit beside the survivor list -- max_num close to the list length -- or can
-  // never run (max_num >= every possible survivor count) the kernel sorts the survivor list in place instead (sp2 = 0)
-  int sp2 = 1;
-  while (sp2 < max_num) sp2 <<= 1;
-  if (max_num >= (ncls - 1) * R || (size_t)np2 * 8 + (size_t)sp2 * 8 > MC_MERGE_LDS_CAP) sp2 = 0;
-  const size_t lds = (size_t)np2 * 8 + (size_t)sp2 * 8;
+  const int sp2 = m.sp2;
+  const size_t lds = m.bytes;
   static std::atomic<unsigned> attr_dev{0};   // (the attribute is per device)
   per_device_once(attr_dev, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mc_nms_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MC_MERGE_LDS_CAP);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mc_nms_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMcMergeLdsCap);
   });
   hipLaunchKernelGGL(mc_nms_merge_kernel, dim3(1), dim3(1024), lds, s, boxes, scores, R, ncls, keepflag, kcount, max_num, sp2, dets, labels, n_out);
   return hipGetLastError();
@@ -1320,7 +1287,7 @@ hipError_t run_multiclass_nms(const float* boxes, const float* scores, int R, in
 // 0 for a shape outside the envelope (R in 1 .. 512, 1 .. 128 foreground classes, a candidate list the merge kernel holds)
 size_t multiclass_nms_workspace_bytes(int R, int ncls) {
   if (R <= 0 || R > MC_MAX_R || ncls < 2 || ncls - 1 > 128 || (long)(ncls - 1) * R > multiclass_nms_max_candidates()) return 0;
-  return (((size_t)(ncls - 1) * R + 255) & ~(size_t)255) + (size_t)(ncls - 1) * sizeof(int) + 256;
+  return mc_nms_ws(nullptr, R, ncls).bytes;
 }
 
 }  // namespace hvr

@@ -210,6 +210,111 @@ __device__ __forceinline__ int mc_cut_to_max_num(uint32_t* key, uint32_t*& idx, 
   return nout;
 }
 
+// The merge kernels keep the whole candidate list, next_pow2(candidates) entries of 8 bytes, in LDS, and behind it the select stage's
+// list (radix-select the max_num-th score, sort only the entries above it) of next_pow2(max_num) entries.  When that second list does
+// not fit beside the first -- max_num close to the list length -- or can never be used (max_num >= every possible survivor count) the
+// kernel sorts the survivor list in place instead (sp2 = 0).  One statement for the greedy (nms.hip), Soft-NMS (softnms.hip) and Seq-NMS
+// (seqnms.hip) merge launchers and for the entry points' refusal of a list that does not fit (multiclass_nms_max_candidates).
+constexpr size_t kMcMergeLdsCap = 160 * 1024 - 3072;
+struct McMergeLds { int np2, sp2; size_t bytes; bool fits; };
+inline McMergeLds mc_merge_lds(int candidates, int max_num) {
+  McMergeLds m;
+  for (m.np2 = 1; m.np2 < candidates;) m.np2 <<= 1;
+  for (m.sp2 = 1; m.sp2 < max_num;) m.sp2 <<= 1;
+  if (max_num >= candidates || (size_t)m.np2 * 8 + (size_t)m.sp2 * 8 > kMcMergeLdsCap) m.sp2 = 0;
+  m.bytes = (size_t)m.np2 * 8 + (size_t)m.sp2 * 8;
+  m.fits = m.bytes <= kMcMergeLdsCap;
+  return m;
+}
+
+// ---- workspace layouts of the NMS family (common.h: Carver; a null base is the size query) ----
+// run_nms_batched, P problems of n boxes: the score order, the sorted boxes, the mask (whole 64-box chunks: the band form)
+struct NmsWs { int* order; float4* boxes4; unsigned long long* mask; size_t bytes; };
+inline NmsWs nms_ws(void* base, int P, int n) {
+  Carver c(base);
+  NmsWs L;
+  const size_t nb = (n + 63) / 64;
+  L.order = c.take<int>((size_t)P * n);
+  L.boxes4 = c.take<float4>((size_t)P * n);
+  L.mask = c.take<unsigned long long>((size_t)P * nb * 64 * nb);
+  L.bytes = c.off;
+  return L;
+}
+
+// run_rpn_select_wide, T frames of n_anchor anchors: hist0 and gcount [T][WBINS] each in one buffer (zeroed together), binstart [T][WBINS],
+// meta [T][4], done [T] (the band sweep's flags: run_nms_batched's band_done), cand [T][n_anchor]
+constexpr int WBINS = 4096;   // score bins
+struct RpnWideWs { int *hist0, *gcount, *binstart, *meta, *done; unsigned long long* cand; size_t bytes; };
+inline RpnWideWs rpn_wide_ws(void* base, int T, long n_anchor) {
+  Carver c(base);
+  RpnWideWs L;
+  L.hist0 = c.take<int>((size_t)T * WBINS * 2);
+  L.gcount = L.hist0 ? L.hist0 + (size_t)T * WBINS : nullptr;
+  L.binstart = c.take<int>((size_t)T * WBINS);
+  L.meta = c.take<int>((size_t)T * 4);
+  L.done = c.take<int>((size_t)T);
+  L.cand = c.take<unsigned long long>((size_t)T * n_anchor);
+  L.bytes = c.off;
+  return L;
+}
+
+// run_multiclass_nms: keepflag [ncls - 1][R], kcount [ncls - 1] (the last buffer: counted unrounded, with 256 bytes of slack behind it)
+struct McNmsWs { unsigned char* keepflag; int* kcount; size_t bytes; };
+inline McNmsWs mc_nms_ws(void* base, int R, int ncls) {
+  Carver c(base);
+  McNmsWs L;
+  L.keepflag = c.take<unsigned char>((size_t)(ncls - 1) * R);
+  L.kcount = c.take<int>(0);
+  c.skip((size_t)(ncls - 1) * sizeof(int) + 256);
+  L.bytes = c.off;
+  return L;
+}
+
+// run_multiclass_soft_nms, P problems: sel_scores and sel_rows [P][ncls - 1][R], counts [P][ncls - 1]
+struct McSoftNmsWs { float* sel_scores; int *sel_rows, *counts; size_t bytes; };
+inline McSoftNmsWs mc_soft_nms_ws(void* base, int P, int R, int ncls) {
+  Carver c(base);
+  McSoftNmsWs L;
+  const size_t e = (size_t)P * (ncls - 1) * R;
+  L.sel_scores = c.take<float>(e);
+  L.sel_rows = c.take<int>(e);
+  L.counts = c.take<int>((size_t)P * (ncls - 1));
+  c.skip(256);
+  L.bytes = c.off;
+  return L;
+}
+
+// run_seq_nms, F frames in all, W = ceil(R / 64) words per row of boxes: link and ovl [F][R][W]; best, osc and next [ncls - 1][F][R]; alive,
+// keep and wmax [ncls - 1][F][W]; with tubes (else null) the per-box (round, length) table [ncls - 1][F][R], the per-(problem, class) round
+// counts and their prefix [P][ncls - 1]
+struct SeqNmsWs {
+  unsigned long long *link, *ovl, *alive, *keep, *wmax;
+  float *best, *osc;
+  short* next;
+  int2* tube;
+  int *tcount, *cbase;
+  size_t bytes;
+};
+inline SeqNmsWs seq_nms_ws(void* base, int P, int F, int R, int ncls, bool tubes) {
+  Carver c(base);
+  SeqNmsWs L;
+  const size_t W = (size_t)(R + 63) / 64, g = (size_t)ncls - 1, f = (size_t)F, r = (size_t)R;
+  L.link = c.take<unsigned long long>(f * r * W);
+  L.ovl = c.take<unsigned long long>(f * r * W);
+  L.best = c.take<float>(g * f * r);
+  L.osc = c.take<float>(g * f * r);
+  L.next = c.take<short>(g * f * r);
+  L.alive = c.take<unsigned long long>(g * f * W);
+  L.keep = c.take<unsigned long long>(g * f * W);
+  L.wmax = c.take<unsigned long long>(g * f * W);
+  c.skip(256);   // (slack behind the path kernel's buffers, part of the size since before the tube tables came behind it)
+  L.tube = tubes ? c.take<int2>(g * f * r) : nullptr;
+  L.tcount = tubes ? c.take<int>((size_t)P * g) : nullptr;
+  L.cbase = tubes ? c.take<int>((size_t)P * g) : nullptr;
+  L.bytes = c.off;
+  return L;
+}
+
 __device__ __forceinline__ float box_iou_plus1(const float4 a, const float4 b) {
   // nms_cpu.cpp:18,46-54 (same arithmetic order; "+1" pixel convention)
   const float xx1 = fmaxf(a.x, b.x), yy1 = fmaxf(a.y, b.y), xx2 = fminf(a.z, b.z), yy2 = fminf(a.w, b.w);

@@ -353,53 +353,29 @@ __global__ __launch_bounds__(1024) void seq_nms_merge_kernel(const float* __rest
 }
 
 // ---------------- launchers ----------------
-static size_t sq_al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// tubes: the per-box (round, length) table, the per-(problem, class) round counts and their prefix
-size_t seq_nms_workspace_bytes(int P, int F, int R, int ncls, int tubes) {
-  const size_t W = (size_t)(R + 63) / 64, nfg = (size_t)ncls - 1, f = (size_t)F, r = (size_t)R;
-  const size_t base = 2 * sq_al256(f * r * W * 8) + 2 * sq_al256(nfg * f * r * 4) + sq_al256(nfg * f * r * 2) + 3 * sq_al256(nfg * f * W * 8) + 256;
-  return base + (tubes ? sq_al256(nfg * f * r * 8) + 2 * sq_al256((size_t)P * nfg * 4) : 0);
-}
-
 // P problems of frame_start [P + 1] (device; NULL: one problem of all F frames), F frames in all.  tube_ids != NULL: the four tube
-// outputs (all four non-NULL then).
+// outputs (all four non-NULL then; ws is then the layout with its tube tables, nms_dev.h: seq_nms_ws).
 hipError_t run_seq_nms(const float* boxes, const float* scores, int P, const int* frame_start, int F, int R, int ncls, float score_thr,
                        float link_thr, float nms_thr, int rescore_max, int max_num, float* dets, long long* labels, int* n_out,
-                       int* tube_ids, int* tubes, float* tube_scores, int* tube_start, int max_tubes, void* ws, int phases, hipStream_t s) {
+                       int* tube_ids, int* tubes, float* tube_scores, int* tube_start, int max_tubes, const SeqNmsWs& ws, int phases, hipStream_t s) {
   const int nfg = ncls - 1;
   if (R > SQ_MAX_R || R <= 0 || nfg > 128 || nfg < 1 || F <= 0 || F > SQ_MAX_F || max_num <= 0 || P < 1 || P > F || (!frame_start && P != 1))
     return hipErrorInvalidValue;
   const int W = (R + 63) / 64;
-  const size_t f = (size_t)F, r = (size_t)R, w = (size_t)W, g = (size_t)nfg;
-  char* p = (char*)ws;
-  sq_u64* link = (sq_u64*)p;   p += sq_al256(f * r * w * 8);
-  sq_u64* ovl = (sq_u64*)p;    p += sq_al256(f * r * w * 8);
-  float* best = (float*)p;     p += sq_al256(g * f * r * 4);
-  float* osc = (float*)p;      p += sq_al256(g * f * r * 4);
-  short* next = (short*)p;     p += sq_al256(g * f * r * 2);
-  sq_u64* alive = (sq_u64*)p;  p += sq_al256(g * f * w * 8);
-  sq_u64* keep = (sq_u64*)p;   p += sq_al256(g * f * w * 8);
-  sq_u64* wmax = (sq_u64*)p;   p += sq_al256(g * f * w * 8) + 256;
-  int2* tube = nullptr;
-  int *tcount = nullptr, *cbase = nullptr;
-  if (tube_ids) {
-    tube = (int2*)p;           p += sq_al256(g * f * r * 8);
-    tcount = (int*)p;          p += sq_al256((size_t)P * g * 4);
-    cbase = (int*)p;
-  }
+  sq_u64 *link = ws.link, *ovl = ws.ovl, *alive = ws.alive, *keep = ws.keep, *wmax = ws.wmax;
+  float *best = ws.best, *osc = ws.osc;
+  short* next = ws.next;
+  if ((tube_ids != nullptr) != (ws.tube != nullptr)) return hipErrorInvalidValue;
+  int2* tube = ws.tube;
+  int *tcount = ws.tcount, *cbase = ws.cbase;
   // the merge's LDS as for the other read-outs: the longest possible list (every candidate of every class kept) + the select list
-  int np2 = 1;
-  while (np2 < nfg * R) np2 <<= 1;
-  int sp2 = 1;
-  while (sp2 < max_num) sp2 <<= 1;
-  const size_t cap = 160 * 1024 - 3072;
-  if (max_num >= nfg * R || (size_t)np2 * 8 + (size_t)sp2 * 8 > cap) sp2 = 0;
-  const size_t lds = (size_t)np2 * 8 + (size_t)sp2 * 8;
-  if (lds > cap) return hipErrorInvalidValue;
+  const McMergeLds m = mc_merge_lds(nfg * R, max_num);
+  if (!m.fits) return hipErrorInvalidValue;
+  const int sp2 = m.sp2;
+  const size_t lds = m.bytes;
   static std::atomic<unsigned> attr_dev{0};   // (the attribute is per device)
   per_device_once(attr_dev, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_nms_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_nms_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMcMergeLdsCap);
   });
   if (phases & 1) hipLaunchKernelGGL(seq_nms_link_kernel, dim3((R + 3) / 4, F), dim3(256), 0, s, (const float4*)boxes, frame_start, P, F, R, W, link_thr, nms_thr,
                      link, ovl);

@@ -262,13 +262,6 @@ __global__ __launch_bounds__(1024) void soft_nms_merge_kernel(const float* __res
 }
 
 // ---------------- launchers ----------------
-static size_t sn_al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-size_t multiclass_soft_nms_workspace_bytes(int P, int R, int ncls) {
-  const size_t e = (size_t)P * (ncls - 1) * R;
-  return sn_al256(e * sizeof(float)) + sn_al256(e * sizeof(int)) + sn_al256((size_t)P * (ncls - 1) * sizeof(int)) + 256;
-}
-
 hipError_t run_soft_nms(const float* dets, int n, float iou_thr, int method, float sigma, float min_score, float* out_dets,
                         long long* inds, int* n_out, hipStream_t s) {
   if (n <= 0 || n > SN_MAX_R) return hipErrorInvalidValue;
@@ -279,28 +272,21 @@ hipError_t run_soft_nms(const float* dets, int n, float iou_thr, int method, flo
 
 hipError_t run_multiclass_soft_nms(const float* boxes, const float* scores, int P, int R, int ncls, float score_thr, float iou_thr,
                                    int method, float sigma, float min_score, int max_num, float* dets, long long* labels, int* n_out,
-                                   void* ws, hipStream_t s) {
+                                   const McSoftNmsWs& ws, hipStream_t s) {
   const int nfg = ncls - 1;
   if (R > SN_MAX_R || nfg > 128 || nfg < 1 || R <= 0 || P <= 0 || max_num <= 0) return hipErrorInvalidValue;
-  const size_t e = (size_t)P * nfg * R;
-  char* w = (char*)ws;
-  float* sel_scores = (float*)w;  w += sn_al256(e * sizeof(float));
-  int* sel_rows = (int*)w;        w += sn_al256(e * sizeof(int));
-  int* counts = (int*)w;
+  float* sel_scores = ws.sel_scores;
+  int *sel_rows = ws.sel_rows, *counts = ws.counts;
   // the merge's LDS, sized for the longest possible list (every candidate of every class survives) as for the greedy merge:
   // survivor list + the select stage's list of next_pow2(max_num) entries; with Soft-NMS a total far above max_num is the NORMAL
   // case, and at R = 300 / 30 classes / max_num = 300 both fit (128 KB + 4 KB), so the cut is a radix select, not a whole-list sort
-  int np2 = 1;
-  while (np2 < nfg * R) np2 <<= 1;
-  int sp2 = 1;
-  while (sp2 < max_num) sp2 <<= 1;
-  const size_t cap = 160 * 1024 - 3072;
-  if (max_num >= nfg * R || (size_t)np2 * 8 + (size_t)sp2 * 8 > cap) sp2 = 0;
-  const size_t lds = (size_t)np2 * 8 + (size_t)sp2 * 8;
-  if (lds > cap) return hipErrorInvalidValue;
+  const McMergeLds m = mc_merge_lds(nfg * R, max_num);
+  if (!m.fits) return hipErrorInvalidValue;
+  const int sp2 = m.sp2;
+  const size_t lds = m.bytes;
   static std::atomic<unsigned> attr_dev{0};   // (the attribute is per device)
   per_device_once(attr_dev, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(soft_nms_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(soft_nms_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMcMergeLdsCap);
   });
   hipLaunchKernelGGL(soft_nms_class_kernel, dim3(nfg, P), dim3(64), 0, s, boxes, 4, (long)R * 4, scores + 1, ncls, (long)R * ncls, R, 1,
                      score_thr, iou_thr, method, sigma, min_score, sel_scores, sel_rows, counts, (float*)nullptr, (long long*)nullptr,
