@@ -72,6 +72,8 @@ hipError_t run_deform_im2col(const void*, const float*, void*, int, int, int, in
                              hipStream_t);
 hipError_t run_deform_roi_pool(const void*, const float*, const float*, const float*, void*, int, int, int, int, int, int, int, int, int, int, int,
                                float, float, long, long, int, hipStream_t);
+hipError_t run_roi_pool_fwd(const void*, const float*, void*, int32_t*, int, int, int, int, int, int, int, float, int, hipStream_t);
+hipError_t run_roi_pool_bwd(const float*, const float*, const int32_t*, float*, int, int, int, int, int, int, int, hipStream_t);
 hipError_t run_nms_batched(const float*, int, int, float, int, int, int, long long*, int*, const NmsWs&, hipStream_t, int band = 0,
                            int* band_done = nullptr);
 hipError_t run_rpn_select(const void*, const void*, long, long, float*, const RpnParams&, int, hipStream_t);
@@ -1758,6 +1760,40 @@ int hvr_deform_roi_pool_fwd(const void* feat, const float* rois, const float* tr
   return check_launch(run_deform_roi_pool(feat, rois, trans, mask_logit, out, B, H, W, C, K, PH, out_channels, group_size, part_size, num_classes,
                                           sample_per_part, spatial_scale, trans_std, (long)ldt, (long)ldm, dtype, (hipStream_t)stream),
                       "hvr_deform_roi_pool_fwd");
+}
+
+// ---- RoI max pooling (roi_pool.hip) ----
+static int roi_pool_shape(const char* what, int B, int H, int W, int C, int K, int PH, int PW) {
+  if (K < 0 || B < 0 || H <= 0 || W <= 0 || C <= 0 || PH <= 0 || PW <= 0)
+    return fail(HVR_EINVAL, "%s: bad shape K=%d B=%d H=%d W=%d C=%d out_size=%d x %d", what, K, B, H, W, C, PH, PW);
+  if ((long)H * W >= (1L << 31) || (long)PH * PW >= (1L << 31))
+    return fail(HVR_EUNSUPPORTED, "%s: a map or an output of 2^31 cells (the argmax is an int32 within the frame's plane)", what);
+  return HVR_OK;
+}
+
+int hvr_roi_pool_fwd(const void* feat, const float* rois, void* out, int32_t* argmax, int B, int H, int W, int C, int K, int PH, int PW,
+                     float spatial_scale, int dtype, void* stream) {
+  if (!valid_dtype(dtype)) return fail(HVR_EINVAL, "hvr_roi_pool_fwd: bad dtype %d", dtype);
+  if (dtype == HVR_F16S) return fail(HVR_EUNSUPPORTED, "hvr_roi_pool_fwd: no split-half instance (pool in f32 and convert)");
+  if (const int rc = roi_pool_shape("hvr_roi_pool_fwd", B, H, W, C, K, PH, PW)) return rc;
+  const int cv = 16 / elem_size(dtype);
+  if (C % cv) return fail(HVR_EUNSUPPORTED, "hvr_roi_pool_fwd: C=%d is not a multiple of %d (16 bytes of channels per lane)", C, cv);
+  if (K == 0) return HVR_OK;
+  if (!feat || !rois || !out) return fail(HVR_EINVAL, "hvr_roi_pool_fwd: null pointer");
+  if (!aligned16(feat) || !aligned16(out) || !aligned16(argmax) || (reinterpret_cast<uintptr_t>(rois) & 3))
+    return fail(HVR_EINVAL, "hvr_roi_pool_fwd: feat, out and argmax must be 16-byte aligned, rois 4-byte");
+  return check_launch(run_roi_pool_fwd(feat, rois, out, argmax, B, H, W, C, K, PH, PW, spatial_scale, dtype, (hipStream_t)stream), "hvr_roi_pool_fwd");
+}
+
+int hvr_roi_pool_bwd(const float* grad_out, const float* rois, const int32_t* argmax, float* grad_feat, int B, int H, int W, int C, int K, int PH,
+                     int PW, void* stream) {
+  if (const int rc = roi_pool_shape("hvr_roi_pool_bwd", B, H, W, C, K, PH, PW)) return rc;
+  if (K == 0) return HVR_OK;
+  if (!grad_out || !rois || !argmax || !grad_feat) return fail(HVR_EINVAL, "hvr_roi_pool_bwd: null pointer");
+  if ((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(rois) | reinterpret_cast<uintptr_t>(argmax) |
+       reinterpret_cast<uintptr_t>(grad_feat)) & 3)
+    return fail(HVR_EINVAL, "hvr_roi_pool_bwd: misaligned pointer");
+  return check_launch(run_roi_pool_bwd(grad_out, rois, argmax, grad_feat, B, H, W, C, K, PH, PW, (hipStream_t)stream), "hvr_roi_pool_bwd");
 }
 
 // ---- NMS ----

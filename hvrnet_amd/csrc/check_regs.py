@@ -24,7 +24,7 @@ def main(*paths):
                 bad.append('%s: %d VGPRs spilled, %d bytes of scratch' % (name, spill, scratch))
             continue
         if name.startswith(('_ZN3hvr19mc_nms_', '_ZN3hvr15nms_', '_ZN3hvr16nms_', '_ZN3hvr17rpn_', '_ZN3hvr25relation_scores_bt', '_ZN3hvr14pc_tile_kernel', '_ZN3hvr15big_tile_kernel')) \
-                or re.match(r'_ZN3hvr\d+(?:tta|soft_nms|seq_nms|deform_im2col|deform_roi_pool|gconv3x3|res2_conv3x3|gcb_pool|gn_stats|gn_apply|gen_attn)_', name):   # (gn.hip: a lane keeps the running partials of its pieces and two steps' loads in registers for its whole run, and the apply its channels' mean, scale and shift, a spill would sit on the one pass over the map; gen_attn.hip: a wave keeps its queries, 16 scores and the d / 16 output accumulators in registers across the key loop, a spill would sit between the two MFMA chains; gcb.hip: a wave keeps acc[C / 64] and two pixels' pieces in registers for its whole run, a spill would sit on the one pass over the map; res2.hip: a wave keeps two units' accumulators and the loads of a whole tap in flight, a spill would sit inside the K loop; gconv3x3.hip: a wave's weights stay in registers for its whole life, a spill would put them behind every tile's loads; dpool.hip: a row of samples, 4 x sample_per_part corner vectors, in flight per lane; tta.hip, softnms.hip, seqnms.hip: the augmentation merge, the Soft-NMS rounds and the Seq-NMS frame sweep are serial sweeps of the same kind; dcn.hip: the sampler keeps four corner vectors in flight per lane)
+                or re.match(r'_ZN3hvr\d+(?:tta|soft_nms|seq_nms|deform_im2col|deform_roi_pool|roi_pool_fwd|gconv3x3|res2_conv3x3|gcb_pool|gn_stats|gn_apply|gen_attn)_', name):   # (gn.hip: a lane keeps the running partials of its pieces and two steps' loads in registers for its whole run, and the apply its channels' mean, scale and shift, a spill would sit on the one pass over the map; gen_attn.hip: a wave keeps its queries, 16 scores and the d / 16 output accumulators in registers across the key loop, a spill would sit between the two MFMA chains; gcb.hip: a wave keeps acc[C / 64] and two pixels' pieces in registers for its whole run, a spill would sit on the one pass over the map; res2.hip: a wave keeps two units' accumulators and the loads of a whole tap in flight, a spill would sit inside the K loop; roi_pool.hip: a lane keeps the running maxima and indices of its 16-byte piece and the unrolled walk's loads in registers, a spill would sit inside the walk over a bin's pixels; gconv3x3.hip: a wave's weights stay in registers for its whole life, a spill would put them behind every tile's loads; dpool.hip: a row of samples, 4 x sample_per_part corner vectors, in flight per lane; tta.hip, softnms.hip, seqnms.hip: the augmentation merge, the Soft-NMS rounds and the Seq-NMS frame sweep are serial sweeps of the same kind; dcn.hip: the sampler keeps four corner vectors in flight per lane)
             # the serial read-out / proposal kernels and the one-round scores kernel: scratch traffic inside their dependency
             # chains (the greedy sweep's prefetched IoU rows, the 176 accumulators) is a silent slowdown -- fail the build
             seen += 1

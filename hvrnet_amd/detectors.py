@@ -229,8 +229,8 @@ class _WindowDetector(TwoStageDetector):
         return self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
 
     def _train_roi_layer(self):
-        """The RoI layer of the training paths: they differentiate through RoIAlign; every other roi_layer (the deformable
-        pooling packs of ops.py) is inference only."""
+        """The RoI layer of the training paths: they differentiate through RoIAlign or RoIPool; every other roi_layer (the
+        deformable pooling packs of ops.py) is inference only."""
         from . import ops
         if getattr(self.backbone, 'gen_attention', None) is not None:
             # (HNMBRCNN.forward_train would run such a backbone frozen, under no_grad; the block is inference only everywhere, as stated)
@@ -240,10 +240,18 @@ class _WindowDetector(TwoStageDetector):
                 raise NotImplementedError('a detector whose %s runs under GroupNorm is inference only: group normalisation has no backward'
                                           % type(part).__name__)
         layer = self.bbox_roi_extractor.roi_layers[0]
-        if not isinstance(layer, ops.RoIAlign):
+        if not isinstance(layer, (ops.RoIAlign, ops.RoIPool)):
             raise NotImplementedError('training runs through RoIAlign only: roi_layer %s is inference only (it has no backward)'
                                       % type(layer).__name__)
         return layer
+
+    @staticmethod
+    def _train_roi_feats(layer, c5, rois):
+        """The sampled RoIs' features of a training step from the physical NHWC c5, through the layer's differentiable function."""
+        from . import ops
+        if isinstance(layer, ops.RoIPool):
+            return ops.roi_pool(c5.permute(0, 3, 1, 2), rois, layer.out_size, layer.spatial_scale)
+        return ops.roi_align(c5.permute(0, 3, 1, 2), rois, layer.out_size, layer.spatial_scale, layer.sample_num)
 
     rpn_side_stream = os.environ.get('HVR_RPN_SIDE', '1') != '0'
 
@@ -733,7 +741,7 @@ class SelsaRCNN(_WindowDetector):
         layer = self._train_roi_layer()
         c4 = self.backbone.forward_train_nhwc(img)
         c5 = self.shared_head.forward_train_nhwc(c4)
-        feats = ops.roi_align(c5.permute(0, 3, 1, 2), rois, layer.out_size, layer.spatial_scale, layer.sample_num)
+        feats = self._train_roi_feats(layer, c5, rois)
         logits = self.bbox_head.forward_train(feats, cur_range)
         return self.bbox_head.loss_train(logits, labels, label_weights, bbox_targets, bbox_weights)
 
@@ -794,7 +802,7 @@ class SelsaRCNN(_WindowDetector):
         n_key = sampling_results[key].bboxes.shape[0]
         cur_range = dict(start=key * n_key, length=n_key)
         c5 = self.shared_head.forward_train_nhwc(c4)
-        feats = ops.roi_align(c5.permute(0, 3, 1, 2), rois, layer.out_size, layer.spatial_scale, layer.sample_num)
+        feats = self._train_roi_feats(layer, c5, rois)
         logits = self.bbox_head.forward_train(feats, cur_range)
         labels, label_w, bbox_t, bbox_w = T.bbox_target([sampling_results[key]], [gt_b], [gt_l], rcnn_cfg,
                                                         target_means=self.bbox_head.target_means, target_stds=self.bbox_head.target_stds)
@@ -962,7 +970,7 @@ class HNMBRCNN(_WindowDetector):
             key_gtb.append(gt_b)
             key_gtl.append(gt_l)
         c5 = self.shared_head.forward_train_nhwc(c4k)                                   # res5 with a graph; C4 is a constant
-        all_feats = ops.roi_align(c5.permute(0, 3, 1, 2), rois, layer.out_size, layer.spatial_scale, layer.sample_num)
+        all_feats = self._train_roi_feats(layer, c5, rois)
         feats = list(torch.split(all_feats, rows, dim=0))
         targets = T.bbox_target(key_results, key_gtb, key_gtl, rcnn_cfg, target_means=self.bbox_head.target_means,
                                 target_stds=self.bbox_head.target_stds)

@@ -218,6 +218,8 @@ SYMBOLS = {
     'hvr_deform_im2col_supported': (_i, [_i, _i, _i]),
     'hvr_deform_im2col': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i, _vp]),
     'hvr_deform_roi_pool_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i64, _i64, _i, _vp]),
+    'hvr_roi_pool_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    'hvr_roi_pool_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'hvr_gcb_supported': (_i, [_i, _i]),
     'hvr_gcb_splits': (_i, [_i, _i, _i]),
     'hvr_gcb_workspace_bytes': (_sz, [_i, _i, _i]),
@@ -1727,6 +1729,45 @@ def deform_roi_pool(feat_nhwc, rois, trans, mask_logit, out_size, out_channels, 
                                              int(out_channels), int(group_size), part_size, ncls, int(sample_per_part), float(spatial_scale),
                                              float(trans_std), ldt, ldm, _dt(feat_nhwc), _stream()), 'hvr_deform_roi_pool_fwd')
     return out
+
+
+def roi_pool_fwd(feat_nhwc, rois, out_h, out_w, spatial_scale, with_argmax=False, out=None):
+    """RoI max pooling (hvr_roi_pool_fwd; the rule is stated in include/hvr_hip.h): feat_nhwc [B,H,W,C] physical NHWC, rois [K,5]
+    -> out [K,out_h,out_w,C] of the map's dtype, or (out, argmax [K,out_h,out_w,C] int32) with with_argmax.  out: a contiguous
+    tensor of the result's shape and dtype to write into (not for split-half maps).  A split-half map is pooled in f32 and handed
+    back in the split format, as roi_align_fwd does; the argmax is that of the f32 call.
+    Byte model of the span: the map once (a pixel is re-read once per bin that covers it; those reads hit L2), out and the argmax
+    written once, the rois once."""
+    _need_cuda(feat_nhwc, rois)
+    if feat_nhwc.dtype == SPLIT:
+        assert out is None
+        r = roi_pool_fwd(cast(feat_nhwc, torch.float32), rois, out_h, out_w, spatial_scale, with_argmax)
+        return (cast(r[0], SPLIT), r[1]) if with_argmax else cast(r, SPLIT)
+    rois = rois.contiguous().float()
+    assert feat_nhwc.dim() == 4 and feat_nhwc.is_contiguous() and rois.dim() == 2 and rois.shape[1] == 5, (tuple(feat_nhwc.shape), tuple(rois.shape))
+    B, H, W, C = feat_nhwc.shape
+    K = rois.shape[0]
+    out = _out(out, (K, int(out_h), int(out_w), C), feat_nhwc.dtype, feat_nhwc.device)
+    argmax = torch.empty(out.shape, dtype=torch.int32, device=out.device) if with_argmax else None
+    work = float((feat_nhwc.numel() + out.numel()) * feat_nhwc.element_size() + (out.numel() * 4 if with_argmax else 0) + rois.numel() * 4)
+    with _span('roi_pool', work):
+        _check(lib().hvr_roi_pool_fwd(_ptr(feat_nhwc), _ptr(rois), _ptr(out), _ptr(argmax), B, H, W, C, K, int(out_h), int(out_w),
+                                      float(spatial_scale), _dt(feat_nhwc), _stream()), 'hvr_roi_pool_fwd')
+    return (out, argmax) if with_argmax else out
+
+
+def roi_pool_bwd(grad_out_nhwc, rois, argmax, feat_shape_nhwc):
+    """grad_out [K,PH,PW,C] scattered to the recorded argmax (hvr_roi_pool_bwd) -> grad_in [B,H,W,C] f32, zeroed here."""
+    _need_cuda(grad_out_nhwc, rois, argmax)
+    grad_out = grad_out_nhwc.contiguous().float()
+    rois = rois.contiguous().float()
+    B, H, W, C = feat_shape_nhwc
+    K, PH, PW, _ = grad_out.shape
+    assert argmax.dtype == torch.int32 and argmax.is_contiguous() and tuple(argmax.shape) == (K, PH, PW, C) and rois.shape[0] == K, \
+        (argmax.dtype, tuple(argmax.shape), tuple(grad_out.shape), tuple(rois.shape), C)
+    grad_in = torch.zeros((B, H, W, C), dtype=torch.float32, device=grad_out.device)
+    _check(lib().hvr_roi_pool_bwd(_ptr(grad_out), _ptr(rois), _ptr(argmax), _ptr(grad_in), B, H, W, C, K, PH, PW, _stream()), 'hvr_roi_pool_bwd')
+    return grad_in
 
 
 # ---- global context block (csrc/gcb.hip; the rule: include/hvr_hip.h)

@@ -6,6 +6,8 @@ core/post_processing/bbox_nms.py:32-34), so this module exposes the same names w
 signatures and error behaviour:
   RoIAlign(out_size, spatial_scale, sample_num=0, use_torchvision=False)   roi_align/roi_align.py:59-87
   roi_align(features, rois, out_size, spatial_scale, sample_num)           roi_align/roi_align.py:56
+  RoIPool(out_size, spatial_scale, use_torchvision=False)                  roi_pool/roi_pool.py:53-75
+  roi_pool(features, rois, out_size, spatial_scale)                        roi_pool/roi_pool.py:50 (forward and argmax backward)
   nms(dets, iou_thr, device_id=None) -> (dets[inds], inds)                  nms/nms_wrapper.py:8-61
   soft_nms(dets, iou_thr, method='linear', sigma=0.5, min_score=1e-3)      nms/nms_wrapper.py:64-102
   seq_nms(boxes, scores, score_thr, link_iou_thr=0.5, nms_iou_thr=0.3, max_num=300, rescore='avg', *, frame_counts=None, tubes=False)   (no reference counterpart:
@@ -115,6 +117,66 @@ def _pooling_map(data, dtype=None):
         v = data.permute(0, 2, 3, 1)
         return v if dtype is None or v.dtype == dtype else native.cast(v, dtype)
     return native.nchw_to_nhwc(data.contiguous(), dtype)
+
+
+class RoIPoolFunction(Function):
+    """roi_pool.py:10-47.  features [B,C,H,W] (channels_last: in place; NCHW-contiguous: converted once, _pooling_map), rois [K,5] ->
+    the logical [K, C, PH, PW] view of the physical [K, PH, PW, C] result, as RoIAlign hands it to the heads.  The argmax is
+    recorded only when the map asks for a gradient; the backward scatters to it (native.roi_pool_bwd) in f32 and hands the
+    gradient back in the map's dtype and layout."""
+
+    @staticmethod
+    def forward(ctx, features, rois, out_size, spatial_scale):
+        out_h, out_w = _pair(out_size)
+        assert isinstance(out_h, int) and isinstance(out_w, int)
+        if not features.is_cuda:
+            raise NotImplementedError
+        if rois.dim() != 2 or rois.size(1) != 5:
+            raise ValueError('wrong roi size: expected [K, 5], got %s' % (tuple(rois.shape),))
+        ctx.feature_size, ctx.feature_dtype = features.size(), features.dtype
+        ctx.nhwc = _channels_last(features)
+        fmap = _pooling_map(features)
+        if features.requires_grad:
+            out, argmax = native.roi_pool_fwd(fmap, rois, out_h, out_w, spatial_scale, with_argmax=True)
+            ctx.save_for_backward(rois, argmax)
+        else:
+            out = native.roi_pool_fwd(fmap, rois, out_h, out_w, spatial_scale)
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        assert ctx.feature_size is not None and grad_output.is_cuda
+        grad_input = None
+        if ctx.needs_input_grad[0]:
+            rois, argmax = ctx.saved_tensors
+            B, C, H, W = ctx.feature_size
+            g = native.cast(native.roi_pool_bwd(grad_output.permute(0, 2, 3, 1), rois, argmax, (B, H, W, C)), ctx.feature_dtype)
+            grad_input = g.permute(0, 3, 1, 2)   # accumulated in f32, handed back in the map's dtype
+            if not ctx.nhwc:
+                grad_input = grad_input.contiguous()
+        return grad_input, None, None, None
+
+
+roi_pool = RoIPoolFunction.apply
+
+
+class RoIPool(nn.Module):
+
+    def __init__(self, out_size, spatial_scale, use_torchvision=False):
+        super(RoIPool, self).__init__()
+        if use_torchvision:
+            raise NotImplementedError('torchvision is not part of this build')
+        self.out_size = _pair(out_size)
+        self.spatial_scale = float(spatial_scale)
+        self.use_torchvision = use_torchvision
+
+    def forward(self, features, rois):
+        return roi_pool(features, rois, self.out_size, self.spatial_scale)
+
+    def __repr__(self):
+        return '%s(out_size=%s, spatial_scale=%s, use_torchvision=%s)' % (
+            self.__class__.__name__, self.out_size, self.spatial_scale, self.use_torchvision)
 
 
 class DeformRoIPoolingFunction(Function):

@@ -628,6 +628,48 @@ int hvr_deform_roi_pool_fwd(const void* feat, const float* rois, const float* tr
                             int sample_per_part, float spatial_scale, float trans_std, int64_t ldt, int64_t ldm, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * RoI max pooling with its argmax backward (RoIPool).  Replaces mmdet/ops/roi_pool/src/roi_pool_kernel.cu:16-74 (forward) and
+ * :112-135 (backward).
+ *   feat     [B][H][W][C]        physical NHWC, `dtype` = HVR_F32 / HVR_BF16 / HVR_F16 (split half: HVR_EUNSUPPORTED, pool in f32)
+ *   rois     [K][5]              f32 (b, x1, y1, x2, y2), as RoIAlign
+ *   out      [K][PH][PW][C]      `dtype`, allocated by the caller
+ *   argmax   [K][PH][PW][C]      int32 or NULL (the inference form: no index is kept or written)
+ * Every geometry step is one f32 operation, rounded on its own (no fused multiply-add), s = spatial_scale:
+ *   rx1 = x1 * s                 ry1 = y1 * s
+ *   rx2 = (x2 + 1) * s           ry2 = (y2 + 1) * s
+ *   rw  = rx2 - rx1              rh  = ry2 - ry1
+ *   bw  = rw / PW                bh  = rh / PH
+ *   bin (ph, pw):  xs = floor(float(pw) * bw + rx1)    xe = ceil(float(pw + 1) * bw + rx1)
+ *                  ys = floor(float(ph) * bh + ry1)    ye = ceil(float(ph + 1) * bh + ry1)
+ *   each clamped to [0, W] resp. [0, H] as a float, then converted to int
+ *   out    = max of feat[b][h][w][c] over ys <= h < ye, xs <= w < xe
+ *   argmax = h * W + w of the FIRST pixel in row-major order (h outer, w inner) that attains it
+ * This is roi_pool_kernel.cu:30-56 with scalar_t = float.  What differs from the reference:
+ *   geometry dtype  f32 for every feature dtype (the reference computes it in half for half maps);
+ *   clamp           on the float, before the conversion to int: any finite coordinate is safe;
+ *   selection       stated as "first pixel that attains the maximum" (values compared after an exact widening to f32, the
+ *                   stored result is the input element).  The reference starts at `first - 1` under a strict `>` and selects the
+ *                   same pixel wherever x - 1 < x; the rule here needs no subtraction and so holds for large bf16 values too.
+ *                   Inputs are finite; NaN is unspecified;
+ *   empty bin       xe <= xs or ye <= ys: value 0 and argmax -1 for every channel;
+ *   malformed RoI   rw <= 0 or rh <= 0: all bins value 0 and argmax -1 (the reference leaves argmax 0 there and its backward adds
+ *                   the gradient to pixel 0);
+ *   batch index     b outside [0, B) (compared as a float, else truncated): the RoI is treated as malformed and no memory is
+ *                   read for it (the reference reads out of bounds);
+ *   backward        grad_feat[b][argmax][c] += grad_out[k][ph][pw][c] for every output element with argmax >= 0; nothing happens
+ *                   for -1 (the reference writes one element before the plane there).
+ * Contraction changes bins: at s = 1/16, PW = 7, W = 11 the last bin of x1 = -39, x2 = 31 is [1, 2) as stated and [1, 3) with a
+ * fused multiply-add; x1 = -39, x2 = 95: [4, 6) against [4, 7); x1 = -37, x2 = 15: [0, 1) against [0, 2).
+ * Forward: C % 8 == 0 (2-byte dtypes) / C % 4 == 0 (f32), else HVR_EUNSUPPORTED; feat, out, argmax 16-byte aligned.  K == 0 returns
+ * without a launch.  Backward: f32 only, ACCUMULATES into grad_feat [B][H][W][C] with f32 atomics (the caller zeroes it); of rois
+ * only the batch index is read.  Non-positive PH, PW, H, W, C or negative K, B: HVR_EINVAL.  No host synchronisation, no allocation.
+ * ---------------------------------------------------------------------------------- */
+int hvr_roi_pool_fwd(const void* feat, const float* rois, void* out, int32_t* argmax /* may be NULL */, int B, int H, int W, int C, int K,
+                     int PH, int PW, float spatial_scale, int dtype, void* stream);
+int hvr_roi_pool_bwd(const float* grad_out, const float* rois, const int32_t* argmax, float* grad_feat, int B, int H, int W, int C, int K,
+                     int PH, int PW, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Greedy NMS.  Replaces nms_cpu.nms / nms_cuda.nms (mmdet/ops/nms/src/nms_cpu.cpp:5-71,
  * nms_kernel.cu:24-136) with no host round trip.  dets [n][5] f32 (x1,y1,x2,y2,score);
  * ge_semantics != 0 suppresses at IoU >= thr (the CPU reference), 0 at IoU > thr (the CUDA
