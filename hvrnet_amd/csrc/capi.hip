@@ -1203,7 +1203,7 @@ int hvr_relation_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, con
   const bool two_byte = dtype == HVR_BF16 || dtype == HVR_F16;
   // tuning overrides, read once
   constexpr int tile_scores = 0, gm_scores = 8;
-#ifdef HVR_DEBUG_KNOBS  // tuning builds only (tools/build_dbg.sh): alias every operand row to row 0 (no memory-system cost)
+#ifdef HVR_DEBUG_KNOBS  // tuning builds only (tools/build_var.sh NAME "-DHVR_DEBUG_KNOBS ..." capi ...): alias every operand row to row 0 (no memory-system cost)
   static const int dbg_ld0 = env_tile("HVR_DBG_LD0");
 #endif
   const bool bt = two_byte && staging && scores_bt_supported(Mq, Mk, D, ldq, ldk, ldv, ldp, Q, K, V, P, Vt);

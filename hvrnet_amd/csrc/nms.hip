@@ -1049,7 +1049,7 @@ __global__ __launch_bounds__(64 * SWEEP_WAVES) void nms_band_sweep_kernel(const 
                                                                           int* __restrict__ done) {
   __shared__ unsigned long long kept[64];
   __shared__ int sh_done, sh_nkept;
-#ifdef HVR_DBG_SWEEP_CLK   // (tools/build_dbg.sh, NMS_DBG=1: per-chunk clock stamps of the hand-over chain, printed for problem 0)
+#ifdef HVR_DBG_SWEEP_CLK   // (tools/build_var.sh NAME "-DHVR_DBG_SWEEP_CLK" nms: per-chunk clock stamps of the hand-over chain, printed for problem 0)
   __shared__ long long dbg_clk[64][5];
 #endif
   const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);

@@ -300,6 +300,37 @@ def test_asm_wait_lint_passes_on_the_built_library():
     assert r.returncode == 0, r.stdout + r.stderr
 
 
+# ---- the build's manifest (hvrnet_amd/csrc/units.txt): the one place that says which units make up the library ----
+CSRC = os.path.join(ROOT, 'hvrnet_amd', 'csrc')
+
+
+def build_units():
+    """units.txt as {unit: set of its words}, in link order ('nofma': -ffp-contract=off, 'remarks': remarks and device assembly kept)."""
+    lines = [line.split('#')[0].split() for line in open(os.path.join(CSRC, 'units.txt'))]
+    names = [words[0] for words in lines if words]
+    assert len(names) == len(set(names)), 'a unit is listed twice'
+    return {words[0]: set(words[1:]) for words in lines if words}
+
+
+def check_regs():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('check_regs', os.path.join(CSRC, 'check_regs.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_every_unit_is_stated_once_in_the_manifest_and_nowhere_else():
+    units = build_units()
+    assert sorted(units) == sorted(f[:-4] for f in os.listdir(CSRC) if f.endswith('.hip'))       # every source once, no unit without one
+    assert all(words <= {'nofma', 'remarks'} for words in units.values())
+    for script in (os.path.join(CSRC, 'build.sh'), os.path.join(ROOT, 'tools', 'build_var.sh')):
+        text = open(script).read()
+        assert 'units.txt' in text
+        named = [u for u in units if re.search(r'(?<![A-Za-z0-9_])%s(?![A-Za-z0-9_])' % u, text)]
+        assert not named, '%s names %s' % (script, named)
+
+
 def test_the_tolerance_constants_are_frozen():
     """hvrnet_amd/parity.py is frozen as the round-5 judge accepted it ("Next round" 1a): class indices exact, scores within
     1e-3, boxes within 1e-3 px + 1.3e-6 x extent; round 4's fixed bar and north_star's literal 1e-3 px are reported beside it."""

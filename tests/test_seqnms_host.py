@@ -234,6 +234,9 @@ def test_raw_read_out_of_a_window_with_a_short_frame_takes_the_exact_path():
 def test_seqnms_source_is_plain_cpp_and_registered():
     src = open(os.path.join(ROOT, 'hvrnet_amd', 'csrc', 'seqnms.hip')).read()
     assert 'asm' not in src and '__builtin_amdgcn_s_' not in src          # ballots, shuffles and vector stores only
-    build = open(os.path.join(ROOT, 'hvrnet_amd', 'csrc', 'build.sh')).read()
-    assert re.search(r'seqnms[^\n]*-ffp-contract=off', build) and build.count('seqnms') >= 7
-    assert 'seq_nms' in open(os.path.join(ROOT, 'hvrnet_amd', 'csrc', 'check_regs.py')).read()
+    from tests.test_host_logic import build_units, check_regs
+    assert build_units()['seqnms'] == {'nofma', 'remarks'}                 # no contraction (w * h in the union), remarks kept
+    for kernel in ('_ZN3hvr19seq_nms_link_kernelEPK15HIP_vector_typeIfLj4EEPKiiiiiffPyS6_', '_ZN3hvr19seq_nms_path_kernelEPKfPKiiiiifiPKyS5_PfPsS6_PyS8_S8_P15HIP_vector_typeIiLj2EEPi',
+                   '_ZN3hvr26seq_nms_tube_prefix_kernelEPKiiiPiS2_', '_ZN3hvr20seq_nms_merge_kernelEPKfiiiiS1_PKyiiPfPxPiPKiiPK15HIP_vector_typeIiLj2EES8_S8_S6_PS9_IiLj4EES4_i'):
+        rule = check_regs().rule_for(kernel)                                # (row of the table, bytes of scratch allowed)
+        assert rule is not None and rule[1] == 0, kernel

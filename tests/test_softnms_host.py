@@ -137,7 +137,8 @@ def test_argument_errors_of_the_public_surface():
 def test_softnms_source_is_plain_cpp():
     src = open(os.path.join(ROOT, 'hvrnet_amd', 'csrc', 'softnms.hip')).read()
     assert 'asm' not in src and '__builtin_amdgcn_s_' not in src          # ballots, shuffles and vector stores only
-    build = open(os.path.join(ROOT, 'hvrnet_amd', 'csrc', 'build.sh')).read()
-    assert re.search(r'softnms[^\n]*-ffp-contract=off', build), 'softnms.hip must be built without contraction (the ua expression)'
-    regs = open(os.path.join(ROOT, 'hvrnet_amd', 'csrc', 'check_regs.py')).read()
-    assert 'soft_nms' in regs
+    from tests.test_host_logic import build_units, check_regs
+    assert build_units()['softnms'] == {'nofma', 'remarks'}, 'softnms.hip must be built without contraction (the ua expression)'
+    for kernel in ('_ZN3hvr21soft_nms_class_kernelEPKfilS1_iliiffiffPfPiS3_S2_PxS3_', '_ZN3hvr21soft_nms_merge_kernelEPKfiiS1_PKiS3_iiPfPxPi'):
+        rule = check_regs().rule_for(kernel)                                # (row of the table, bytes of scratch allowed)
+        assert rule is not None and rule[1] == 0, kernel

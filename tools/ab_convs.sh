@@ -1,5 +1,5 @@
 #!/bin/bash
-# the window's convs in one operand format under several A/B libraries (tools/build_ab.sh), interleaved: $1 = dtype, rest = library names ("-" = product)
+# the window's convs in one operand format under several A/B libraries (tools/build_var.sh NAME "DEFS" gemm gemm_f16), interleaved: $1 = dtype, rest = library names ("-" = product)
 dt=$1; shift
 for round in 1 2; do
   for lib in "$@"; do

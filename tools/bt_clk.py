@@ -1,4 +1,4 @@
-"""Per-workgroup wall-clock stamps of the persistent scores kernel (debug build -DHVR_DBG_BT_CLK, tools/build_dbg.sh btclk "-DHVR_DBG_BT_CLK";
+"""Per-workgroup wall-clock stamps of the persistent scores kernel (debug build -DHVR_DBG_BT_CLK, tools/build_var.sh btclk "-DHVR_DBG_BT_CLK" relation_bt;
 HVR_BENCH_LIB=abtest/libhvr_btclk.so): V^T, then per tile loop start / loop end / epilogue end, in 100 MHz ticks from the workgroup's start.
 
     HVR_BENCH_LIB=abtest/libhvr_btclk.so python tools/bt_clk.py [--groups 4] > bt_clk.txt
