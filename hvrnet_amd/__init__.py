@@ -14,6 +14,8 @@ from .box_ops import (bbox_flip, bbox_mapping, bbox_mapping_back, merge_aug_bbox
 from .config import Config, hvr_config, selsa_config  # noqa: F401
 from .detectors import HNMBRCNN, SelsaRCNN  # noqa: F401
 from .ga_rpn_head import GARPNHead  # noqa: F401
+from . import losses  # noqa: F401
+from .losses import FocalLoss  # noqa: F401
 from .ops import ContextBlock, GeneralizedAttention, MaskedConv2d, RoIPool, masked_conv2d, roi_pool, seq_nms, soft_nms  # noqa: F401
 from .pipelines import FrameIngest, FrameIngestAug  # noqa: F401
 from .registry import build_detector  # noqa: F401

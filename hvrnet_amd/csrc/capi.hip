@@ -49,6 +49,12 @@ hipError_t run_box_targets(const float*, int, int, const float*, const long long
 hipError_t run_rpn_loss(const float*, int, int, int, const long long*, const float*, const float*, const float*, const int*, float, float*,
                         float*, hipStream_t);
 hipError_t run_ce_rows(const float*, int, int, int, const long long*, int, float*, hipStream_t);
+void focal_split(int N, int C, int* S, int* rows);
+hipError_t run_focal_elem(const void*, int, const long long*, const float*, int, int, float, float, int, float*, hipStream_t);
+hipError_t run_focal_fused(const float*, int, const long long*, const float*, int, int, float, float, float, float, const int*, float*, float*, float*,
+                           hipStream_t);
+hipError_t run_rpn_focal_loss(const float*, int, int, int, const long long*, const float*, const float*, const float*, const int*, float, float, float,
+                              float, float, float*, float*, hipStream_t);
 hipError_t run_triplet_margin(const void*, long, const void*, long, int, int, int, const long long*, const long long*, const long long*, int,
                               float, int, float*, float*, float*, float*, hipStream_t);
 hipError_t run_ingest(const uint8_t*, int, int, long, float*, int, int, int, int, const float*, const float*, int, int, hipStream_t);
@@ -1575,6 +1581,71 @@ int hvr_rpn_loss(const float* o, int ldo, int A, int rows, const int64_t* labels
   return check_launch(run_rpn_loss(o, ldo, A, rows, (const long long*)labels, label_weights, bbox_targets, bbox_weights, counts, beta,
                                    out2, d_o, (hipStream_t)stream),
                       "hvr_rpn_loss");
+}
+
+// ---- sigmoid focal loss (focal.hip; the rule: include/hvr_hip.h)
+static int focal_args(const char* what, int N, int C, int ldl, float gamma, float alpha) {
+  if (N < 1 || C < 1) return fail(HVR_EINVAL, "%s: N=%d rows of C=%d columns (N, C >= 1)", what, N, C);
+  if (ldl < C) return fail(HVR_EINVAL, "%s: row pitch ldl=%d is below C=%d (ldl >= C)", what, ldl, C);
+  if ((long)N * ldl >= (1L << 31)) return fail(HVR_EUNSUPPORTED, "%s: N * ldl = %ld elements (N * ldl < 2^31)", what, (long)N * ldl);
+  if (!(gamma >= 0.f) || !std::isfinite(gamma)) return fail(HVR_EINVAL, "%s: gamma=%g (gamma >= 0)", what, (double)gamma);
+  if (!(alpha >= 0.f && alpha <= 1.f)) return fail(HVR_EINVAL, "%s: alpha=%g (0 <= alpha <= 1)", what, (double)alpha);
+  return HVR_OK;
+}
+static int focal_dtype(const char* what, int dtype) {
+  if (!valid_dtype(dtype)) return fail(HVR_EINVAL, "%s: bad dtype %d", what, dtype);
+  if (dtype == HVR_F16S) return fail(HVR_EUNSUPPORTED, "%s: no split-half logits (HVR_F32 / HVR_BF16 / HVR_F16)", what);
+  return HVR_OK;
+}
+int hvr_sigmoid_focal_loss_fwd(const void* logits, int ldl, const int64_t* targets, int N, int C, float gamma, float alpha, int dtype,
+                               float* loss, void* stream) {
+  if (!logits || !targets || !loss) return fail(HVR_EINVAL, "hvr_sigmoid_focal_loss_fwd: null pointer");
+  if (int rc = focal_dtype("hvr_sigmoid_focal_loss_fwd", dtype)) return rc;
+  if (int rc = focal_args("hvr_sigmoid_focal_loss_fwd", N, C, ldl, gamma, alpha)) return rc;
+  return check_launch(run_focal_elem(logits, ldl, (const long long*)targets, nullptr, N, C, gamma, alpha, dtype, loss, (hipStream_t)stream),
+                      "hvr_sigmoid_focal_loss_fwd");
+}
+int hvr_sigmoid_focal_loss_bwd(const void* logits, int ldl, const int64_t* targets, const float* d_loss, int N, int C, float gamma,
+                               float alpha, int dtype, float* d_logits, void* stream) {
+  if (!logits || !targets || !d_loss || !d_logits) return fail(HVR_EINVAL, "hvr_sigmoid_focal_loss_bwd: null pointer");
+  if (int rc = focal_dtype("hvr_sigmoid_focal_loss_bwd", dtype)) return rc;
+  if (int rc = focal_args("hvr_sigmoid_focal_loss_bwd", N, C, ldl, gamma, alpha)) return rc;
+  return check_launch(run_focal_elem(logits, ldl, (const long long*)targets, d_loss, N, C, gamma, alpha, dtype, d_logits, (hipStream_t)stream),
+                      "hvr_sigmoid_focal_loss_bwd");
+}
+int hvr_focal_loss_splits(int N, int C) {
+  if (N <= 0 || C <= 0) return 0;
+  int S, rows;
+  focal_split(N, C, &S, &rows);
+  return S;
+}
+size_t hvr_focal_loss_workspace_bytes(int N, int C) { return align256((size_t)hvr_focal_loss_splits(N, C) * sizeof(float)); }
+int hvr_focal_loss(const float* logits, int ldl, const int64_t* targets, const float* w, int N, int C, float gamma, float alpha,
+                   float loss_weight, float avg, const int32_t* counts_dev, void* ws, size_t ws_bytes, float* out1, float* d_logits,
+                   void* stream) {
+  if (!logits || !targets || !ws || !out1 || !d_logits) return fail(HVR_EINVAL, "hvr_focal_loss: null pointer");
+  if (int rc = focal_args("hvr_focal_loss", N, C, ldl, gamma, alpha)) return rc;
+  if (!counts_dev && !(avg > 0.f && std::isfinite(avg))) return fail(HVR_EINVAL, "hvr_focal_loss: avg=%g (avg > 0 when no device count is given)", (double)avg);
+  if (!std::isfinite(loss_weight)) return fail(HVR_EINVAL, "hvr_focal_loss: loss_weight=%g is not finite", (double)loss_weight);
+  if (ws_bytes < hvr_focal_loss_workspace_bytes(N, C))
+    return fail(HVR_EWORKSPACE, "hvr_focal_loss: workspace of %zu bytes, %zu needed (ws_bytes >= hvr_focal_loss_workspace_bytes)", ws_bytes,
+                hvr_focal_loss_workspace_bytes(N, C));
+  return check_launch(run_focal_fused(logits, ldl, (const long long*)targets, w, N, C, gamma, alpha, loss_weight, avg, counts_dev, (float*)ws, out1,
+                                      d_logits, (hipStream_t)stream),
+                      "hvr_focal_loss");
+}
+int hvr_rpn_focal_loss(const float* o, int ldo, int A, int rows, const int64_t* labels, const float* label_weights,
+                       const float* bbox_targets, const float* bbox_weights, const int32_t* counts, float beta, float gamma, float alpha,
+                       float w_cls, float w_bbox, float* out2, float* d_o, void* stream) {
+  if (!o || !labels || !label_weights || !bbox_targets || !bbox_weights || !counts || !out2 || !d_o) return fail(HVR_EINVAL, "hvr_rpn_focal_loss: null pointer");
+  if (A <= 0 || rows <= 0 || ldo < 5 * A || !(beta > 0.f))
+    return fail(HVR_EINVAL, "hvr_rpn_focal_loss: A=%d rows=%d ldo=%d beta=%g (A, rows >= 1, ldo >= 5 A, beta > 0)", A, rows, ldo, (double)beta);
+  if ((long)rows * ldo >= (1L << 31)) return fail(HVR_EUNSUPPORTED, "hvr_rpn_focal_loss: rows * ldo = %ld elements (below 2^31)", (long)rows * ldo);
+  if (int rc = focal_args("hvr_rpn_focal_loss", rows, 1, ldo, gamma, alpha)) return rc;
+  if (!std::isfinite(w_cls) || !std::isfinite(w_bbox)) return fail(HVR_EINVAL, "hvr_rpn_focal_loss: loss weights must be finite");
+  return check_launch(run_rpn_focal_loss(o, ldo, A, rows, (const long long*)labels, label_weights, bbox_targets, bbox_weights, counts, beta, gamma,
+                                         alpha, w_cls, w_bbox, out2, d_o, (hipStream_t)stream),
+                      "hvr_rpn_focal_loss");
 }
 
 int hvr_mining_argreduce(const float* aff, int Mq, int Mk, int64_t ld, const int64_t* labels, const int64_t* all_labels, int64_t* out4,

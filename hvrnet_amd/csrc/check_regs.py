@@ -47,6 +47,8 @@ RULES = [
      'one pass over the map'),
     (r'_ZN3hvr\d+gen_attn_', 0, 'gen_attn.hip: a wave keeps its queries, 16 scores and the d / 16 output accumulators in registers '
      'across the key loop, a spill would sit between the two MFMA chains'),
+    (r'_ZN3hvr\d+focal_(?:elem|fused)_', 0, 'focal.hip: a lane keeps one 16-byte piece of logits and its results across three library '
+     'calls per element, a spill would sit on the one pass over the logits'),
 ]
 
 # The tile engine (gemm.hip, gemm_f16.hip) is gated by template arguments, not by name alone.  Kernels that use loads the compiler

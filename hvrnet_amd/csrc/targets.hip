@@ -11,6 +11,8 @@
 
 #include <cstdint>
 
+#include "smooth_l1_dev.h"
+
 namespace hvr {
 hipError_t run_zero_fill(void*, size_t, hipStream_t);   // misc.hip: a kernel, not a memset node (captured graphs)
 
@@ -295,9 +297,9 @@ __global__ __launch_bounds__(1024) void rpn_loss_kernel(const float* __restrict_
     const float sig = x >= 0.f ? 1.f / (1.f + ex) : ex / (1.f + ex);
     drow[a] = (sig - z) * w / avg;
     for (int e = 0; e < 4; ++e) {
-      const float d = row[A + a * 4 + e] - bbox_t[(long)m * 4 + e], ad = fabsf(d), bw = bbox_w[(long)m * 4 + e];
-      lb += (ad < beta ? 0.5f * ad * ad / beta : ad - 0.5f * beta) * bw;
-      drow[A + a * 4 + e] = bw / avg * (ad < beta ? d / beta : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)));
+      float g;
+      lb += smooth_l1_term(row[A + a * 4 + e] - bbox_t[(long)m * 4 + e], beta, bbox_w[(long)m * 4 + e], avg, &g);
+      drow[A + a * 4 + e] = g;
     }
   }
   red[0][tid] = lc; red[1][tid] = lb;

@@ -205,6 +205,12 @@ SYMBOLS = {
     'hvr_box_targets': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     'hvr_rpn_loss': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     'hvr_ce_rows': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'hvr_sigmoid_focal_loss_fwd': (_i, [_vp, _i, _vp, _i, _i, _f, _f, _i, _vp, _vp]),
+    'hvr_sigmoid_focal_loss_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _f, _f, _i, _vp, _vp]),
+    'hvr_focal_loss_splits': (_i, [_i, _i]),
+    'hvr_focal_loss_workspace_bytes': (_sz, [_i, _i]),
+    'hvr_focal_loss': (_i, [_vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _sz, _vp, _vp, _vp]),
+    'hvr_rpn_focal_loss': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
     'hvr_triplet_margin': (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     'hvr_ingest_frame': (_i, [_vp, _i, _i, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'hvr_ingest_frame_flip': (_i, [_vp, _i, _i, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
@@ -1446,6 +1452,85 @@ def rpn_loss(o, A, labels, label_weights, bbox_targets, bbox_weights, counts, be
     d_o = torch.empty_like(o)
     _check(lib().hvr_rpn_loss(_ptr(o), o.shape[1], int(A), rows, _ptr(labels), _ptr(lw), _ptr(bt), _ptr(bw), _ptr(counts),
                               float(beta), _ptr(out2), _ptr(d_o), _stream()), 'hvr_rpn_loss')
+    return out2, d_o
+
+
+# ---- sigmoid focal loss (csrc/focal.hip; the rule: include/hvr_hip.h "Sigmoid focal loss")
+def _focal_logits(logits, targets, what, dtypes):
+    """(N, C, ldl) of a logit matrix [N, C] whose rows are contiguous (any row pitch >= C) with its int64 targets [N]."""
+    assert logits.dim() == 2 and logits.dtype in dtypes, '%s: logits [N, C] in %s, got %s %s' % (what, dtypes, logits.dtype, tuple(logits.shape))
+    N, C = logits.shape
+    assert N >= 1 and C >= 1, '%s: empty logits %s' % (what, tuple(logits.shape))
+    assert logits.stride(1) == 1 or C == 1, '%s: the columns of a row must be contiguous' % what
+    assert targets.dtype == torch.long and targets.is_contiguous() and targets.numel() == N, '%s: one contiguous int64 target per row' % what
+    return N, C, (logits.stride(0) if N > 1 else max(logits.stride(0), C))
+
+
+_FOCAL_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def sigmoid_focal_loss_fwd(logits, targets, gamma, alpha):
+    """logits [N, C] f32 / bf16 / half (rows contiguous, any pitch), targets int64 [N] -> loss f32 [N, C]."""
+    _need_cuda(logits, targets)
+    N, C, ldl = _focal_logits(logits, targets, 'sigmoid_focal_loss_fwd', _FOCAL_DTYPES)
+    loss = torch.empty((N, C), dtype=torch.float32, device=logits.device)
+    _check(lib().hvr_sigmoid_focal_loss_fwd(_ptr(logits), ldl, _ptr(targets), N, C, float(gamma), float(alpha), _dt(logits), _ptr(loss), _stream()),
+           'hvr_sigmoid_focal_loss_fwd')
+    return loss
+
+
+def sigmoid_focal_loss_bwd(logits, targets, d_loss, gamma, alpha):
+    """-> d_logits f32 [N, C] = dl/dx * d_loss (d_loss f32 [N, C] contiguous)."""
+    _need_cuda(logits, targets, d_loss)
+    N, C, ldl = _focal_logits(logits, targets, 'sigmoid_focal_loss_bwd', _FOCAL_DTYPES)
+    assert d_loss.dtype == torch.float32 and d_loss.is_contiguous() and tuple(d_loss.shape) == (N, C)
+    d_logits = torch.empty((N, C), dtype=torch.float32, device=logits.device)
+    _check(lib().hvr_sigmoid_focal_loss_bwd(_ptr(logits), ldl, _ptr(targets), _ptr(d_loss), N, C, float(gamma), float(alpha), _dt(logits),
+                                            _ptr(d_logits), _stream()), 'hvr_sigmoid_focal_loss_bwd')
+    return d_logits
+
+
+def focal_loss_splits(N, C):
+    """The workgroups (one f32 partial each) the reduced form cuts N rows of C columns into: a function of the shape only."""
+    return int(lib().hvr_focal_loss_splits(int(N), int(C)))
+
+
+def focal_loss(logits, targets, weight=None, gamma=2.0, alpha=0.25, loss_weight=1.0, avg=1.0, counts=None, ws=None):
+    """The reduced form in one launch pair: logits f32 [N, C] (rows contiguous, pitch ldl), targets int64 [N], weight f32 [N] or None
+    -> (out1 f32 [1] = loss_weight / avg * sum_n w[n] sum_c l[n][c], d_logits f32 [N, ldl] = loss_weight / avg * w[n] * dl/dx, pitch
+    columns zero).  avg: a float, or with counts (int32 on the device) max(counts[0], 1) read there.  ws: a uint8 workspace to use in
+    place of a fresh one (a test hands a short one in)."""
+    _need_cuda(logits, targets, weight, counts, ws)
+    N, C, ldl = _focal_logits(logits, targets, 'focal_loss', (torch.float32,))
+    if weight is not None:
+        assert weight.dtype == torch.float32 and weight.is_contiguous() and weight.numel() == N, 'focal_loss: one contiguous f32 weight per row'
+    if counts is not None:
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= 1
+    nbytes = lib().hvr_focal_loss_workspace_bytes(N, C)
+    if ws is None:   # a fresh tensor of torch's allocator (a few KB, stream-ordered), so the call can be captured in a graph on any stream
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=logits.device)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous()
+    given = ws.numel()
+    out1 = torch.empty(1, dtype=torch.float32, device=logits.device)
+    d_logits = torch.empty((N, ldl), dtype=torch.float32, device=logits.device)
+    _check(lib().hvr_focal_loss(_ptr(logits), ldl, _ptr(targets), _ptr(weight), N, C, float(gamma), float(alpha), float(loss_weight), float(avg),
+                                _ptr(counts), _ptr(ws), given, _ptr(out1), _ptr(d_logits), _stream()), 'hvr_focal_loss')
+    return out1, d_logits
+
+
+def rpn_focal_loss(o, A, labels, label_weights, bbox_targets, bbox_weights, counts, beta, gamma, alpha, w_cls=1.0, w_bbox=1.0):
+    """rpn_loss for a sampling-free head: o [rows, ldo] f32 -> (out2 = [loss_rpn_cls, loss_rpn_bbox], d_o like o); focal rule on the
+    objectness logits, both terms over max(counts[0], 1)."""
+    _need_cuda(o, labels, label_weights, bbox_targets, bbox_weights, counts)
+    assert o.dtype == torch.float32 and o.dim() == 2 and o.is_contiguous() and labels.dtype == torch.long
+    rows = o.shape[0]
+    assert A >= 1 and o.shape[1] >= 5 * A and counts.dtype == torch.int32 and counts.numel() == 2
+    labels, lw, bt, bw = _loss_operands(labels, label_weights, bbox_targets, bbox_weights, rows * A)
+    counts = counts.contiguous()
+    out2 = torch.empty(2, dtype=torch.float32, device=o.device)
+    d_o = torch.empty_like(o)
+    _check(lib().hvr_rpn_focal_loss(_ptr(o), o.shape[1], int(A), rows, _ptr(labels), _ptr(lw), _ptr(bt), _ptr(bw), _ptr(counts), float(beta),
+                                    float(gamma), float(alpha), float(w_cls), float(w_bbox), _ptr(out2), _ptr(d_o), _stream()), 'hvr_rpn_focal_loss')
     return out2, d_o
 
 

@@ -688,6 +688,44 @@ class RelationFunction(Function):
 relation = RelationFunction.apply
 
 
+class SigmoidFocalLossFunction(Function):
+    """mmdet/ops/sigmoid_focal_loss/sigmoid_focal_loss.py:8-34: the elementwise loss [N, C] of logits [N, C] (f32 / bf16 / half) and
+    int64 targets [N] (0 background, c + 1 class c, < 0 nothing), with the kernels' own backward.  The rule: include/hvr_hip.h."""
+
+    @staticmethod
+    def forward(ctx, input, target, gamma=2.0, alpha=0.25):
+        ctx.save_for_backward(input, target)
+        ctx.gamma, ctx.alpha = float(gamma), float(alpha)
+        loss = native.sigmoid_focal_loss_fwd(input if input.stride(-1) == 1 else input.contiguous(), target.contiguous(), ctx.gamma, ctx.alpha)
+        return loss if input.dtype == torch.float32 else loss.to(input.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_loss):
+        input, target = ctx.saved_tensors
+        d_input = native.sigmoid_focal_loss_bwd(input if input.stride(-1) == 1 else input.contiguous(), target.contiguous(),
+                                                d_loss.float().contiguous(), ctx.gamma, ctx.alpha)
+        return (d_input if input.dtype == torch.float32 else d_input.to(input.dtype)), None, None, None
+
+
+sigmoid_focal_loss = SigmoidFocalLossFunction.apply
+
+
+class SigmoidFocalLoss(nn.Module):
+    """sigmoid_focal_loss.py:40-54: forward returns loss.sum()."""
+
+    def __init__(self, gamma, alpha):
+        super(SigmoidFocalLoss, self).__init__()
+        self.gamma, self.alpha = gamma, alpha
+
+    def forward(self, logits, targets):
+        assert logits.is_cuda
+        return sigmoid_focal_loss(logits, targets, self.gamma, self.alpha).sum()
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(gamma={}, alpha={})'.format(self.gamma, self.alpha)
+
+
 def nms(dets, iou_thr, device_id=None):
     """Same dispatch contract as nms_wrapper.nms: tensor or ndarray in, same type out."""
     if isinstance(dets, torch.Tensor):

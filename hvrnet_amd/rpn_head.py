@@ -33,6 +33,16 @@ class RPNHead(nn.Module, PackedMixin):
             raise NotImplementedError('softmax RPN scores are outside the HVR hot path (configs use sigmoid)')
         self.cls_out_channels = self.num_classes - 1
         self.loss_cls_cfg, self.loss_bbox_cfg = loss_cls, loss_bbox
+        # anchor_head.py:62: a focal / GHM classification loss trains on every assigned anchor, not on a sampled subset.  The two
+        # classification losses this head can run are named here; any other type is refused instead of being trained as BCE.
+        loss_type = loss_cls.get('type', 'CrossEntropyLoss')
+        if loss_type not in ('CrossEntropyLoss', 'FocalLoss'):
+            raise NotImplementedError('RPNHead: loss_cls type %r is not on the HIP path (CrossEntropyLoss or FocalLoss)' % (loss_type,))
+        self.sampling = loss_type not in ('FocalLoss', 'GHMC')
+        if loss_type == 'FocalLoss':
+            from . import losses  # noqa: F401  (registers FocalLoss)
+            from .registry import build_loss
+            self.loss_cls = build_loss(loss_cls)          # validates the dict (use_sigmoid, gamma, alpha, loss_weight) as the reference does
         self.fp16_enabled = False
         self.anchor_generators = [AnchorGenerator(b, anchor_scales, anchor_ratios) for b in self.anchor_base_sizes]
         self.num_anchors = len(self.anchor_ratios) * len(self.anchor_scales)
@@ -122,7 +132,15 @@ class RPNHead(nn.Module, PackedMixin):
         H, W, ld = o_key.shape
         anchors, valid = self._train_anchors((H, W), img_meta, o_key.device)
         labels, label_w, bbox_t, bbox_w, counts = T.anchor_target_single(anchors, valid, gt_bboxes, img_meta, self.target_means,
-                                                                         self.target_stds, cfg, keys=keys, generator=generator)
+                                                                         self.target_stds, cfg, keys=keys, generator=generator,
+                                                                         sampling=self.sampling)
+        if not self.sampling:   # FocalLoss: every assigned anchor, both terms over the positive count (anchor_head.py:194-195)
+            fl = self.loss_cls
+            if fl.reduction != 'mean':
+                raise NotImplementedError('RPNHead: FocalLoss reduction %r (the head averages over the positive count: "mean")' % (fl.reduction,))
+            return TO.rpn_focal_loss(o_key.reshape(H * W, ld), self.num_anchors, labels, label_w, bbox_t, bbox_w, counts,
+                                     beta=self.loss_bbox_cfg.get('beta', 1.0), gamma=fl.gamma, alpha=fl.alpha, w_cls=fl.loss_weight,
+                                     w_bbox=self.loss_bbox_cfg.get('loss_weight', 1.0))
         if self.loss_cls_cfg.get('loss_weight', 1.0) != 1.0 or self.loss_bbox_cfg.get('loss_weight', 1.0) != 1.0:
             raise NotImplementedError('RPN loss weights other than 1.0')
         return TO.rpn_loss(o_key.reshape(H * W, ld), self.num_anchors, labels, label_w, bbox_t, bbox_w, counts,

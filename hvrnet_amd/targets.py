@@ -155,8 +155,22 @@ class RandomSampler(BaseSampler):
 
 
 class PseudoSampler(object):
+    """samplers/pseudo_sampler.py: no sampling at all -- every assigned box is kept, positives = gt_inds > 0, negatives = gt_inds == 0,
+    on the device.  hvr_sample_pos_neg with num = num_expected_pos = n and no neg_pos_ub selects exactly that set, in SamplingResult's
+    order (each class ascending), whatever the keys: no kernel of its own."""
+
     def __init__(self, **kwargs):
-        raise NotImplementedError('PseudoSampler (sampling=False heads: RetinaNet-style) is outside the HVR training path')
+        pass
+
+    @staticmethod
+    def select(gt_inds):
+        """-> (inds int64 [n]: all positives then all negatives, counts int32 [2]); no host copy."""
+        n = gt_inds.numel()
+        return native.sample_pos_neg(gt_inds.contiguous(), gt_inds.new_zeros(n, dtype=torch.float32), n, n, -1.0)
+
+    def sample(self, assign_result, bboxes, gt_bboxes, **kwargs):
+        inds, counts = self.select(assign_result.gt_inds)
+        return SamplingResult(inds, counts, bboxes[:, :4].contiguous(), gt_bboxes, assign_result, 0)
 
 
 class OHEMHNLSampler(BaseSampler):
@@ -204,7 +218,7 @@ def build_assigner(cfg, **kwargs):
 
 def build_sampler(cfg, **kwargs):
     """assign_sampling.py:16-30: a dict builds one sampler, a list of dicts a list (the SELSA config's [Random, OHEMHNL])."""
-    if isinstance(cfg, BaseSampler):
+    if isinstance(cfg, (BaseSampler, PseudoSampler)):
         return cfg
     if isinstance(cfg, (list, tuple)):
         return [_from_dict(c, _SAMPLERS, 'sampler', **kwargs) for c in cfg]
@@ -228,20 +242,26 @@ def anchor_inside_flags(flat_anchors, valid_flags, img_shape, allowed_border=0):
     return inside.to(torch.uint8) if valid_flags is None else (valid_flags.to(torch.uint8) & inside.to(torch.uint8))
 
 
-def anchor_target_single(flat_anchors, valid_flags, gt_bboxes, img_meta, target_means, target_stds, cfg, keys=None, generator=None):
-    """anchor_target_single (anchor_target.py:92-155) with sampling=True, gt_labels=None, unmap_outputs=True, entirely on the
-    device: -> (labels, label_weights, bbox_targets, bbox_weights) over ALL anchors and counts int32 [2] = (#pos, #neg)
-    sampled.  The anchors outside the image are masked instead of compacted, so nothing is unmapped afterwards."""
+def anchor_target_single(flat_anchors, valid_flags, gt_bboxes, img_meta, target_means, target_stds, cfg, keys=None, generator=None,
+                         sampling=True):
+    """anchor_target_single (anchor_target.py:92-155) with gt_labels=None, unmap_outputs=True, entirely on the device: -> (labels,
+    label_weights, bbox_targets, bbox_weights) over ALL anchors and counts int32 [2] = (#pos, #neg) sampled.  The anchors outside the
+    image are masked instead of compacted, so nothing is unmapped afterwards.  sampling=False (anchor_target.py:115-118: a PseudoSampler
+    whatever cfg['sampler'] says) keeps every assigned anchor: counts cover all of them, and the anchors in the ignore band or outside
+    the image carry weight 0."""
     inside = anchor_inside_flags(flat_anchors, valid_flags, img_meta['img_shape'][:2], cfg['allowed_border'])
     assign_result = build_assigner(cfg['assigner']).assign(flat_anchors, gt_bboxes, None, None, valid=inside)
-    sampler = build_sampler(cfg['sampler'])
-    if not isinstance(sampler, RandomSampler) or sampler.add_gt_as_proposals:
-        raise NotImplementedError('anchor targets use a RandomSampler with add_gt_as_proposals=False (train_cfg.rpn.sampler)')
-    n = flat_anchors.shape[0]
-    if keys is None:
-        keys = torch.rand(n, device=flat_anchors.device, generator=generator)
-    inds, counts = native.sample_pos_neg(assign_result.gt_inds, keys.float().contiguous(), sampler.num,
-                                         int(sampler.num * sampler.pos_fraction), sampler.neg_pos_ub)
+    if not sampling:
+        inds, counts = PseudoSampler.select(assign_result.gt_inds)
+    else:
+        sampler = build_sampler(cfg['sampler'])
+        if not isinstance(sampler, RandomSampler) or sampler.add_gt_as_proposals:
+            raise NotImplementedError('anchor targets use a RandomSampler with add_gt_as_proposals=False (train_cfg.rpn.sampler)')
+        n = flat_anchors.shape[0]
+        if keys is None:
+            keys = torch.rand(n, device=flat_anchors.device, generator=generator)
+        inds, counts = native.sample_pos_neg(assign_result.gt_inds, keys.float().contiguous(), sampler.num,
+                                             int(sampler.num * sampler.pos_fraction), sampler.neg_pos_ub)
     out = native.box_targets(flat_anchors, gt_bboxes, None, assign_result.gt_inds, inds, counts, target_means, target_stds,
                              cfg['pos_weight'], scatter=True)
     return out + (counts,)
@@ -251,15 +271,15 @@ def anchor_target(anchor_list, valid_flag_list, gt_bboxes_list, img_metas, targe
                   gt_labels_list=None, label_channels=1, sampling=True, unmap_outputs=True, keys_list=None):
     """anchor_target (anchor_target.py:7-76) for single-level anchors: -> (labels_list, label_weights_list,
     bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg), the *_list entries indexed by level ([num_imgs, N])."""
-    if not sampling or gt_labels_list is not None and any(g is not None for g in gt_labels_list) or not unmap_outputs:
-        raise NotImplementedError('RPN-style targets only: sampling=True, no gt_labels, unmap_outputs=True')
+    if gt_labels_list is not None and any(g is not None for g in gt_labels_list) or not unmap_outputs:
+        raise NotImplementedError('RPN-style targets only: no gt_labels (multi-class dense heads), unmap_outputs=True')
     if any(len(a) != 1 for a in anchor_list):
         raise NotImplementedError('single-level anchors only (anchor_strides=[16])')
     per_img = []
     for i, meta in enumerate(img_metas):
         valid = valid_flag_list[i][0] if valid_flag_list is not None else None
         per_img.append(anchor_target_single(anchor_list[i][0], valid, gt_bboxes_list[i], meta, target_means, target_stds, cfg,
-                                            keys=None if keys_list is None else keys_list[i]))
+                                            keys=None if keys_list is None else keys_list[i], sampling=sampling))
     counts = torch.stack([p[4] for p in per_img]).clamp(min=1).sum(0).tolist()   # anchor_target.py:66-67
     return ([torch.stack([p[0] for p in per_img])], [torch.stack([p[1] for p in per_img])], [torch.stack([p[2] for p in per_img])],
             [torch.stack([p[3] for p in per_img])], int(counts[0]), int(counts[1]))

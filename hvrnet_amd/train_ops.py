@@ -489,6 +489,37 @@ def rpn_loss(o, A, labels, label_weights, bbox_targets, bbox_weights, counts, be
     return dict(total=total, loss_rpn_cls=lc, loss_rpn_bbox=lb)
 
 
+class RpnFocalLossFunction(Function):
+    """AnchorHead.loss_single for a sampling-free head (loss_cls type FocalLoss: anchor_head.py:62,194-195) on the fused RPN head
+    output o [rows, ld] of ONE frame: the focal rule (include/hvr_hip.h) on the objectness logits over ALL assigned anchors, smooth-L1
+    on the deltas, both divided by the positive count max(counts[0], 1) and scaled by their loss weights -> (total [2], loss_rpn_cls,
+    loss_rpn_bbox); only `total` carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, o, A, labels, label_weights, bbox_targets, bbox_weights, counts, beta, gamma, alpha, w_cls, w_bbox):
+        out2, d_o = native.rpn_focal_loss(o.contiguous(), A, labels, label_weights, bbox_targets, bbox_weights, counts, beta, gamma, alpha,
+                                          w_cls, w_bbox)
+        ctx.save_for_backward(d_o)
+        ctx.cols = (0, int(A))
+        loss_cls, loss_bbox = out2[0], out2[1]
+        total = out2.clone()
+        ctx.mark_non_differentiable(loss_cls, loss_bbox)
+        return total, loss_cls, loss_bbox
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_total, g_cls, g_bbox):
+        d_o, = ctx.saved_tensors
+        return (_scale_columns(d_o, g_total, *ctx.cols),) + (None,) * 11
+
+
+def rpn_focal_loss(o, A, labels, label_weights, bbox_targets, bbox_weights, counts, beta=1.0 / 9.0, gamma=2.0, alpha=0.25, w_cls=1.0,
+                   w_bbox=1.0):
+    total, lc, lb = RpnFocalLossFunction.apply(o, int(A), labels, label_weights, bbox_targets, bbox_weights, counts, float(beta), float(gamma),
+                                               float(alpha), float(w_cls), float(w_bbox))
+    return dict(total=total, loss_rpn_cls=lc, loss_rpn_bbox=lb)
+
+
 class TripletMarginFunction(Function):
     """STAND-IN for `TripletNonLocalLoss(margin).compute_loss(q, k, labels, [anchors, pos, neg])` (hrnmp_bbox_head.py:555-561): the
     fork of pytorch_metric_learning that defines it is not in the reference tree, so this is the library's published

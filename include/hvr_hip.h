@@ -964,6 +964,53 @@ int hvr_det_loss_sampled(const float* logits, int ldl, int cls_off, int reg_off,
                          const float* label_weights, const float* bbox_targets, const float* bbox_weights, int R,
                          const int32_t* sel_counts, float beta, float* out3, float* dlogits, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Sigmoid focal loss (mmdet/ops/sigmoid_focal_loss/src/sigmoid_focal_loss_cuda.cu:24,62 SigmoidFocalLossForward / Backward,
+ * mmdet/models/losses/focal_loss.py, losses/utils.py weight_reduce_loss).  THE RULE, stated once: x is a logit, p = sigmoid(x); row n
+ * of N has the int64 target t[n]; column c of C is POSITIVE iff t == c + 1, NEGATIVE iff t >= 0 and t != c + 1, and contributes
+ * NOTHING (loss 0, gradient 0) iff t < 0 (the reference's c1 / c2; t = 0 is background):
+ *   positive:  l = -alpha     (1-p)^gamma log p         dl/dx = -alpha     (1-p)^gamma (1 - p - gamma p log p)
+ *   negative:  l = -(1-alpha) p^gamma     log(1-p)      dl/dx = -(1-alpha) p^gamma     (gamma (1-p) log(1-p) - p)
+ * gamma >= 0 and 0 <= alpha <= 1, anything else is HVR_EINVAL before any launch.  All math is f32 through the stable forms
+ *   e = expf(-|x|), log p = min(x,0) - log1pf(e), log(1-p) = -max(x,0) - log1pf(e), p and 1-p = 1/(1+e) and e/(1+e) by the sign of x,
+ *   q^gamma = expf(gamma log q) on the log already formed (so q^0 = 1 also where q underflows to 0, as powf gives),
+ * with the device library's expf / log1pf, not the fast intrinsics.  The result is finite for every finite x.  DEVIATION: the
+ * reference clamps log p at log FLT_MIN once p underflows (x < -87.3, where its loss stops growing at 87.3 alpha); this build
+ * follows the mathematical value there (the loss goes on as -alpha x).
+ * Reduction (weight_reduce_loss): a per-row weight w[n] multiplies all C columns of the row (focal_loss.py:39-41); 'none' is the
+ * [N, C] matrix, 'sum' its sum, 'mean' the sum divided by N C, or by avg_factor when one is given; then times loss_weight.
+ *   hvr_sigmoid_focal_loss_fwd : logits [N][ldl] (HVR_F32 / HVR_BF16 / HVR_F16; HVR_F16S is refused), row pitch ldl >= C in elements,
+ *                        targets int64 [N] -> loss f32 [N][C].
+ *   hvr_sigmoid_focal_loss_bwd : the same inputs and d_loss f32 [N][C] -> d_logits f32 [N][C] = dl/dx * d_loss.
+ *   hvr_focal_loss     : the reduced form on f32 logits in ONE pass over them: out1[0] = (sum_n w[n] sum_c l[n][c]) * (loss_weight / avg)
+ *                        and d_logits [N][ldl] = (loss_weight / avg * w[n]) * dl/dx, every element written (columns C .. ldl: zero).
+ *                        w is nullable (all ones).  avg is the host float `avg` (> 0), or, when counts_dev (int32, nullable) is given,
+ *                        max(counts_dev[0], 1) read on the device.  The sum is deterministic: S = hvr_focal_loss_splits workgroups of
+ *                        consecutive rows (a function of the shape only, none empty), per-lane partials in row-then-column order, xor
+ *                        shuffles, the four waves through LDS in wave order, ONE f32 partial per workgroup into ws
+ *                        (hvr_focal_loss_workspace_bytes), the partials merged in workgroup order by one wave (lane i takes i, i + 64,
+ *                        ...; xor shuffles).  No float atomics: two calls give the same bits.
+ *   hvr_rpn_focal_loss : hvr_rpn_loss's contract (o [rows][ldo] = A objectness logits then 4A deltas, out2 = (loss_rpn_cls,
+ *                        loss_rpn_bbox), d_o fully written, columns 5A .. ldo zero) for a sampling-free head (anchor_head.py:62): the
+ *                        classification term is the rule above with C = 1, target = label, row weight = label_weights, per anchor;
+ *                        BOTH terms divide by max(counts[0], 1), the positive count (anchor_head.py:194-195, anchor_target.py:66);
+ *                        w_cls / w_bbox are the loss_weight of either term.  The smooth-L1 element is hvr_rpn_loss's own.
+ * 16 bytes per lane where pitch and addresses allow, a scalar form otherwise (any ldl works); no host synchronisation and no
+ * allocation: every entry point can be captured in a graph.  N * ldl < 2^31.
+ * ---------------------------------------------------------------------------------- */
+int hvr_sigmoid_focal_loss_fwd(const void* logits, int ldl, const int64_t* targets, int N, int C, float gamma, float alpha, int dtype,
+                               float* loss, void* stream);
+int hvr_sigmoid_focal_loss_bwd(const void* logits, int ldl, const int64_t* targets, const float* d_loss, int N, int C, float gamma,
+                               float alpha, int dtype, float* d_logits, void* stream);
+int hvr_focal_loss_splits(int N, int C);
+size_t hvr_focal_loss_workspace_bytes(int N, int C);
+int hvr_focal_loss(const float* logits, int ldl, const int64_t* targets, const float* w, int N, int C, float gamma, float alpha,
+                   float loss_weight, float avg, const int32_t* counts_dev, void* ws, size_t ws_bytes, float* out1, float* d_logits,
+                   void* stream);
+int hvr_rpn_focal_loss(const float* o, int ldo, int A, int rows, const int64_t* labels, const float* label_weights,
+                       const float* bbox_targets, const float* bbox_weights, const int32_t* counts, float beta, float gamma, float alpha,
+                       float w_cls, float w_bbox, float* out2, float* d_o, void* stream);
+
 /* Frame ingest: decoded BGR uint8 frame src [src_h][src_pitch bytes] (3 bytes per pixel) -> dst f32 [3][pad_h][pad_w]:
  * bilinear resize to new_w x new_h (OpenCV's 8-bit INTER_LINEAR fixed-point arithmetic, which mmcv.imrescale calls), optional
  * BGR->RGB, (x - mean) / std, zero padding -- the reference's Resize -> Normalize -> Pad -> ImageToTensor
