@@ -15,7 +15,7 @@ from .config import Config, hvr_config, selsa_config  # noqa: F401
 from .detectors import HNMBRCNN, SelsaRCNN  # noqa: F401
 from .ga_rpn_head import GARPNHead  # noqa: F401
 from . import losses  # noqa: F401
-from .losses import FocalLoss  # noqa: F401
+from .losses import (FocalLoss, SmoothL1Loss, BalancedL1Loss, MSELoss, IoULoss, BoundedIoULoss, GHMC, GHMR)  # noqa: F401
 from .ops import ContextBlock, GeneralizedAttention, MaskedConv2d, RoIPool, masked_conv2d, roi_pool, seq_nms, soft_nms  # noqa: F401
 from .pipelines import FrameIngest, FrameIngestAug  # noqa: F401
 from .registry import build_detector  # noqa: F401

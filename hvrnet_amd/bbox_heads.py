@@ -60,6 +60,16 @@ class BBoxHead(nn.Module, PackedMixin):
             raise NotImplementedError('class-specific regression is outside the HVR hot path')
         self.fp16_enabled = False
         self.loss_cls_cfg, self.loss_bbox_cfg = loss_cls, loss_bbox
+        # the box loss the heads run: SmoothL1Loss inside the fused det_loss kernel, BalancedL1Loss through its module beside it (the
+        # plain BBoxHead.loss only); any other type is refused by name instead of being trained as smooth-L1
+        self.loss_bbox_type = loss_bbox.get('type', 'SmoothL1Loss')
+        if self.loss_bbox_type not in ('SmoothL1Loss', 'BalancedL1Loss'):
+            raise NotImplementedError('%s: loss_bbox type %r is not on the HIP path (SmoothL1Loss or BalancedL1Loss)' % (
+                type(self).__name__, self.loss_bbox_type))
+        if self.loss_bbox_type == 'BalancedL1Loss':
+            from . import losses  # noqa: F401  (registers the loss modules)
+            from .registry import build_loss
+            self.loss_bbox = build_loss(loss_bbox)
         self.fc_cls = nn.Linear(in_channels * self.roi_feat_area, num_classes)
         self.fc_reg = nn.Linear(in_channels * self.roi_feat_area, 4)
         self._init_packed()
@@ -114,6 +124,28 @@ class BBoxHead(nn.Module, PackedMixin):
         if cfg is None:
             return bboxes, scores
         return self._nms(bboxes, scores, cfg, defer)
+
+    def refuse_balanced_l1(self, where):
+        """The paths whose kernels fuse the smooth-L1 row loss name the box loss they cannot run, before anything is launched."""
+        if self.loss_bbox_type != 'SmoothL1Loss':
+            raise NotImplementedError('%s: loss_bbox type %r is not on the HIP path of %s (its kernels fuse the smooth-L1 row loss); '
+                                      'SmoothL1Loss only' % (type(self).__name__, self.loss_bbox_type, where))
+
+    def _loss_balanced(self, logits, labels, label_weights, bbox_targets, bbox_weights):
+        """BBoxHead.loss (bbox_head.py:100-130) with loss_bbox type BalancedL1Loss on fused logits [R, ld].  loss_cls and acc are the
+        fused kernel's own, called with zero box weights (the same bits as under SmoothL1Loss).  The box term is the module's reduced
+        kernel on the four delta columns with avg_factor = bbox_targets.size(0): the reference hands it the rows with a label above 0
+        and their weights; here every row goes in with its bbox_weights, which bbox_target leaves at zero on all other rows, so the sum is
+        the same and no row index is read on the host."""
+        from . import train_ops as TO
+        nc = self.num_classes
+        if self.loss_bbox.reduction != 'mean':
+            raise NotImplementedError('%s: BalancedL1Loss reduction %r (the head averages over avg_factor: "mean")' % (
+                type(self).__name__, self.loss_bbox.reduction))
+        d = TO.det_loss(logits, 0, nc, nc, labels, label_weights, bbox_targets, torch.zeros_like(bbox_weights), beta=1.0)
+        box = self.loss_bbox(logits[:, nc:nc + 4], bbox_targets, bbox_weights, avg_factor=float(bbox_targets.size(0)))
+        total = torch.stack([d['total'][0], box])
+        return dict(total=total, loss_cls=d['loss_cls'], loss_bbox=box.detach(), acc=d['acc'])
 
 
 class _RelationHead(BBoxHead):
@@ -333,6 +365,8 @@ class SelsaBBoxHead(_RelationHead):
         """BBoxHead.loss on forward_train's fused logits (bbox_head.py:100-130) -> dict(loss_cls, loss_bbox, acc, total)."""
         from . import train_ops as TO
         nc = self.num_classes
+        if self.loss_bbox_type == 'BalancedL1Loss':
+            return self._loss_balanced(logits, labels, label_weights, bbox_targets, bbox_weights)
         return TO.det_loss(logits, 0, nc, nc, labels, label_weights, bbox_targets, bbox_weights, beta=1.0)
 
 
@@ -469,6 +503,7 @@ class HRNMPBBoxHead(_RelationHead):
         """HRNMPBBoxHead.loss (hrnmp_bbox_head.py:970-1007) on the fused logits of each branch:
         -> dict(loss_cls_1, acc_1, loss_bbox_1, loss_cls_2, acc_2, loss_bbox_2); the loss entries carry the gradient."""
         from . import train_ops as TO
+        self.refuse_balanced_l1('HRNMPBBoxHead.loss')
         nc = self.num_classes
         out = dict()
         for i, logits in enumerate(logits_list):

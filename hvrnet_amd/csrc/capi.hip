@@ -55,6 +55,17 @@ hipError_t run_focal_fused(const float*, int, const long long*, const float*, in
                            hipStream_t);
 hipError_t run_rpn_focal_loss(const float*, int, int, int, const long long*, const float*, const float*, const float*, const int*, float, float, float,
                               float, float, float*, float*, hipStream_t);
+hipError_t run_reg_elem(int, const float*, int, const float*, const float*, int, int, const float*, float*, hipStream_t);
+hipError_t run_reg_fused(int, const float*, int, const float*, const float*, int, int, const float*, float, float, const int*, float*, float*, float*,
+                         hipStream_t);
+hipError_t run_box_elem(int, const float*, const float*, const float*, int, float, float, float*, hipStream_t);
+hipError_t run_box_fused(int, const float*, const float*, const float*, int, float, float, float, float, const int*, float*, float*, float*, hipStream_t);
+void ghm_split(int N, int C, int* S, long* per);
+size_t ghm_workspace_words(int N, int C);
+hipError_t run_ghmc(const float*, const float*, const long long*, const float*, int, int, int, const float*, int, float, float*, float, void*, float*,
+                    float*, hipStream_t);
+hipError_t run_ghmr(const float*, const float*, const float*, int, int, float, const float*, int, float, float*, float, void*, float*, float*,
+                    hipStream_t);
 hipError_t run_triplet_margin(const void*, long, const void*, long, int, int, int, const long long*, const long long*, const long long*, int,
                               float, int, float*, float*, float*, float*, hipStream_t);
 hipError_t run_ingest(const uint8_t*, int, int, long, float*, int, int, int, int, const float*, const float*, int, int, hipStream_t);
@@ -1646,6 +1657,119 @@ int hvr_rpn_focal_loss(const float* o, int ldo, int A, int rows, const int64_t* 
   return check_launch(run_rpn_focal_loss(o, ldo, A, rows, (const long long*)labels, label_weights, bbox_targets, bbox_weights, counts, beta, gamma,
                                          alpha, w_cls, w_bbox, out2, d_o, (hipStream_t)stream),
                       "hvr_rpn_focal_loss");
+}
+
+// ---- regression, IoU and GHM losses (reg_loss.hip, ghm.hip; the rules: include/hvr_hip.h)
+static int reg_args(const char* what, int rule, int N, int D, int ldp, float beta, float alpha, float gamma, float* prm4) {
+  if (rule < HVR_REG_SMOOTH_L1 || rule > HVR_REG_MSE) return fail(HVR_EINVAL, "%s: rule %d (HVR_REG_SMOOTH_L1 / _BALANCED_L1 / _MSE)", what, rule);
+  if (N < 1 || D < 1) return fail(HVR_EINVAL, "%s: N=%d rows of D=%d columns (N, D >= 1)", what, N, D);
+  if (ldp < D) return fail(HVR_EINVAL, "%s: row pitch ldp=%d is below D=%d (ldp >= D)", what, ldp, D);
+  if ((long)N * ldp >= (1L << 31)) return fail(HVR_EUNSUPPORTED, "%s: N * ldp = %ld elements (below 2^31)", what, (long)N * ldp);
+  prm4[0] = beta; prm4[1] = alpha; prm4[2] = gamma; prm4[3] = 0.f;
+  if (rule != HVR_REG_MSE && !(beta > 0.f && std::isfinite(beta))) return fail(HVR_EINVAL, "%s: beta=%g (beta > 0)", what, (double)beta);
+  if (rule == HVR_REG_BALANCED_L1) {
+    if (!(alpha > 0.f && std::isfinite(alpha)) || !(gamma > 0.f && std::isfinite(gamma)))
+      return fail(HVR_EINVAL, "%s: alpha=%g gamma=%g (alpha, gamma > 0)", what, (double)alpha, (double)gamma);
+    const double b = std::exp((double)gamma / (double)alpha) - 1.0;      // formed in f64, rounded once
+    if (!(b < 3e38)) return fail(HVR_EINVAL, "%s: e^(gamma / alpha) - 1 = %g does not fit f32", what, b);
+    prm4[3] = (float)b;
+  }
+  return HVR_OK;
+}
+static int reduce_args(const char* what, float loss_weight, float avg, const int32_t* counts_dev, size_t ws_bytes, size_t need) {
+  if (!counts_dev && !(avg > 0.f && std::isfinite(avg))) return fail(HVR_EINVAL, "%s: avg=%g (avg > 0 when no device count is given)", what, (double)avg);
+  if (!std::isfinite(loss_weight)) return fail(HVR_EINVAL, "%s: loss_weight=%g is not finite", what, (double)loss_weight);
+  if (ws_bytes < need) return fail(HVR_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed", what, ws_bytes, need);
+  return HVR_OK;
+}
+int hvr_reg_loss_fwd(int rule, const float* pred, int ldp, const float* target, int N, int D, float beta, float alpha, float gamma, float* loss,
+                     void* stream) {
+  if (!pred || !target || !loss) return fail(HVR_EINVAL, "hvr_reg_loss_fwd: null pointer");
+  float prm[4];
+  if (int rc = reg_args("hvr_reg_loss_fwd", rule, N, D, ldp, beta, alpha, gamma, prm)) return rc;
+  return check_launch(run_reg_elem(rule, pred, ldp, target, nullptr, N, D, prm, loss, (hipStream_t)stream), "hvr_reg_loss_fwd");
+}
+int hvr_reg_loss_bwd(int rule, const float* pred, int ldp, const float* target, const float* d_loss, int N, int D, float beta, float alpha,
+                     float gamma, float* d_pred, void* stream) {
+  if (!pred || !target || !d_loss || !d_pred) return fail(HVR_EINVAL, "hvr_reg_loss_bwd: null pointer");
+  float prm[4];
+  if (int rc = reg_args("hvr_reg_loss_bwd", rule, N, D, ldp, beta, alpha, gamma, prm)) return rc;
+  return check_launch(run_reg_elem(rule, pred, ldp, target, d_loss, N, D, prm, d_pred, (hipStream_t)stream), "hvr_reg_loss_bwd");
+}
+int hvr_reg_loss_splits(int N, int D) { return hvr_focal_loss_splits(N, D); }
+size_t hvr_reg_loss_workspace_bytes(int N, int D) { return align256((size_t)hvr_reg_loss_splits(N, D) * sizeof(float)); }
+int hvr_reg_loss(int rule, const float* pred, int ldp, const float* target, const float* w, int N, int D, float beta, float alpha, float gamma,
+                 float loss_weight, float avg, const int32_t* counts_dev, void* ws, size_t ws_bytes, float* out1, float* d_pred, void* stream) {
+  if (!pred || !target || !ws || !out1 || !d_pred) return fail(HVR_EINVAL, "hvr_reg_loss: null pointer");
+  float prm[4];
+  if (int rc = reg_args("hvr_reg_loss", rule, N, D, ldp, beta, alpha, gamma, prm)) return rc;
+  if (int rc = reduce_args("hvr_reg_loss", loss_weight, avg, counts_dev, ws_bytes, hvr_reg_loss_workspace_bytes(N, D))) return rc;
+  return check_launch(run_reg_fused(rule, pred, ldp, target, w, N, D, prm, loss_weight, avg, counts_dev, (float*)ws, out1, d_pred, (hipStream_t)stream),
+                      "hvr_reg_loss");
+}
+static int box_args(const char* what, int rule, int n, float beta, float eps) {
+  if (rule < HVR_BOX_IOU || rule > HVR_BOX_BOUNDED_IOU) return fail(HVR_EINVAL, "%s: rule %d (HVR_BOX_IOU / HVR_BOX_BOUNDED_IOU)", what, rule);
+  if (n < 1 || n >= (1 << 29)) return fail(HVR_EINVAL, "%s: n=%d box pairs (1 <= n < 2^29)", what, n);
+  if (!(eps > 0.f && std::isfinite(eps))) return fail(HVR_EINVAL, "%s: eps=%g (eps > 0)", what, (double)eps);
+  if (rule == HVR_BOX_BOUNDED_IOU && !(beta > 0.f && std::isfinite(beta))) return fail(HVR_EINVAL, "%s: beta=%g (beta > 0)", what, (double)beta);
+  return HVR_OK;
+}
+int hvr_box_loss_fwd(int rule, const float* pred, const float* target, int n, float beta, float eps, float* loss, void* stream) {
+  if (!pred || !target || !loss) return fail(HVR_EINVAL, "hvr_box_loss_fwd: null pointer");
+  if (int rc = box_args("hvr_box_loss_fwd", rule, n, beta, eps)) return rc;
+  return check_launch(run_box_elem(rule, pred, target, nullptr, n, beta, eps, loss, (hipStream_t)stream), "hvr_box_loss_fwd");
+}
+int hvr_box_loss_bwd(int rule, const float* pred, const float* target, const float* d_loss, int n, float beta, float eps, float* d_pred,
+                     void* stream) {
+  if (!pred || !target || !d_loss || !d_pred) return fail(HVR_EINVAL, "hvr_box_loss_bwd: null pointer");
+  if (int rc = box_args("hvr_box_loss_bwd", rule, n, beta, eps)) return rc;
+  return check_launch(run_box_elem(rule, pred, target, d_loss, n, beta, eps, d_pred, (hipStream_t)stream), "hvr_box_loss_bwd");
+}
+int hvr_box_loss_splits(int n) { return hvr_focal_loss_splits(n, 4); }
+size_t hvr_box_loss_workspace_bytes(int n) { return align256((size_t)hvr_box_loss_splits(n) * sizeof(float)); }
+int hvr_box_loss(int rule, const float* pred, const float* target, const float* w, int n, float beta, float eps, float loss_weight, float avg,
+                 const int32_t* counts_dev, void* ws, size_t ws_bytes, float* out1, float* d_pred, void* stream) {
+  if (!pred || !target || !ws || !out1 || !d_pred) return fail(HVR_EINVAL, "hvr_box_loss: null pointer");
+  if (int rc = box_args("hvr_box_loss", rule, n, beta, eps)) return rc;
+  if (int rc = reduce_args("hvr_box_loss", loss_weight, avg, counts_dev, ws_bytes, hvr_box_loss_workspace_bytes(n))) return rc;
+  return check_launch(run_box_fused(rule, pred, target, w, n, beta, eps, loss_weight, avg, counts_dev, (float*)ws, out1, d_pred, (hipStream_t)stream),
+                      "hvr_box_loss");
+}
+static int ghm_args(const char* what, int N, int C, int bins, float momentum, const float* acc_sum, float loss_weight, size_t ws_bytes) {
+  if (N < 1 || C < 1 || (long)N * C >= (1L << 31)) return fail(HVR_EINVAL, "%s: N=%d x C=%d elements (N, C >= 1, N C < 2^31)", what, N, C);
+  if (bins < 1 || bins > 64) return fail(HVR_EINVAL, "%s: bins=%d (1 .. 64)", what, bins);
+  if (!(momentum >= 0.f && momentum < 1.f)) return fail(HVR_EINVAL, "%s: momentum=%g (0 <= momentum < 1)", what, (double)momentum);
+  if (momentum > 0.f && !acc_sum) return fail(HVR_EINVAL, "%s: momentum > 0 needs the acc_sum buffer", what);
+  if (!std::isfinite(loss_weight)) return fail(HVR_EINVAL, "%s: loss_weight=%g is not finite", what, (double)loss_weight);
+  if (ws_bytes < hvr_ghm_workspace_bytes(N, C))
+    return fail(HVR_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed (ws_bytes >= hvr_ghm_workspace_bytes)", what, ws_bytes, hvr_ghm_workspace_bytes(N, C));
+  return HVR_OK;
+}
+int hvr_ghm_splits(int N, int C) {
+  if (N <= 0 || C <= 0) return 0;
+  int S;
+  long per;
+  ghm_split(N, C, &S, &per);
+  return S;
+}
+size_t hvr_ghm_workspace_bytes(int N, int C) { return N <= 0 || C <= 0 ? 0 : align256(ghm_workspace_words(N, C) * 4); }
+int hvr_ghmc_loss(const float* logits, const float* target, const int64_t* labels, const float* weight, int weight_per_row, int N, int C,
+                  const float* edges, int bins, float momentum, float* acc_sum, float loss_weight, void* ws, size_t ws_bytes, float* out1,
+                  float* d_logits, void* stream) {
+  if (!logits || !weight || !edges || !ws || !out1 || !d_logits) return fail(HVR_EINVAL, "hvr_ghmc_loss: null pointer");
+  if (!target == !labels) return fail(HVR_EINVAL, "hvr_ghmc_loss: exactly one of target (f32 [N][C]) and labels (int64 [N])");
+  if (int rc = ghm_args("hvr_ghmc_loss", N, C, bins, momentum, acc_sum, loss_weight, ws_bytes)) return rc;
+  return check_launch(run_ghmc(logits, target, (const long long*)labels, weight, weight_per_row ? 1 : 0, N, C, edges, bins, momentum, acc_sum,
+                               loss_weight, ws, out1, d_logits, (hipStream_t)stream),
+                      "hvr_ghmc_loss");
+}
+int hvr_ghmr_loss(const float* pred, const float* target, const float* weight, int N, int C, float mu, const float* edges, int bins,
+                  float momentum, float* acc_sum, float loss_weight, void* ws, size_t ws_bytes, float* out1, float* d_pred, void* stream) {
+  if (!pred || !target || !weight || !edges || !ws || !out1 || !d_pred) return fail(HVR_EINVAL, "hvr_ghmr_loss: null pointer");
+  if (!(mu > 0.f && std::isfinite(mu))) return fail(HVR_EINVAL, "hvr_ghmr_loss: mu=%g (mu > 0)", (double)mu);
+  if (int rc = ghm_args("hvr_ghmr_loss", N, C, bins, momentum, acc_sum, loss_weight, ws_bytes)) return rc;
+  return check_launch(run_ghmr(pred, target, weight, N, C, mu, edges, bins, momentum, acc_sum, loss_weight, ws, out1, d_pred, (hipStream_t)stream),
+                      "hvr_ghmr_loss");
 }
 
 int hvr_mining_argreduce(const float* aff, int Mq, int Mk, int64_t ld, const int64_t* labels, const int64_t* all_labels, int64_t* out4,

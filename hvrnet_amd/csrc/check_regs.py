@@ -49,6 +49,9 @@ RULES = [
      'across the key loop, a spill would sit between the two MFMA chains'),
     (r'_ZN3hvr\d+focal_(?:elem|fused)_', 0, 'focal.hip: a lane keeps one 16-byte piece of logits and its results across three library '
      'calls per element, a spill would sit on the one pass over the logits'),
+    (r'_ZN3hvr\d+(?:reg_elem|box_pair)_', 0, 'reg_loss.hip: a lane keeps 16-byte pieces of pred, target and weight and the four gradients of a box '
+     'pair in registers, a spill would sit on the one pass over the inputs'),
+    (r'_ZN3hvr\d+ghm_(?:hist|loss)_', 0, 'ghm.hip: two passes over the elements with a library call each, a spill would sit on the pass'),
 ]
 
 # The tile engine (gemm.hip, gemm_f16.hip) is gated by template arguments, not by name alone.  Kernels that use loads the compiler

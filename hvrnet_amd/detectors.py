@@ -767,6 +767,8 @@ class SelsaRCNN(_WindowDetector):
             raise NotImplementedError('gt_bboxes_ignore is not on the HIP training path (ignore_iof_thr = -1 in both configs)')
         keys = keys or {}
         rcnn_cfg = self.train_cfg.rcnn
+        if isinstance(rcnn_cfg.sampler, (list, tuple)):     # the OHEM form: its ranking and loss kernels fuse the smooth-L1 row loss
+            self.bbox_head.refuse_balanced_l1('the OHEM form (train_cfg.rcnn.sampler is a list)')
         c4 = self.backbone.forward_train_nhwc(img)
         losses = dict()
         if self.with_rpn:
@@ -912,6 +914,7 @@ class HNMBRCNN(_WindowDetector):
         keys: optional {'rcnn': [[f32 [num_gt + nms_post] per frame] per chosen video]} replacing the sampler's draws.
         -> dict(loss_cls_1, acc_1, loss_bbox_1, loss_cls_2, acc_2, loss_bbox_2, loss_trip)."""
         from . import ops, targets as T
+        self.bbox_head.refuse_balanced_l1('HRNMPBBoxHead.loss')      # its two-branch loss fuses the smooth-L1 row loss: refused before anything is launched
         layer = self._train_roi_layer()
         if self.train_cfg is None:
             raise ValueError('this detector was built without train_cfg (hvrnet_amd.config.hvr_train_config, or the reference config file)')

@@ -211,6 +211,20 @@ SYMBOLS = {
     'hvr_focal_loss_workspace_bytes': (_sz, [_i, _i]),
     'hvr_focal_loss': (_i, [_vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _sz, _vp, _vp, _vp]),
     'hvr_rpn_focal_loss': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
+    'hvr_reg_loss_fwd': (_i, [_i, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
+    'hvr_reg_loss_bwd': (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
+    'hvr_reg_loss_splits': (_i, [_i, _i]),
+    'hvr_reg_loss_workspace_bytes': (_sz, [_i, _i]),
+    'hvr_reg_loss': (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _sz, _vp, _vp, _vp]),
+    'hvr_box_loss_fwd': (_i, [_i, _vp, _vp, _i, _f, _f, _vp, _vp]),
+    'hvr_box_loss_bwd': (_i, [_i, _vp, _vp, _vp, _i, _f, _f, _vp, _vp]),
+    'hvr_box_loss_splits': (_i, [_i]),
+    'hvr_box_loss_workspace_bytes': (_sz, [_i]),
+    'hvr_box_loss': (_i, [_i, _vp, _vp, _vp, _i, _f, _f, _f, _f, _vp, _vp, _sz, _vp, _vp, _vp]),
+    'hvr_ghm_splits': (_i, [_i, _i]),
+    'hvr_ghm_workspace_bytes': (_sz, [_i, _i]),
+    'hvr_ghmc_loss': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _f, _vp, _f, _vp, _sz, _vp, _vp, _vp]),
+    'hvr_ghmr_loss': (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _i, _f, _vp, _f, _vp, _sz, _vp, _vp, _vp]),
     'hvr_triplet_margin': (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     'hvr_ingest_frame': (_i, [_vp, _i, _i, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'hvr_ingest_frame_flip': (_i, [_vp, _i, _i, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
@@ -1532,6 +1546,185 @@ def rpn_focal_loss(o, A, labels, label_weights, bbox_targets, bbox_weights, coun
     _check(lib().hvr_rpn_focal_loss(_ptr(o), o.shape[1], int(A), rows, _ptr(labels), _ptr(lw), _ptr(bt), _ptr(bw), _ptr(counts), float(beta),
                                     float(gamma), float(alpha), float(w_cls), float(w_bbox), _ptr(out2), _ptr(d_o), _stream()), 'hvr_rpn_focal_loss')
     return out2, d_o
+
+
+# ---- regression, IoU and GHM losses (csrc/reg_loss.hip, csrc/ghm.hip; the rules: include/hvr_hip.h)
+REG_RULES = dict(smooth_l1=0, balanced_l1=1, mse=2)
+BOX_RULES = dict(iou=0, bounded_iou=1)
+
+
+def _reg_pair(pred, target, what):
+    """(N, D, ldp) of pred f32 [N, D] (rows contiguous, any row pitch >= D) and a dense f32 target of the same shape."""
+    assert pred.dim() == 2 and pred.dtype == torch.float32 and pred.numel() > 0, '%s: pred f32 [N, D], got %s %s' % (what, pred.dtype, tuple(pred.shape))
+    N, D = pred.shape
+    assert pred.stride(1) == 1 or D == 1, '%s: pred rows must be contiguous' % what
+    assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (N, D), '%s: target f32 [N, D] contiguous' % what
+    return N, D, (pred.stride(0) if N > 1 else max(pred.stride(0), D))
+
+
+def _dense(t, shape, what):
+    assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), '%s: f32 %s contiguous, got %s %s' % (
+        what, tuple(shape), t.dtype, tuple(t.shape))
+
+
+def _loss_ws(nbytes, ws, device):
+    if ws is None:   # a fresh tensor of torch's allocator (stream-ordered), so the call can be captured in a graph on any stream
+        ws = torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous()
+    return ws
+
+
+def _avg_counts(counts):
+    if counts is not None:
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= 1
+    return counts
+
+
+def reg_loss_fwd(rule, pred, target, beta=1.0, alpha=0.5, gamma=1.5):
+    """rule 'smooth_l1' / 'balanced_l1' / 'mse': pred f32 [N, D] (any row pitch), target f32 [N, D] -> loss f32 [N, D]."""
+    _need_cuda(pred, target)
+    N, D, ldp = _reg_pair(pred, target, 'reg_loss_fwd')
+    loss = torch.empty((N, D), dtype=torch.float32, device=pred.device)
+    _check(lib().hvr_reg_loss_fwd(REG_RULES[rule], _ptr(pred), ldp, _ptr(target), N, D, float(beta), float(alpha), float(gamma), _ptr(loss),
+                                  _stream()), 'hvr_reg_loss_fwd')
+    return loss
+
+
+def reg_loss_bwd(rule, pred, target, d_loss, beta=1.0, alpha=0.5, gamma=1.5):
+    """-> d_pred f32 [N, D] = dl/dpred * d_loss (d_loss f32 [N, D] contiguous)."""
+    _need_cuda(pred, target, d_loss)
+    N, D, ldp = _reg_pair(pred, target, 'reg_loss_bwd')
+    _dense(d_loss, (N, D), 'reg_loss_bwd: d_loss')
+    d_pred = torch.empty((N, D), dtype=torch.float32, device=pred.device)
+    _check(lib().hvr_reg_loss_bwd(REG_RULES[rule], _ptr(pred), ldp, _ptr(target), _ptr(d_loss), N, D, float(beta), float(alpha), float(gamma),
+                                  _ptr(d_pred), _stream()), 'hvr_reg_loss_bwd')
+    return d_pred
+
+
+def reg_loss_splits(N, D):
+    return int(lib().hvr_reg_loss_splits(int(N), int(D)))
+
+
+def reg_loss(rule, pred, target, weight=None, beta=1.0, alpha=0.5, gamma=1.5, loss_weight=1.0, avg=1.0, counts=None, ws=None):
+    """The reduced form in one pass: -> (out1 f32 [1] = loss_weight / avg * sum w l, d_pred f32 [N, D] = loss_weight / avg * w * dl/dpred).
+    weight f32 [N, D] or None.  avg: a float, or with counts (int32 on the device) max(counts[0], 1) read there."""
+    _need_cuda(pred, target, weight, counts, ws)
+    N, D, ldp = _reg_pair(pred, target, 'reg_loss')
+    if weight is not None:
+        _dense(weight, (N, D), 'reg_loss: weight')
+    counts = _avg_counts(counts)
+    ws = _loss_ws(lib().hvr_reg_loss_workspace_bytes(N, D), ws, pred.device)
+    out1 = torch.empty(1, dtype=torch.float32, device=pred.device)
+    d_pred = torch.empty((N, D), dtype=torch.float32, device=pred.device)
+    _check(lib().hvr_reg_loss(REG_RULES[rule], _ptr(pred), ldp, _ptr(target), _ptr(weight), N, D, float(beta), float(alpha), float(gamma),
+                              float(loss_weight), float(avg), _ptr(counts), _ptr(ws), ws.numel(), _ptr(out1), _ptr(d_pred), _stream()), 'hvr_reg_loss')
+    return out1, d_pred
+
+
+def _box_pair(pred, target, what):
+    assert pred.dim() == 2 and pred.shape[1] == 4 and pred.shape[0] > 0 and pred.dtype == torch.float32 and pred.is_contiguous(), \
+        '%s: pred f32 [n, 4] contiguous, got %s %s' % (what, pred.dtype, tuple(pred.shape))
+    _dense(target, pred.shape, what + ': target')
+    return pred.shape[0]
+
+
+def _box_loss_shape(rule, n):
+    return (n,) if rule == 'iou' else (n, 4)
+
+
+def box_loss_fwd(rule, pred, target, beta=0.2, eps=1e-3):
+    """rule 'iou' / 'bounded_iou': pred, target f32 [n, 4] -> loss f32 [n] / [n, 4]."""
+    _need_cuda(pred, target)
+    n = _box_pair(pred, target, 'box_loss_fwd')
+    loss = torch.empty(_box_loss_shape(rule, n), dtype=torch.float32, device=pred.device)
+    _check(lib().hvr_box_loss_fwd(BOX_RULES[rule], _ptr(pred), _ptr(target), n, float(beta), float(eps), _ptr(loss), _stream()), 'hvr_box_loss_fwd')
+    return loss
+
+
+def box_loss_bwd(rule, pred, target, d_loss, beta=0.2, eps=1e-3):
+    """-> d_pred f32 [n, 4] (d_loss in the loss's shape)."""
+    _need_cuda(pred, target, d_loss)
+    n = _box_pair(pred, target, 'box_loss_bwd')
+    _dense(d_loss, _box_loss_shape(rule, n), 'box_loss_bwd: d_loss')
+    d_pred = torch.empty((n, 4), dtype=torch.float32, device=pred.device)
+    _check(lib().hvr_box_loss_bwd(BOX_RULES[rule], _ptr(pred), _ptr(target), _ptr(d_loss), n, float(beta), float(eps), _ptr(d_pred), _stream()),
+           'hvr_box_loss_bwd')
+    return d_pred
+
+
+def box_loss_splits(n):
+    return int(lib().hvr_box_loss_splits(int(n)))
+
+
+def box_loss(rule, pred, target, weight=None, beta=0.2, eps=1e-3, loss_weight=1.0, avg=1.0, counts=None, ws=None):
+    """The reduced form: -> (out1 f32 [1], d_pred f32 [n, 4]).  weight f32 in the loss's shape ([n] for 'iou', [n, 4] for 'bounded_iou') or None."""
+    _need_cuda(pred, target, weight, counts, ws)
+    n = _box_pair(pred, target, 'box_loss')
+    if weight is not None:
+        _dense(weight, _box_loss_shape(rule, n), 'box_loss: weight')
+    counts = _avg_counts(counts)
+    ws = _loss_ws(lib().hvr_box_loss_workspace_bytes(n), ws, pred.device)
+    out1 = torch.empty(1, dtype=torch.float32, device=pred.device)
+    d_pred = torch.empty((n, 4), dtype=torch.float32, device=pred.device)
+    _check(lib().hvr_box_loss(BOX_RULES[rule], _ptr(pred), _ptr(target), _ptr(weight), n, float(beta), float(eps), float(loss_weight), float(avg),
+                              _ptr(counts), _ptr(ws), ws.numel(), _ptr(out1), _ptr(d_pred), _stream()), 'hvr_box_loss')
+    return out1, d_pred
+
+
+def ghm_splits(N, C):
+    return int(lib().hvr_ghm_splits(int(N), int(C)))
+
+
+def ghm_workspace_views(ws, bins):
+    """(counts int32 [bins], w f32 [bins], tot f32 [1], n int32 [1]) views of a GHM workspace (the layout: include/hvr_hip.h)."""
+    wi, wf = ws[:768].view(torch.int32), ws[:768].view(torch.float32)
+    return wi[:bins], wf[64:64 + bins], wf[128:129], wi[129:130]
+
+
+def _ghm_common(pred, edges, bins, momentum, acc_sum, what):
+    assert pred.dim() == 2 and pred.dtype == torch.float32 and pred.is_contiguous() and pred.numel() > 0, '%s: pred f32 [N, C] contiguous' % what
+    _dense(edges, (bins + 1,), what + ': edges')
+    if momentum > 0:
+        _dense(acc_sum, (bins,), what + ': acc_sum')
+    return pred.shape
+
+
+def ghmc_loss(logits, target, weight, edges, momentum=0.0, acc_sum=None, loss_weight=1.0, ws=None):
+    """logits f32 [N, C]; target f32 [N, C] with weight f32 [N, C], or int64 labels [N] (label k >= 1 marks column k - 1) with weight
+    f32 [N] per row -> (out1 f32 [1], d_logits f32 [N, C], ws); acc_sum f32 [bins] is updated in place when momentum > 0."""
+    _need_cuda(logits, target, weight, edges, acc_sum, ws)
+    bins = edges.numel() - 1
+    N, C = _ghm_common(logits, edges, bins, momentum, acc_sum, 'ghmc_loss')
+    by_label = target.dtype == torch.long
+    if by_label:
+        assert target.is_contiguous() and tuple(target.shape) == (N,), 'ghmc_loss: int64 labels [N]'
+        _dense(weight, (N,), 'ghmc_loss: label weights')
+    else:
+        _dense(target, (N, C), 'ghmc_loss: target')
+        _dense(weight, (N, C), 'ghmc_loss: weight')
+    ws = _loss_ws(lib().hvr_ghm_workspace_bytes(N, C), ws, logits.device)
+    out1 = torch.empty(1, dtype=torch.float32, device=logits.device)
+    d = torch.empty((N, C), dtype=torch.float32, device=logits.device)
+    _check(lib().hvr_ghmc_loss(_ptr(logits), None if by_label else _ptr(target), _ptr(target) if by_label else None, _ptr(weight), int(by_label),
+                               N, C, _ptr(edges), bins, float(momentum), _ptr(acc_sum) if momentum > 0 else None, float(loss_weight), _ptr(ws),
+                               ws.numel(), _ptr(out1), _ptr(d), _stream()), 'hvr_ghmc_loss')
+    return out1, d, ws
+
+
+def ghmr_loss(pred, target, weight, edges, mu=0.02, momentum=0.0, acc_sum=None, loss_weight=1.0, ws=None):
+    """pred, target, weight f32 [N, C] -> (out1 f32 [1], d_pred f32 [N, C], ws); acc_sum as in ghmc_loss."""
+    _need_cuda(pred, target, weight, edges, acc_sum, ws)
+    bins = edges.numel() - 1
+    N, C = _ghm_common(pred, edges, bins, momentum, acc_sum, 'ghmr_loss')
+    _dense(target, (N, C), 'ghmr_loss: target')
+    _dense(weight, (N, C), 'ghmr_loss: weight')
+    ws = _loss_ws(lib().hvr_ghm_workspace_bytes(N, C), ws, pred.device)
+    out1 = torch.empty(1, dtype=torch.float32, device=pred.device)
+    d = torch.empty((N, C), dtype=torch.float32, device=pred.device)
+    _check(lib().hvr_ghmr_loss(_ptr(pred), _ptr(target), _ptr(weight), N, C, float(mu), _ptr(edges), bins, float(momentum),
+                               _ptr(acc_sum) if momentum > 0 else None, float(loss_weight), _ptr(ws), ws.numel(), _ptr(out1), _ptr(d), _stream()),
+           'hvr_ghmr_loss')
+    return out1, d, ws
 
 
 def ce_rows(logits, cls_off, ncls, labels):

@@ -711,6 +711,74 @@ class SigmoidFocalLossFunction(Function):
 sigmoid_focal_loss = SigmoidFocalLossFunction.apply
 
 
+def _rows(t):
+    """A 2-D f32 view whose rows are contiguous (any row pitch), or a contiguous copy."""
+    t = t if t.dtype == torch.float32 else t.float()
+    return t if t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1) and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+class RegLossFunction(Function):
+    """The elementwise ('none') form of the regression losses (csrc/reg_loss.hip; the rules: include/hvr_hip.h): pred, target f32
+    [N, D] -> loss [N, D], with the kernels' own backward (to pred only)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, rule, beta, alpha, gamma):
+        assert pred.dim() == 2 and pred.shape == target.shape, '%s: pred and target [N, D] of one shape' % rule
+        p, t = _rows(pred), target.float().contiguous()
+        ctx.save_for_backward(p, t)
+        ctx.args = (rule, float(beta), float(alpha), float(gamma))
+        return native.reg_loss_fwd(rule, p, t, *ctx.args[1:])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_loss):
+        p, t = ctx.saved_tensors
+        return (native.reg_loss_bwd(ctx.args[0], p, t, d_loss.float().contiguous(), *ctx.args[1:]),) + (None,) * 5
+
+
+class BoxLossFunction(Function):
+    """The elementwise form of the box-pair losses: pred, target f32 [n, 4] -> loss [n] ('iou') / [n, 4] ('bounded_iou')."""
+
+    @staticmethod
+    def forward(ctx, pred, target, rule, beta, eps):
+        assert pred.dim() == 2 and pred.shape[1] == 4 and pred.shape == target.shape, '%s: pred and target [n, 4]' % rule
+        p, t = pred.float().contiguous(), target.float().contiguous()
+        ctx.save_for_backward(p, t)
+        ctx.args = (rule, float(beta), float(eps))
+        return native.box_loss_fwd(rule, p, t, *ctx.args[1:])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_loss):
+        p, t = ctx.saved_tensors
+        return (native.box_loss_bwd(ctx.args[0], p, t, d_loss.float().contiguous(), *ctx.args[1:]),) + (None,) * 4
+
+
+def smooth_l1_loss(pred, target, beta=1.0):
+    """smooth_l1_loss.py:8-18 without the reduction: [N, D]."""
+    return RegLossFunction.apply(pred, target, 'smooth_l1', beta, 0.0, 0.0)
+
+
+def balanced_l1_loss(pred, target, beta=1.0, alpha=0.5, gamma=1.5):
+    """balanced_l1_loss.py:9-27 without the reduction: [N, D]."""
+    return RegLossFunction.apply(pred, target, 'balanced_l1', beta, alpha, gamma)
+
+
+def mse_loss(pred, target):
+    """F.mse_loss(reduction='none'): [N, D]."""
+    return RegLossFunction.apply(pred, target, 'mse', 0.0, 0.0, 0.0)
+
+
+def iou_loss(pred, target, eps=1e-6):
+    """iou_loss.py:9-26 without the reduction: [n]."""
+    return BoxLossFunction.apply(pred, target, 'iou', 0.0, eps)
+
+
+def bounded_iou_loss(pred, target, beta=0.2, eps=1e-3):
+    """iou_loss.py:29-63 without the reduction: [n, 4]."""
+    return BoxLossFunction.apply(pred, target, 'bounded_iou', beta, eps)
+
+
 class SigmoidFocalLoss(nn.Module):
     """sigmoid_focal_loss.py:40-54: forward returns loss.sum()."""
 

@@ -43,6 +43,15 @@ class RPNHead(nn.Module, PackedMixin):
             from . import losses  # noqa: F401  (registers FocalLoss)
             from .registry import build_loss
             self.loss_cls = build_loss(loss_cls)          # validates the dict (use_sigmoid, gamma, alpha, loss_weight) as the reference does
+        # the box loss the head runs: SmoothL1Loss inside the fused RPN loss kernels, BalancedL1Loss through its module beside them
+        # (loss_train); any other type is refused by name instead of being trained as smooth-L1
+        self.loss_bbox_type = loss_bbox.get('type', 'SmoothL1Loss')
+        if self.loss_bbox_type not in ('SmoothL1Loss', 'BalancedL1Loss'):
+            raise NotImplementedError('RPNHead: loss_bbox type %r is not on the HIP path (SmoothL1Loss or BalancedL1Loss)' % (self.loss_bbox_type,))
+        if self.loss_bbox_type == 'BalancedL1Loss':
+            from . import losses  # noqa: F401,F811  (registers the loss modules)
+            from .registry import build_loss
+            self.loss_bbox = build_loss(loss_bbox)
         self.fp16_enabled = False
         self.anchor_generators = [AnchorGenerator(b, anchor_scales, anchor_ratios) for b in self.anchor_base_sizes]
         self.num_anchors = len(self.anchor_ratios) * len(self.anchor_scales)
@@ -134,6 +143,8 @@ class RPNHead(nn.Module, PackedMixin):
         labels, label_w, bbox_t, bbox_w, counts = T.anchor_target_single(anchors, valid, gt_bboxes, img_meta, self.target_means,
                                                                          self.target_stds, cfg, keys=keys, generator=generator,
                                                                          sampling=self.sampling)
+        if self.loss_bbox_type == 'BalancedL1Loss':
+            return self._loss_train_balanced(o_key, labels, label_w, bbox_t, bbox_w, counts)
         if not self.sampling:   # FocalLoss: every assigned anchor, both terms over the positive count (anchor_head.py:194-195)
             fl = self.loss_cls
             if fl.reduction != 'mean':
@@ -145,6 +156,35 @@ class RPNHead(nn.Module, PackedMixin):
             raise NotImplementedError('RPN loss weights other than 1.0')
         return TO.rpn_loss(o_key.reshape(H * W, ld), self.num_anchors, labels, label_w, bbox_t, bbox_w, counts,
                            beta=self.loss_bbox_cfg.get('beta', 1.0))
+
+    def _loss_train_balanced(self, o_key, labels, label_w, bbox_t, bbox_w, counts):
+        """loss_train with loss_bbox type BalancedL1Loss.  The classification term is the fused kernel's own, called with zero box weights
+        (the same bits as under SmoothL1Loss); the box term is the module's reduced kernel on the deltas as the reference hands them over
+        (anchor_head.py:141-160: every anchor's four deltas with bbox_weights, reduction 'mean'), over the reference's avg_factor read on
+        the device: sampled positives + negatives (each at least 1, anchor_target.py:66-67) in the BCE form, the positive count in the
+        focal form."""
+        from . import train_ops as TO
+        H, W, ld = o_key.shape
+        A = self.num_anchors
+        o = o_key.reshape(H * W, ld)
+        zero_w = torch.zeros_like(bbox_w)
+        if not self.sampling:
+            fl = self.loss_cls
+            if fl.reduction != 'mean':
+                raise NotImplementedError('RPNHead: FocalLoss reduction %r (the head averages over the positive count: "mean")' % (fl.reduction,))
+            rl = TO.rpn_focal_loss(o, A, labels, label_w, bbox_t, zero_w, counts, beta=1.0, gamma=fl.gamma, alpha=fl.alpha, w_cls=fl.loss_weight,
+                                   w_bbox=1.0)
+            avg = counts[:1].to(torch.int32).contiguous()
+        else:
+            if self.loss_cls_cfg.get('loss_weight', 1.0) != 1.0:
+                raise NotImplementedError('RPN loss weights other than 1.0')
+            rl = TO.rpn_loss(o, A, labels, label_w, bbox_t, zero_w, counts, beta=1.0)
+            avg = counts[:2].clamp(min=1).sum(dtype=torch.int32).reshape(1)       # anchor_target.py:66-67, formed on the device: two small launches
+        if self.loss_bbox.reduction != 'mean':
+            raise NotImplementedError('RPNHead: BalancedL1Loss reduction %r (the head averages over avg_factor: "mean")' % (self.loss_bbox.reduction,))
+        box = self.loss_bbox(o[:, A:5 * A], bbox_t.reshape(H * W, 4 * A), bbox_w.reshape(H * W, 4 * A), avg_factor=avg)
+        total = torch.stack([rl['total'][0], box])
+        return dict(total=total, loss_rpn_cls=total[0].detach(), loss_rpn_bbox=total[1].detach())
 
     def forward(self, feats):
         outs = [self.forward_single(f) for f in feats]

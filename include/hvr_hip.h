@@ -1011,6 +1011,98 @@ int hvr_rpn_focal_loss(const float* o, int ldo, int A, int rows, const int64_t* 
                        const float* bbox_targets, const float* bbox_weights, const int32_t* counts, float beta, float gamma, float alpha,
                        float w_cls, float w_bbox, float* out2, float* d_o, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Regression and IoU losses (mmdet/models/losses/smooth_l1_loss.py, balanced_l1_loss.py, mse_loss.py, iou_loss.py, with
+ * losses/utils.py weight_reduce_loss).  THE RULES, stated once; all math is f32, every product and sum rounded on its own, with the
+ * device library's logf / log1pf, not the fast intrinsics.
+ * Elementwise family (hvr_reg_*): pred f32 [N][ldp] (row pitch ldp >= D in elements); target, the optional weight, the loss and the
+ * gradient are dense f32 [N][D].  d = pred - target, a = |d|, sign(0) = 0:
+ *   HVR_REG_SMOOTH_L1 (beta):    l = a < beta ? 0.5 a a / beta : a - 0.5 beta          dl/dpred = a < beta ? d / beta : sign(d)
+ *   HVR_REG_BALANCED_L1 (alpha, gamma, beta), b = e^(gamma / alpha) - 1 formed in f64 from the three floats and rounded once:
+ *       a < beta:   l = alpha / b (b a + 1) log(b a / beta + 1) - alpha a
+ *                   dl/dpred = (alpha log(b a / beta + 1) + alpha (1 - beta) / (b a + beta)) sign(d)
+ *       otherwise:  l = gamma a + gamma / b - alpha beta                                dl/dpred = gamma sign(d)
+ *     The gradient is the derivative of l as stated, which is what the reference's autograd gives; its second term vanishes
+ *     (exactly, in f32 too) at beta = 1, where the gradient is the paper's alpha log(b a + 1).
+ *     log(y + 1) is log1pf(y): DEVIATION in the accurate direction (the reference forms y + 1 first and loses y's low bits).
+ *   HVR_REG_MSE:                 l = d d                                                dl/dpred = 2 d
+ *     DEVIATION: the reference's mse_loss wraps F.mse_loss, whose own default reduction averages BEFORE weight_reduce_loss sees the
+ *     elements (mse_loss.py:7), so there only the unweighted 'mean' is the mean of d d; this build applies weight and reduction to the
+ *     elements, as weighted_loss states its contract.
+ *   beta, alpha, gamma are ignored by the rules that do not name them.
+ * Box-pair family (hvr_box_*): pred, target dense f32 [n][4] = x1, y1, x2, y2 with the legacy "+1" widths; gradient [n][4], to pred only.
+ *   HVR_BOX_IOU (eps):  I = max(min(x2) - max(x1) + 1, 0) max(min(y2) - max(y1) + 1, 0), iou = I / (A_pred + A_target - I) as
+ *     bbox_overlaps(is_aligned=True) forms it; l = -log(max(iou, eps)), ONE value and ONE weight per pair (loss, weight: [n]).  The
+ *     gradient is zero where iou < eps; elsewhere dl = dU / U - dI / I.  Where the two sides of a max / min tie, PRED takes the
+ *     gradient.  DEVIATION: a NaN iou (both boxes of zero area) gives l = -log eps with a zero gradient, not NaN.
+ *   HVR_BOX_BOUNDED_IOU (beta, eps):  per axis, with centres c = (x1 + x2) / 2, sizes s = x2 - x1 + 1 and dx = c_t - c_p:
+ *       centre term  1 - max((s_t - 2|dx|) / (s_t + 2|dx| + eps), 0)      size term  1 - min(s_t / (s_p + eps), s_p / (s_t + eps))
+ *     in the order (dx, dy, dw, dh) (iou_loss.py:41-58); each term c goes through c < beta ? 0.5 c c / beta : c - 0.5 beta.  The loss and
+ *     the weight are [n][4], per element.  Ties: the ZERO takes the gradient of the max; the FIRST ratio (s_t / (s_p + eps)) that of the min.
+ * Forms of both families:
+ *   *_fwd : the 'none' loss.      *_bwd : d_pred = dl/dpred * d_loss (d_loss in the loss's shape).
+ *   hvr_reg_loss / hvr_box_loss : the reduced form in ONE pass over the inputs: out1[0] = (sum w l) * (loss_weight / avg) and
+ *     d_pred = (loss_weight / avg * w) dl/dpred, every element written.  w is nullable (all ones); all-zero weights give exactly 0
+ *     through the sum itself (the reference's torch.any early exit would be a host read and is not reproduced).  avg is the host
+ *     float `avg` (> 0), or, when counts_dev (int32, nullable) is given, max(counts_dev[0], 1) read on the device.  The sum follows the
+ *     focal scheme: S = hvr_reg_loss_splits(N, D) / hvr_box_loss_splits(n) workgroups of consecutive rows (a function of the shape
+ *     only, none empty), per-lane partials in row-then-column order, xor shuffles, the four waves through LDS in wave order, ONE f32
+ *     partial per workgroup into ws (S floats: hvr_*_workspace_bytes), the partials merged in workgroup order by one wave.  No float
+ *     atomics: two calls give the same bits.
+ * 16 bytes per lane where pitch and addresses allow, a scalar form otherwise; no host synchronisation and no allocation: every entry
+ * point can be captured in a graph.  N * ldp < 2^31, n < 2^29.
+ * ---------------------------------------------------------------------------------- */
+enum { HVR_REG_SMOOTH_L1 = 0, HVR_REG_BALANCED_L1 = 1, HVR_REG_MSE = 2 };
+enum { HVR_BOX_IOU = 0, HVR_BOX_BOUNDED_IOU = 1 };
+int hvr_reg_loss_fwd(int rule, const float* pred, int ldp, const float* target, int N, int D, float beta, float alpha, float gamma, float* loss,
+                     void* stream);
+int hvr_reg_loss_bwd(int rule, const float* pred, int ldp, const float* target, const float* d_loss, int N, int D, float beta, float alpha,
+                     float gamma, float* d_pred, void* stream);
+int hvr_reg_loss_splits(int N, int D);
+size_t hvr_reg_loss_workspace_bytes(int N, int D);
+int hvr_reg_loss(int rule, const float* pred, int ldp, const float* target, const float* w, int N, int D, float beta, float alpha, float gamma,
+                 float loss_weight, float avg, const int32_t* counts_dev, void* ws, size_t ws_bytes, float* out1, float* d_pred, void* stream);
+int hvr_box_loss_fwd(int rule, const float* pred, const float* target, int n, float beta, float eps, float* loss, void* stream);
+int hvr_box_loss_bwd(int rule, const float* pred, const float* target, const float* d_loss, int n, float beta, float eps, float* d_pred,
+                     void* stream);
+int hvr_box_loss_splits(int n);
+size_t hvr_box_loss_workspace_bytes(int n);
+int hvr_box_loss(int rule, const float* pred, const float* target, const float* w, int n, float beta, float eps, float loss_weight, float avg,
+                 const int32_t* counts_dev, void* ws, size_t ws_bytes, float* out1, float* d_pred, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * GHM losses (mmdet/models/losses/ghm_loss.py GHMC / GHMR).  THE RULES, stated once.  Inputs are dense f32 [N][C], taken as E = N C
+ * elements; the weight is [N][C] (or [N], one per row, when weight_per_row: the labels form below).  An element is VALID iff its
+ * weight is above 0.  Per element:
+ *   GHMC: x the logit, t the target; p = sigmoid(x) in focal's stable forms (e = expf(-|x|), p = 1 / (1 + e) or e / (1 + e));
+ *         g = |p - t|;   term = max(x, 0) - x t + log1pf(expf(-|x|));   slope = p - t.
+ *         t is the float target [N][C], or with int64 labels [N] the rule of _expand_binary_labels: label k >= 1 marks column k - 1.
+ *   GHMR: d = pred - target, r = sqrtf(d d + mu mu);   g = |d / r|;   term = r - mu;   slope = d / r.
+ * `edges` f32 [bins + 1] (1 <= bins <= 64) belongs to the caller; a valid element falls into bin i iff edges[i] <= g < edges[i + 1]
+ * (an element outside every bin counts towards tot and carries no loss).  One call runs three passes and reads nothing on the host:
+ *   0. the counts are zeroed by a one-wave launch of their own (a kernel, not a memset node: the call is meant to be captured).
+ *   1. histogram: counts[i] per workgroup in LDS with integer atomics, one integer atomic per bin and workgroup into counts (exact
+ *      whatever the order).  tot = max(., 1) of: GHMC the NUMBER of valid elements (integer sum); GHMR the SUM OF ALL WEIGHTS, as the
+ *      reference has it (f32, in the deterministic order of the reduced losses over S = hvr_ghm_splits(N, C) workgroups of consecutive
+ *      elements).
+ *   2. finalize, one wave: n = the number of non-empty bins; per non-empty bin, with momentum > 0: acc_sum[i] = momentum acc_sum[i] +
+ *      (1 - momentum) counts[i] IN PLACE and beta_i = tot / acc_sum[i], otherwise beta_i = tot / counts[i]; w[i] = beta_i / n.
+ *      Empty bins leave acc_sum[i] untouched and have w[i] = 0.
+ *   3. loss and gradient in one pass (bin weights are constants of the gradient): out1[0] = loss_weight * (sum w[bin] term) / tot,
+ *      d[e] = loss_weight * w[bin] * slope / tot, zero for invalid elements; the sum as in the reduced losses (one partial per
+ *      workgroup, merged in order by a one-wave launch).
+ * Workspace (hvr_ghm_workspace_bytes), in 4-byte words, left behind for the caller to read: [0, 64) counts int32; [64, 128) w f32;
+ * [128] tot f32; [129] n int32; [192, 192 + S) the workgroups' partials.  No float atomics, no allocation: capturable in a graph (a
+ * replay with momentum > 0 advances acc_sum once).  N C < 2^31.
+ * ---------------------------------------------------------------------------------- */
+int hvr_ghm_splits(int N, int C);
+size_t hvr_ghm_workspace_bytes(int N, int C);
+int hvr_ghmc_loss(const float* logits, const float* target, const int64_t* labels, const float* weight, int weight_per_row, int N, int C,
+                  const float* edges, int bins, float momentum, float* acc_sum, float loss_weight, void* ws, size_t ws_bytes, float* out1,
+                  float* d_logits, void* stream);
+int hvr_ghmr_loss(const float* pred, const float* target, const float* weight, int N, int C, float mu, const float* edges, int bins,
+                  float momentum, float* acc_sum, float loss_weight, void* ws, size_t ws_bytes, float* out1, float* d_pred, void* stream);
+
 /* Frame ingest: decoded BGR uint8 frame src [src_h][src_pitch bytes] (3 bytes per pixel) -> dst f32 [3][pad_h][pad_w]:
  * bilinear resize to new_w x new_h (OpenCV's 8-bit INTER_LINEAR fixed-point arithmetic, which mmcv.imrescale calls), optional
  * BGR->RGB, (x - mean) / std, zero padding -- the reference's Resize -> Normalize -> Pad -> ImageToTensor
