@@ -1,7 +1,7 @@
 """hvrnet_amd -- MI355X-native HVRNet video-detection forward path.
 
 Importing the package registers the hot-path components under the reference's names
-(ResNet, ResNeXt, Res2Net, ResLayer, ResXLayer, Res2Layer, RPNHead, GARPNHead, SingleRoIExtractor, SelsaBBoxHead, HRNMPBBoxHead, SelsaRCNN, HNMBRCNN).
+(ResNet, ResNeXt, Res2Net, ResLayer, ResXLayer, Res2Layer, FPN, RPNHead, GARPNHead, SingleRoIExtractor, SelsaBBoxHead, HRNMPBBoxHead, SelsaRCNN, HNMBRCNN).
 """
 __version__ = '0.1.0'
 
@@ -16,9 +16,10 @@ from .detectors import HNMBRCNN, SelsaRCNN  # noqa: F401
 from .ga_rpn_head import GARPNHead  # noqa: F401
 from . import losses  # noqa: F401
 from .losses import (FocalLoss, SmoothL1Loss, BalancedL1Loss, MSELoss, IoULoss, BoundedIoULoss, GHMC, GHMR)  # noqa: F401
+from .necks import FPN  # noqa: F401
 from .ops import ContextBlock, GeneralizedAttention, MaskedConv2d, RoIPool, masked_conv2d, roi_pool, seq_nms, soft_nms  # noqa: F401
 from .pipelines import FrameIngest, FrameIngestAug  # noqa: F401
-from .registry import build_detector  # noqa: F401
+from .registry import build_detector, build_neck  # noqa: F401
 from .roi_extractor import SingleRoIExtractor  # noqa: F401
 from .rpn_head import RPNHead  # noqa: F401
 

@@ -91,6 +91,10 @@ hipError_t run_deform_roi_pool(const void*, const float*, const float*, const fl
                                float, float, long, long, int, hipStream_t);
 hipError_t run_roi_pool_fwd(const void*, const float*, void*, int32_t*, int, int, int, int, int, int, int, float, int, hipStream_t);
 hipError_t run_roi_pool_bwd(const float*, const float*, const int32_t*, float*, int, int, int, int, int, int, int, hipStream_t);
+hipError_t run_fpn_merge(const void* const*, void* const*, int, int, const int*, const int*, int, int, hipStream_t);
+int roi_align_levels_instance(int C, int dtype);
+hipError_t run_roi_align_levels(const void* const*, const int*, const int*, const float*, int, int, int, int, int, int, int, float, const float*,
+                                const float*, void*, int*, hipStream_t);
 hipError_t run_nms_batched(const float*, int, int, float, int, int, int, long long*, int*, const NmsWs&, hipStream_t, int band = 0,
                            int* band_done = nullptr);
 hipError_t run_rpn_select(const void*, const void*, long, long, float*, const RpnParams&, int, hipStream_t);
@@ -1989,6 +1993,82 @@ int hvr_roi_pool_bwd(const float* grad_out, const float* rois, const int32_t* ar
        reinterpret_cast<uintptr_t>(grad_feat)) & 3)
     return fail(HVR_EINVAL, "hvr_roi_pool_bwd: misaligned pointer");
   return check_launch(run_roi_pool_bwd(grad_out, rois, argmax, grad_feat, B, H, W, C, K, PH, PW, (hipStream_t)stream), "hvr_roi_pool_bwd");
+}
+
+// ---- FPN top-down merge and multi-level RoIAlign (fpn.hip) ----
+static inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + nb && y < x + na;
+}
+
+int hvr_fpn_merge_supported(int L, int C, int dtype) {
+  if (L < 1 || L > HVR_FPN_MAX_LEVELS || C <= 0 || C > 65536) return 0;
+  if (dtype == HVR_F32) return C % 4 == 0;
+  if (dtype == HVR_BF16 || dtype == HVR_F16) return C % 8 == 0;
+  return 0;
+}
+
+int hvr_fpn_merge(const void* const* lat, void* const* out, int L, int B, const int32_t* H, const int32_t* W, int C, int dtype, void* stream) {
+  if (!valid_dtype(dtype)) return fail(HVR_EINVAL, "hvr_fpn_merge: bad dtype %d", dtype);
+  if (L < 1 || B < 0 || C <= 0 || !H || !W || !lat) return fail(HVR_EINVAL, "hvr_fpn_merge: bad shape L=%d B=%d C=%d or a null array", L, B, C);
+  if (!hvr_fpn_merge_supported(L, C, dtype))
+    return fail(HVR_EUNSUPPORTED, "hvr_fpn_merge: no instance for L=%d C=%d dtype=%d (1 <= L <= %d; C a multiple of 16 bytes of channels, "
+                "at most 65536; f32, bf16 or half)", L, C, dtype, HVR_FPN_MAX_LEVELS);
+  if (L > 1 && !out) return fail(HVR_EINVAL, "hvr_fpn_merge: null output array");
+  for (int l = 0; l < L; ++l) {
+    if (H[l] <= 0 || W[l] <= 0) return fail(HVR_EINVAL, "hvr_fpn_merge: level %d is %d x %d", l, H[l], W[l]);
+    if (l + 1 < L && (H[l] != 2 * H[l + 1] || W[l] != 2 * W[l + 1]))
+      return fail(HVR_EINVAL, "hvr_fpn_merge: size mismatch, level %d is %d x %d and level %d is %d x %d (each level is exactly twice the next)",
+                  l, H[l], W[l], l + 1, H[l + 1], W[l + 1]);
+    if ((long)B * H[l] * W[l] >= (1L << 31)) return fail(HVR_EUNSUPPORTED, "hvr_fpn_merge: level %d has 2^31 pixels or more", l);
+  }
+  if (B == 0 || L == 1) return HVR_OK;
+  const size_t es = (size_t)elem_size(dtype);
+  size_t bytes[HVR_FPN_MAX_LEVELS];
+  for (int l = 0; l < L; ++l) {
+    bytes[l] = (size_t)B * H[l] * W[l] * C * es;
+    if (!lat[l] || !aligned16(lat[l])) return fail(HVR_EINVAL, "hvr_fpn_merge: lat[%d] is null or not 16-byte aligned", l);
+    if (l < L - 1 && (!out[l] || !aligned16(out[l]))) return fail(HVR_EINVAL, "hvr_fpn_merge: out[%d] is null or not 16-byte aligned", l);
+  }
+  for (int l = 0; l < L - 1; ++l) {
+    for (int j = 0; j < L; ++j)
+      if (ranges_overlap(out[l], bytes[l], lat[j], bytes[j])) return fail(HVR_EINVAL, "hvr_fpn_merge: out[%d] aliases lat[%d]", l, j);
+    for (int j = l + 1; j < L - 1; ++j)
+      if (ranges_overlap(out[l], bytes[l], out[j], bytes[j])) return fail(HVR_EINVAL, "hvr_fpn_merge: out[%d] aliases out[%d]", l, j);
+  }
+  return check_launch(run_fpn_merge(lat, out, L, B, H, W, C, dtype, (hipStream_t)stream), "hvr_fpn_merge");
+}
+
+int hvr_roi_align_levels_supported(int L, int C, int dtype) {
+  return L >= 1 && L <= HVR_FPN_MAX_LEVELS && C > 0 && roi_align_levels_instance(C, dtype);
+}
+
+int hvr_roi_align_levels_fwd(const hvr_roi_levels_desc* d, void* stream) {
+  if (!d) return fail(HVR_EINVAL, "hvr_roi_align_levels_fwd: null descriptor");
+  if (!valid_dtype(d->dtype)) return fail(HVR_EINVAL, "hvr_roi_align_levels_fwd: bad dtype %d", d->dtype);
+  if (d->dtype == HVR_F16S) return fail(HVR_EUNSUPPORTED, "hvr_roi_align_levels_fwd: no split-half instance (pool in f32 and convert)");
+  if (d->L < 1 || d->L > HVR_FPN_MAX_LEVELS) return fail(HVR_EINVAL, "hvr_roi_align_levels_fwd: L=%d is outside 1 .. %d", d->L, HVR_FPN_MAX_LEVELS);
+  if (d->K < 0 || d->B <= 0 || d->C <= 0 || d->PH <= 0 || d->PW <= 0 || d->sample_num < 0)
+    return fail(HVR_EINVAL, "hvr_roi_align_levels_fwd: bad shape K=%d B=%d C=%d out_size=%d x %d sample_num=%d", d->K, d->B, d->C, d->PH, d->PW,
+                d->sample_num);
+  if (!(d->finest_scale > 0.f)) return fail(HVR_EINVAL, "hvr_roi_align_levels_fwd: finest_scale=%g is not positive", (double)d->finest_scale);
+  for (int l = 0; l < d->L; ++l)
+    if (d->H[l] <= 0 || d->W[l] <= 0 || (long)d->H[l] * d->W[l] >= (1L << 31))
+      return fail(HVR_EINVAL, "hvr_roi_align_levels_fwd: level %d is %d x %d", l, d->H[l], d->W[l]);
+  if (!roi_align_levels_instance(d->C, d->dtype))
+    return fail(HVR_EUNSUPPORTED, "hvr_roi_align_levels_fwd: no instance for C=%d dtype=%d (C a multiple of 4, at most 1024)", d->C, d->dtype);
+  if (d->K == 0) return HVR_OK;
+  if (!d->rois || !d->pool_rois || !d->out) return fail(HVR_EINVAL, "hvr_roi_align_levels_fwd: null pointer");
+  const int al = d->dtype == HVR_F32 ? 15 : 7;   // what the widest load of the body needs when the 16-byte form is not taken
+  for (int l = 0; l < d->L; ++l)
+    if (!d->feat[l] || (reinterpret_cast<uintptr_t>(d->feat[l]) & al))
+      return fail(HVR_EINVAL, "hvr_roi_align_levels_fwd: feat[%d] is null or misaligned", l);
+  if ((reinterpret_cast<uintptr_t>(d->out) & al) || ((reinterpret_cast<uintptr_t>(d->rois) | reinterpret_cast<uintptr_t>(d->pool_rois) |
+                                                      reinterpret_cast<uintptr_t>(d->levels)) & 3))
+    return fail(HVR_EINVAL, "hvr_roi_align_levels_fwd: misaligned pointer");
+  return check_launch(run_roi_align_levels(d->feat, d->H, d->W, d->spatial_scale, d->L, d->C, d->K, d->PH, d->PW, d->sample_num, d->dtype,
+                                           d->finest_scale, d->rois, d->pool_rois, d->out, d->levels, (hipStream_t)stream),
+                      "hvr_roi_align_levels_fwd");
 }
 
 // ---- NMS ----

@@ -52,6 +52,10 @@ RULES = [
     (r'_ZN3hvr\d+(?:reg_elem|box_pair)_', 0, 'reg_loss.hip: a lane keeps 16-byte pieces of pred, target and weight and the four gradients of a box '
      'pair in registers, a spill would sit on the one pass over the inputs'),
     (r'_ZN3hvr\d+ghm_(?:hist|loss)_', 0, 'ghm.hip: two passes over the elements with a library call each, a spill would sit on the pass'),
+    (r'_ZN3hvr\d+fpn_merge_', 0, 'fpn.hip, the top-down merge: a lane keeps the 16-byte pieces of its pixel\'s chain of up to four laterals in '
+     'flight, a spill would sit on the one pass over the maps'),
+    (r'_ZN3hvr\d+roi_align_levels_', 0, 'fpn.hip, RoIAlign behind the level select: the pipelined form keeps a bin\'s 16 corner vectors in flight, '
+     'a spill would sit inside the gather chain the form exists to overlap'),
 ]
 
 # The tile engine (gemm.hip, gemm_f16.hip) is gated by template arguments, not by name alone.  Kernels that use loads the compiler

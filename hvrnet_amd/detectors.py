@@ -89,9 +89,11 @@ class TwoStageDetector(BaseDetector):
     def __init__(self, backbone, neck=None, shared_head=None, rpn_head=None, bbox_roi_extractor=None, bbox_head=None,
                  mask_roi_extractor=None, mask_head=None, train_cfg=None, test_cfg=None, pretrained=None):
         super(TwoStageDetector, self).__init__()
-        if neck is not None or mask_head is not None or mask_roi_extractor is not None:
-            raise NotImplementedError('necks / mask heads are outside the HVR hot path')
+        if mask_head is not None or mask_roi_extractor is not None:
+            raise NotImplementedError('mask_head / mask_roi_extractor: mask heads are outside the HVR hot path')
         self.backbone = registry.build_backbone(backbone)
+        if neck is not None:
+            self.neck = registry.build_neck(neck)
         if shared_head is not None:
             self.shared_head = registry.build_shared_head(shared_head)
         if rpn_head is not None:
@@ -111,6 +113,9 @@ class TwoStageDetector(BaseDetector):
 
     def init_weights(self, pretrained=None):
         self.backbone.init_weights(pretrained=pretrained)
+        if self.with_neck:
+            for m in (self.neck if isinstance(self.neck, nn.Sequential) else [self.neck]):   # two_stage.py:75-80
+                m.init_weights()
         if self.with_shared_head:
             self.shared_head.init_weights(pretrained=pretrained)
         if self.with_rpn:
@@ -126,6 +131,8 @@ class TwoStageDetector(BaseDetector):
         slice of ONE C4 map (frames are independent through the backbone: the chunking changes no result).  (Rounds 1-4 could also
         cut a batch into groups on several HIP streams; it stopped paying in round 2 -- 114.6 vs 114.7 us per layer-3 block -- and was
         removed in round 5.)"""
+        if self.with_neck:   # (several maps come out of the backbone: no chunking; the neck's maps are what the detector sees)
+            return self.neck(self.backbone(img))
         bb = self.backbone
         shape_of = getattr(bb, 'out_shape_nhwc', None)
         if img.is_cuda and img.dim() == 4 and shape_of is not None and shape_of(img.shape[0], img.shape[2], img.shape[3]) is not None:
@@ -230,7 +237,10 @@ class _WindowDetector(TwoStageDetector):
 
     def _train_roi_layer(self):
         """The RoI layer of the training paths: they differentiate through RoIAlign or RoIPool; every other roi_layer (the
-        deformable pooling packs of ops.py) is inference only."""
+        deformable pooling packs of ops.py) is inference only.  A detector with a neck is inference only as a whole."""
+        if self.with_neck:
+            raise NotImplementedError('a detector with a neck (%s) is inference only: training through the neck and the multi-level '
+                                      'RoI extraction is not on the HIP path' % type(self.neck).__name__)
         from . import ops
         if getattr(self.backbone, 'gen_attention', None) is not None:
             # (HNMBRCNN.forward_train would run such a backbone frozen, under no_grad; the block is inference only everywhere, as stated)

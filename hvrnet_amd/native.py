@@ -144,6 +144,18 @@ class GaRpnDesc(ctypes.Structure):           # hvr_ga_rpn_desc
                 ('proposals', ctypes.c_void_p), ('counts', ctypes.c_void_p)]
 
 
+FPN_MAX_LEVELS = 4   # HVR_FPN_MAX_LEVELS
+
+
+class RoiLevelsDesc(ctypes.Structure):       # hvr_roi_levels_desc
+    _fields_ = [('feat', ctypes.c_void_p * FPN_MAX_LEVELS), ('H', ctypes.c_int32 * FPN_MAX_LEVELS), ('W', ctypes.c_int32 * FPN_MAX_LEVELS),
+                ('spatial_scale', ctypes.c_float * FPN_MAX_LEVELS),
+                ('L', ctypes.c_int32), ('B', ctypes.c_int32), ('C', ctypes.c_int32), ('K', ctypes.c_int32), ('PH', ctypes.c_int32),
+                ('PW', ctypes.c_int32), ('sample_num', ctypes.c_int32), ('dtype', ctypes.c_int32),
+                ('finest_scale', ctypes.c_float),
+                ('rois', ctypes.c_void_p), ('pool_rois', ctypes.c_void_p), ('out', ctypes.c_void_p), ('levels', ctypes.c_void_p)]
+
+
 # every symbol include/hvr_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _f, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
 SYMBOLS = {
@@ -240,6 +252,10 @@ SYMBOLS = {
     'hvr_deform_roi_pool_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i64, _i64, _i, _vp]),
     'hvr_roi_pool_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     'hvr_roi_pool_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'hvr_fpn_merge_supported': (_i, [_i, _i, _i]),
+    'hvr_fpn_merge': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp]),
+    'hvr_roi_align_levels_supported': (_i, [_i, _i, _i]),
+    'hvr_roi_align_levels_fwd': (_i, [ctypes.POINTER(RoiLevelsDesc), _vp]),
     'hvr_gcb_supported': (_i, [_i, _i]),
     'hvr_gcb_splits': (_i, [_i, _i, _i]),
     'hvr_gcb_workspace_bytes': (_sz, [_i, _i, _i]),
@@ -2046,6 +2062,133 @@ def roi_pool_bwd(grad_out_nhwc, rois, argmax, feat_shape_nhwc):
     grad_in = torch.zeros((B, H, W, C), dtype=torch.float32, device=grad_out.device)
     _check(lib().hvr_roi_pool_bwd(_ptr(grad_out), _ptr(rois), _ptr(argmax), _ptr(grad_in), B, H, W, C, K, PH, PW, _stream()), 'hvr_roi_pool_bwd')
     return grad_in
+
+
+# ---- the multi-level feature path (csrc/fpn.hip; the rules: include/hvr_hip.h)
+def fpn_merge_supported(L, C, dtype):
+    """True when hvr_fpn_merge takes L laterals of C channels in the compute format `dtype` (split half: its laterals arrive as f32)."""
+    code = HVR_F32 if dtype == SPLIT else DTYPE_CODES.get(dtype)
+    return code is not None and bool(lib().hvr_fpn_merge_supported(int(L), int(C), code))
+
+
+def fpn_merge(laterals, out=None):
+    """The FPN top-down pass in one launch (hvr_fpn_merge): laterals [B,H_l,W_l,C] physical NHWC, finest first, each level exactly twice
+    the next; f32, bf16 or half (split-half laterals arrive as f32: the lateral convs hand them over with out_f32) -> the list of
+    merged maps, lat[l] + the nearest-neighbour upsampled merged map of level l + 1, summed in f32 from the coarsest level inwards
+    and rounded once.  The last entry IS the last input.  out: the L - 1 tensors to write into (none may alias an input).
+    Byte model of the span: every lateral read once (the coarse re-reads hit L2), every output written once."""
+    laterals = list(laterals)
+    _need_cuda(*laterals)
+    L = len(laterals)
+    if L < 1:
+        raise HvrError('fpn_merge needs at least one lateral')
+    t0 = laterals[0]
+    for t in laterals:
+        assert t.dim() == 4 and t.is_contiguous(), (tuple(t.shape), t.stride())
+        if t.dtype != t0.dtype or t.shape[0] != t0.shape[0] or t.shape[3] != t0.shape[3] or t.device != t0.device:
+            raise HvrError('fpn_merge: the laterals differ in dtype, batch, channels or device: %s'
+                           % ([(tuple(x.shape), x.dtype) for x in laterals],))
+    if t0.dtype == SPLIT:
+        raise HvrError('fpn_merge: split-half laterals arrive as f32 (conv2d_nhwc(..., out_f32=True)); merge those and cast once')
+    B, _, _, C = t0.shape
+    if out is None:
+        outs = [torch.empty_like(t) for t in laterals[:-1]]
+    else:
+        outs = list(out)
+        assert len(outs) == L - 1, (len(outs), L)
+        for o, t in zip(outs, laterals):
+            assert tuple(o.shape) == tuple(t.shape) and o.dtype == t.dtype and o.is_contiguous() and o.device == t.device, (tuple(o.shape), o.dtype)
+    lat_p = (ctypes.c_void_p * L)(*[t.data_ptr() for t in laterals])
+    out_p = (ctypes.c_void_p * L)(*([o.data_ptr() for o in outs] + [None]))
+    Hs = (ctypes.c_int32 * L)(*[t.shape[1] for t in laterals])
+    Ws = (ctypes.c_int32 * L)(*[t.shape[2] for t in laterals])
+    work = float((sum(t.numel() for t in laterals) + sum(o.numel() for o in outs)) * t0.element_size())
+    with _span('fpn_merge', work):
+        _check(lib().hvr_fpn_merge(lat_p, out_p, L, B, Hs, Ws, C, _dt(t0), _stream()), 'hvr_fpn_merge')
+    return outs + [laterals[-1]]
+
+
+def roi_levels(rois, num_levels, finest_scale=56):
+    """map_roi_levels (single_level.py:55-73) with torch's own expressions: the levels `route='composite'` pools by."""
+    scale = torch.sqrt((rois[:, 3] - rois[:, 1] + 1) * (rois[:, 4] - rois[:, 2] + 1))
+    lv = torch.floor(torch.log2(scale / finest_scale + 1e-6))
+    return torch.nan_to_num(lv, nan=0.0).clamp(min=0, max=num_levels - 1).long()   # (a NaN scale: level 0, the kernel's choice)
+
+
+def roi_rescale(rois, scale_factor):
+    """roi_rescale (single_level.py:75-87), the reference's expressions."""
+    cx = (rois[:, 1] + rois[:, 3]) * 0.5
+    cy = (rois[:, 2] + rois[:, 4]) * 0.5
+    w = rois[:, 3] - rois[:, 1] + 1
+    h = rois[:, 4] - rois[:, 2] + 1
+    new_w = w * scale_factor
+    new_h = h * scale_factor
+    x1 = cx - new_w * 0.5 + 0.5
+    x2 = cx + new_w * 0.5 - 0.5
+    y1 = cy - new_h * 0.5 + 0.5
+    y2 = cy + new_h * 0.5 - 0.5
+    return torch.stack((rois[:, 0], x1, y1, x2, y2), dim=-1)
+
+
+ROI_LEVELS_COMPOSITE_SHAPES = frozenset()   # (L, C, K, dtype) at which route=None takes the composite: none measured slower on the one launch
+
+
+def roi_align_levels(feats, rois, out_size, scales, finest_scale=56, sample_num=2, roi_scale_factor=None, with_levels=False, out=None,
+                     route=None):
+    """RoIAlign over up to four maps in one launch (hvr_roi_align_levels_fwd): feats [B,H_l,W_l,C] physical NHWC, finest first, rois
+    [K,5], scales the levels' spatial scales -> out [K,oh,ow,C] of the maps' dtype, or (out, levels [K] int32) with with_levels.
+    Each RoI is pooled on the level its size selects (the rule: include/hvr_hip.h) with the arithmetic of roi_align_fwd on that map.
+    roi_scale_factor: the levels come from `rois`, the rescaled boxes (the reference's expressions, roi_rescale) are pooled.
+    Split-half maps go through f32 and back, as roi_align_fwd does.  out: a contiguous tensor of the result's shape and dtype.
+    route: None / 'kernel' the one launch; 'composite' the reference's loop over the levels on roi_align_fwd, host reads included
+    (tests and tools/fpn_bench.py).
+    Byte model of the span: the maps once (taps re-read hit L2), out written once, the rois once."""
+    feats = list(feats)
+    L = len(feats)
+    if not 1 <= L <= FPN_MAX_LEVELS:
+        raise HvrError('roi_align_levels takes 1 .. %d maps, got %d' % (FPN_MAX_LEVELS, L))
+    if len(scales) != L:
+        raise HvrError('roi_align_levels: %d maps but %d scales' % (L, len(scales)))
+    if route not in (None, 'kernel', 'composite'):
+        raise HvrError("roi_align_levels: route %r (None, 'kernel' or 'composite')" % (route,))
+    _need_cuda(rois, *feats)
+    if feats[0].dtype == SPLIT:
+        assert out is None
+        r = roi_align_levels([cast(f, torch.float32) for f in feats], rois, out_size, scales, finest_scale, sample_num, roi_scale_factor,
+                             with_levels, None, route)
+        return (cast(r[0], SPLIT), r[1]) if with_levels else cast(r, SPLIT)
+    out_h, out_w = (out_size, out_size) if isinstance(out_size, int) else out_size
+    rois = rois.contiguous().float()
+    assert rois.dim() == 2 and rois.shape[1] == 5, tuple(rois.shape)
+    f0 = feats[0]
+    for f in feats:
+        assert f.dim() == 4 and f.is_contiguous(), (tuple(f.shape), f.stride())
+        if f.dtype != f0.dtype or f.shape[0] != f0.shape[0] or f.shape[3] != f0.shape[3] or f.device != f0.device:
+            raise HvrError('roi_align_levels: the maps differ in dtype, batch, channels or device: %s' % ([(tuple(x.shape), x.dtype) for x in feats],))
+    B, _, _, C = f0.shape
+    K = rois.shape[0]
+    pool_rois = rois if roi_scale_factor is None else roi_rescale(rois, roi_scale_factor).contiguous()
+    out = _out(out, (K, int(out_h), int(out_w), C), f0.dtype, f0.device)
+    if route is None and (L, C, K, f0.dtype) in ROI_LEVELS_COMPOSITE_SHAPES:
+        route = 'composite'
+    if route == 'composite':
+        lv = roi_levels(rois, L, finest_scale)
+        out.zero_()
+        for i in range(L):
+            inds = lv == i
+            if inds.any():
+                out[inds] = roi_align_fwd(feats[i], pool_rois[inds, :], out_h, out_w, scales[i], sample_num, LAYOUT_NHWC)
+        return (out, lv.int()) if with_levels else out
+    levels = torch.empty((K,), dtype=torch.int32, device=f0.device) if with_levels else None
+    d = RoiLevelsDesc(L=L, B=B, C=C, K=K, PH=int(out_h), PW=int(out_w), sample_num=int(sample_num), dtype=_dt(f0),
+                      finest_scale=float(finest_scale), rois=rois.data_ptr(), pool_rois=pool_rois.data_ptr(), out=out.data_ptr(),
+                      levels=levels.data_ptr() if levels is not None else None)
+    for i, f in enumerate(feats):
+        d.feat[i], d.H[i], d.W[i], d.spatial_scale[i] = f.data_ptr(), f.shape[1], f.shape[2], float(scales[i])
+    work = float((sum(f.numel() for f in feats) + out.numel()) * f0.element_size() + rois.numel() * 4)
+    with _span('roi_align_levels', work):
+        _check(lib().hvr_roi_align_levels_fwd(ctypes.byref(d), _stream()), 'hvr_roi_align_levels_fwd')
+    return (out, levels) if with_levels else out
 
 
 # ---- global context block (csrc/gcb.hip; the rule: include/hvr_hip.h)

@@ -77,6 +77,10 @@ def build_backbone(cfg):
     return build(cfg, BACKBONES)
 
 
+def build_neck(cfg):
+    return build(cfg, NECKS)
+
+
 def build_roi_extractor(cfg):
     return build(cfg, ROI_EXTRACTORS)
 

@@ -670,6 +670,68 @@ int hvr_roi_pool_bwd(const float* grad_out, const float* rois, const int32_t* ar
                      int PH, int PW, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * FPN top-down merge, one launch, out of place.  Replaces the L - 1 steps
+ *   laterals[i - 1] += F.interpolate(laterals[i], scale_factor=2, mode='nearest')
+ * of mmdet/models/necks/fpn.py:117-120 (an upsample launch and an add launch each).
+ *   lat[l]   [B][H[l]][W[l]][C]   physical NHWC, `dtype` = HVR_F32 / HVR_BF16 / HVR_F16, l = 0 (finest) .. L - 1 (coarsest)
+ *   out[l]   [B][H[l]][W[l]][C]   `dtype`, for l < L - 1; out[L - 1] is never read: the top level's merged map is its lateral
+ * lat, out, H, W are host arrays of L entries.  H[l] == 2 * H[l + 1] and W[l] == 2 * W[l + 1] exactly (what scale_factor=2 produces;
+ * the reference raises on anything else).  The rule, in f32:
+ *   m[L - 1]            = lat[L - 1]
+ *   m[j][b][h][w][c]    = lat[j][b][h][w][c] + m[j + 1][b][h >> 1][w >> 1][c]
+ *   out[l][b][h][w][c]  = lat[l][b][h][w][c] + m[l + 1][b][h >> 1][w >> 1][c]        rounded to `dtype` ONCE
+ * i.e. the sum is associated from the coarsest level inwards, the reference's order, and no level reads another level's rounded
+ * output (the composite rounds a 16-bit level once per add, up to three times at L = 4; in f32 both give the same bits).
+ * 16 bytes of channels per lane, no atomics, no workspace, no host synchronisation; workgroups need no order.
+ * Instances (hvr_fpn_merge_supported answers 1 / 0): 1 <= L <= HVR_FPN_MAX_LEVELS; C a multiple of 8 (2-byte dtypes) / of 4 (f32), at most
+ * 65536; not split half (merge the f32 laterals).  Outside the set: HVR_EUNSUPPORTED.  A size mismatch, a non-positive size, a null
+ * or not 16-byte aligned map, or an out[l] whose bytes overlap any lat[j] or another out[j]: HVR_EINVAL.  Every refusal comes before
+ * any launch and nothing is written.  L == 1 or B == 0 succeeds without a launch.
+ * ---------------------------------------------------------------------------------- */
+#define HVR_FPN_MAX_LEVELS 4
+int hvr_fpn_merge_supported(int L, int C, int dtype);
+int hvr_fpn_merge(const void* const* lat, void* const* out, int L, int B, const int32_t* H, const int32_t* W, int C, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * RoIAlign over up to four NHWC maps of one batch in ONE launch: each RoI is pooled on the map its size selects.  Replaces the loop
+ * of mmdet/models/roi_extractors/single_level.py:89-107 (map_roi_levels :55-73, one `inds.any()` host read per level, gather, pool,
+ * scatter into a zeroed output).  No host read, no workspace, no zero-fill pass; a level without RoIs costs nothing.
+ * Level of RoI k, from rois[k] = (b, x1, y1, x2, y2), in f32, every operation rounded on its own (no fused multiply-add; the
+ * division and the square root correctly rounded):
+ *   w = (x2 - x1) + 1
+ *   h = (y2 - y1) + 1
+ *   s = sqrt(w * h)
+ *   v = s / finest_scale + 1e-6f
+ *   level = [v >= 2] + [v >= 4] + ... + [v >= 2^(L-1)]
+ * This is floor(log2(v)) clamped to [0, L - 1] without a transcendental.  It differs from torch's own evaluation only where torch's
+ * log2f rounds a value just below a power of two up to it: on a CPU with finest_scale = 56 that happened in 1 of 2 000 000 random
+ * float boxes, in 0 of 2 000 000 integer-sized boxes and in none of the boundary boxes (squares of side 56 * 2^k, 112 x 111,
+ * 111 x 113, 224 x 224, 223 x 225).  A NaN v (exactly one side negative) fails every comparison: level 0.  (The reference's
+ * .long() of NaN is platform-defined: no level on the CPU, level 0 on CUDA.)
+ * Pooling: out[k] is what hvr_roi_align_fwd writes for pool_rois[k] (layout NHWC) on map `level` with that level's H, W and
+ * spatial_scale -- the same device code, bit for bit, the sample_num == 2 form of the 2-byte dtypes included.  pool_rois == rois
+ * unless the boxes are rescaled for pooling (roi_scale_factor); the batch index of pool_rois[k] selects the frame and must lie in
+ * [0, B), as for hvr_roi_align_fwd.
+ * Instances (hvr_roi_align_levels_supported answers 1 / 0): 1 <= L <= HVR_FPN_MAX_LEVELS, dtype HVR_F32 / HVR_BF16 / HVR_F16 (split half:
+ * HVR_EUNSUPPORTED, pool in f32), C a multiple of 4 up to 1024 -- the set of the single-map call.  Maps and out 16-byte aligned
+ * (2-byte dtypes: 8-byte; the 16-byte form is taken when all are 16-byte aligned), rois / pool_rois / levels 4-byte.  Bad shapes,
+ * null or misaligned pointers, finest_scale <= 0: HVR_EINVAL, before any launch.  K == 0 succeeds without a launch.
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+  const void* feat[HVR_FPN_MAX_LEVELS];      /* [B][H[l]][W[l]][C], entries l >= L ignored */
+  int32_t H[HVR_FPN_MAX_LEVELS], W[HVR_FPN_MAX_LEVELS];
+  float spatial_scale[HVR_FPN_MAX_LEVELS];   /* 1 / stride of the level */
+  int32_t L, B, C, K, PH, PW, sample_num, dtype;
+  float finest_scale;                        /* 56 in the reference's configs */
+  const float* rois;                         /* [K][5] decide the level */
+  const float* pool_rois;                    /* [K][5] are pooled (== rois without a roi_scale_factor) */
+  void* out;                                 /* [K][PH][PW][C] */
+  int32_t* levels;                           /* [K] or NULL: the level of every RoI */
+} hvr_roi_levels_desc;
+int hvr_roi_align_levels_supported(int L, int C, int dtype);
+int hvr_roi_align_levels_fwd(const hvr_roi_levels_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Greedy NMS.  Replaces nms_cpu.nms / nms_cuda.nms (mmdet/ops/nms/src/nms_cpu.cpp:5-71,
  * nms_kernel.cu:24-136) with no host round trip.  dets [n][5] f32 (x1,y1,x2,y2,score);
  * ge_semantics != 0 suppresses at IoU >= thr (the CPU reference), 0 at IoU > thr (the CUDA
